@@ -5,14 +5,19 @@
                                                           environment launches its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py ... --full                            (+ B = 10 point, roofline, CPU baseline)
+  python bench.py ... --dump-outputs DIR                (+ the last timed step's results as DIR/*.npy)
 
 One "step" = SexAnonymizationTraining.fit_batch on one synthetic 16 kHz batch per rank (weak
 scaling): Fbank x2 + InputNormalization x2 + ConvAutoencoder fwd + L1 recon / NLL losses +
 backward + clip_grad_norm_(5.0) + Adam + Noam (+ SyncBN statistic and gradient all-reduce on
 N > 1).  Workload = BASELINE.json configs[1]: recon 0.1 + sex 0.9 adversarial, shape M of
-SURVEY.md 8(d): B utterances of 161 120 samples -> T = 1008 frames each (B = 32 is `value`; the
-B = 10 point of the same config is reported under config.b10).  Inputs are resident in HBM when
-the timed region starts.  Prints ONE JSON line on rank 0.
+SURVEY.md 8(d): B utterances of 161 120 samples -> T = 1008 frames each (B = 32 is `value`).
+Inputs are resident in HBM when the timed region starts.  Prints ONE JSON line on rank 0.
+
+A plain run measures `value` and nothing else.  --full adds what takes measurements of its own:
+the B = 10 point of the same config (config.b10), the HIP-event roofline of the dominant kernel
+family (roofline, roofline_family) and the CPU oracle baseline (cpu_baseline).
 """
 import argparse
 import json
@@ -48,8 +53,13 @@ def parse_args(argv=None):
                          "the mode that passes the 1e-4 parity tests; bf16: bf16 storage, single MFMA")
     ap.add_argument("--samples", type=int, default=N_SAMPLES,
                     help="waveform samples per utterance (default 161120 = shape M; 480000 = the 30 s shape XL)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-b10", action="store_true", help="skip the secondary B = 10 measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure config.b10, the roofline of the dominant kernel family and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss terms and the model state it "
+                         "updated (parameters, buffers, normaliser statistics) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-b10", action="store_true", help="with --full: skip the secondary B = 10 measurement")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launcher / rendezvous / max-over-ranks timing / JSON relay with the train step "
                          "replaced by a sleep (CPU test of the N > 1 path; the line says so, it is NOT a measurement)")
@@ -57,9 +67,10 @@ def parse_args(argv=None):
                     help="replay the captured hipGraph of the step instead of launching eagerly (N = 1 only). "
                          "GPU time is the same (B = 32: 9.12-9.14 vs 9.04-9.10 ms); what differs is the host: "
                          "~190 launches per step cost 4-8 ms of host time depending on the box, 0.15 ms as a "
-                         "replay.  Default: B = 32 eager (its kernels are timed live with HIP events), replay "
-                         "only if the eager region turns out host-bound on this box; the B = 10 block, which "
-                         "eager cannot keep GPU-bound (3.8 ms of GPU work per step), as a replay")
+                         "replay.  Default: B = 32 eager (with --full its kernels are timed live with HIP "
+                         "events), replay only if the eager region turns out host-bound on this box; the B = 10 "
+                         "block of --full, which eager cannot keep GPU-bound (3.8 ms of GPU work per step), as a "
+                         "replay")
     ap.add_argument("--no-graph", action="store_true", help="never replay a hipGraph (eager everywhere)")
     ap.add_argument("--dp-graph", action="store_true",
                     help="allow the hipGraph replay with more than one rank too (the RCCL all-reduces are "
@@ -205,10 +216,29 @@ def cpu_baseline():
                       f"frames, {warm} warm-up + median of {steps} timed steps"}
 
 
-def run_config(args, batch_size, rank, world, device, profile_key=None, graph=None):
+def step_outputs(brain, loss):
+    """what a caller of fit_batch holds after the last step: the loss it returned, the loss's two
+    terms, and the state the step updated (every parameter and buffer of the modules, the
+    normaliser's running statistics included), as float32 host arrays keyed by name (~2 MB)"""
+    out = {"loss": loss, "recon_loss": brain.last_losses["recon"], "sex_loss": brain.last_losses["sex"]}
+    out.update(brain.modules.named_parameters())
+    out.update(brain.modules.named_buffers())
+    return {k: t.detach().float().cpu().numpy() for k, t in out.items()}
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    note(f"{len(outputs)} arrays ({sum(a.nbytes for a in outputs.values()) / 1e6:.1f} MB) written to {path}")
+
+
+def run_config(args, batch_size, rank, world, device, profile_key=None, graph=None, dump=False):
     """SETUP_STEPS + args.warmup un-timed steps, then EXACTLY args.steps timed steps between
     barrier + synchronize on both sides; returns (elapsed max over ranks, last loss, profile of the
-    dominant kernel, graph mode, host time spent issuing one step)."""
+    dominant kernel, graph mode, host time spent issuing one step, step_outputs of the last timed
+    step if `dump` else None)."""
     import torch
     from speech_anonymization_amd import ops
     ops.conv_impl(pingpong=args.conv_impl == "pingpong", ws=args.conv_impl == "default",
@@ -244,6 +274,7 @@ def run_config(args, batch_size, rank, world, device, profile_key=None, graph=No
     sync_all()
     elapsed = time.perf_counter() - t0
     host_ms = host_issue / args.steps * 1e3
+    outputs = step_outputs(brain, loss) if dump else None      # before any un-timed step below
     prof = ops.PROFILE.collect() if profile_key and not graph else None
     loss = float(loss)
     if profile_key and graph:
@@ -268,7 +299,7 @@ def run_config(args, batch_size, rank, world, device, profile_key=None, graph=No
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt)
-    return elapsed, loss, prof, graph, host_ms
+    return elapsed, loss, prof, graph, host_ms, outputs
 
 
 def roofline_of(prof, dtype):
@@ -383,8 +414,10 @@ def main(argv=None):
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
 
-    elapsed, loss, prof, graph, host_b = run_config(args, args.batch, rank, world, device,
-                                                    profile_key="conv_gemm(128,128,1,1)")
+    dump = args.dump_outputs is not None and rank == 0
+    elapsed, loss, prof, graph, host_b, outputs = run_config(
+        args, args.batch, rank, world, device, profile_key="conv_gemm(128,128,1,1)" if args.full else None,
+        dump=dump)
     eager_ms = None
     if (world == 1 and not graph and not args.no_graph
             and host_b > 0.9 * elapsed / args.steps * 1e3):
@@ -394,26 +427,28 @@ def main(argv=None):
         # stays the one taken live in the eager region (its duration does not depend on who issued it)
         note(f"eager region host-bound ({host_b:.2f} ms issue / {elapsed / args.steps * 1e3:.2f} ms step): replaying as hipGraph")
         try:
-            e2, l2, _, _, h2 = run_config(args, args.batch, rank, world, device, graph=True)
+            e2, l2, _, _, h2, o2 = run_config(args, args.batch, rank, world, device, graph=True, dump=dump)
         except Exception as exc:                      # the eager measurement above stands
             note(f"hipGraph replay failed ({type(exc).__name__}: {exc}); keeping the eager region")
             e2 = float("inf")
         if e2 < elapsed:
-            eager_ms, elapsed, loss, graph, host_b = elapsed / args.steps * 1e3, e2, l2, True, h2
+            eager_ms, elapsed, loss, graph, host_b, outputs = elapsed / args.steps * 1e3, e2, l2, True, h2, o2
     frames = world * args.batch * T * args.steps
     value = frames / elapsed
     if rank == 0:
         note(f"B={args.batch}: {value:.4g} frames/s, {elapsed / args.steps * 1e3:.3f} ms/step")
+    if dump:
+        write_outputs(outputs, args.dump_outputs)
     b10 = None
-    if not args.no_b10 and args.batch != 10 and args.samples == N_SAMPLES:
+    if args.full and not args.no_b10 and args.batch != 10 and args.samples == N_SAMPLES:
         g10_want = False if args.no_graph else (True if (world == 1 or args.dp_graph) else None)
         try:
-            e10, l10, _, g10, host10 = run_config(args, 10, rank, world, device, graph=g10_want)
+            e10, l10, _, g10, host10, _ = run_config(args, 10, rank, world, device, graph=g10_want)
         except Exception as exc:
             if not g10_want:
                 raise
             note(f"hipGraph replay failed at B=10 ({type(exc).__name__}: {exc}); eager")
-            e10, l10, _, g10, host10 = run_config(args, 10, rank, world, device, graph=False)
+            e10, l10, _, g10, host10, _ = run_config(args, 10, rank, world, device, graph=False)
         b10 = {"batch_per_gpu": 10, "value": world * 10 * T * args.steps / e10, "unit": "frames/s",
                "ms_per_step": e10 / args.steps * 1e3, "host_issue_ms_per_step": host10,
                "hip_graph": bool(g10), "loss": l10}
@@ -430,7 +465,7 @@ def main(argv=None):
             "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "setup_steps": SETUP_STEPS,
             "ms_per_step": elapsed / args.steps * 1e3, "host_issue_ms_per_step": host_b, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "ranks_seen": ranks_seen, "backend": backend, "hip_graph": graph,
             "eager_ms_per_step": eager_ms,     # set when the eager region was host-bound and the K steps were re-timed as a replay
             "config": {"workload": "ConvAE recon0.1+sex0.9 adversarial train step (L1 recon + NLL), "
@@ -446,7 +481,7 @@ def main(argv=None):
                                                    "frac_mfma", "algorithmic_bytes", "algorithmic_flops", "traffic")}
                                 for r in roofs],
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -173,6 +173,33 @@ def test_entry_script_config1_plumbing(tmp_path):
         os.listdir(out / "save" / ck[-1]))
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full times the headline configuration only, and --dump-outputs writes
+    the last timed step's loss and the model state it left as float32 .npy files"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--batch", "2", "--samples", str(36 * 160 * 2 - 160),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["full"] is False
+    assert rec["config"]["b10"] is None and rec["roofline"] is None and "cpu_baseline" not in rec
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert float(arrays["loss"]) == rec["config"]["loss"]
+    assert {"recon_loss", "sex_loss", "ConvAE.encoder.0.weight", "normalize.state"} <= set(arrays)
+    assert all(np.isfinite(a).all() for a in arrays.values())
+
+
 def test_fused_clip_takes_the_buckets_only_when_every_gradient_lives_there():
     """Brain._grad_flats: after a plain backward every .grad is a view of the three stage buckets (the two-launch
     clip applies); with a frozen stage, a frozen single parameter or an accumulated second backward it does not

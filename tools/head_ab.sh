@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/head_ab}; mkdir -p $OUT
 for rep in 1 2; do
   for fh in 1 0; do
-    SA_FUSED_HEAD=$fh timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_fh${fh}_$rep.json 2> $OUT/bench_fh${fh}_$rep.err
+    SA_FUSED_HEAD=$fh timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_fh${fh}_$rep.json 2> $OUT/bench_fh${fh}_$rep.err
     python3 - <<PY
 import json
 d = json.load(open("$OUT/bench_fh${fh}_$rep.json"))
