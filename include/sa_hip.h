@@ -279,8 +279,10 @@ int sa_reduce_finalize(const SaFinArgs* a, void* stream);
  * [nbatch][C] per record). */
 /* clip_grad_norm_(params, max_norm) of speechbrain's check_gradients (speechbrain_convae_train.py:249) on up to
  * SA_FLATS_MAX flat fp32 gradient buffers (the stage buckets of a backward): total = sqrt(sum g^2),
- * coef = min(1, max_norm / (total + eps)), g *= coef; partials: fp64 scratch [SA_FLATS_MAX * 64]; total_norm
- * (optional) receives the norm.  Two launches. */
+ * coef = min(1, max_norm / (total + eps)), g *= coef, with torch's clamp(max=1) on non-finite values: a NaN norm
+ * gives a NaN coef (every element NaN), an inf norm coef 0 (finite elements 0, infinite ones NaN); g is left
+ * untouched only when coef >= 1.  partials: fp64 scratch [SA_FLATS_MAX * 64]; total_norm (optional) receives
+ * the norm.  Two launches. */
 #define SA_FLATS_MAX 4
 typedef struct SaFlat { float* p; long long n; } SaFlat;
 typedef struct SaFlats { int n, pad_; SaFlat f[SA_FLATS_MAX]; } SaFlats;

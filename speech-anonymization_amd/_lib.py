@@ -143,7 +143,8 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         for s in SYMBOLS:
             getattr(_lib, s).restype = C.c_int
-        for i, rec in enumerate((SaConvArgs, SaWgradArgs, SaEwArgs, SaPackDesc, SaTaps, SaFinArgs, SaBiasMulti, SaWredMulti)):
+        for i, rec in enumerate((SaConvArgs, SaWgradArgs, SaEwArgs, SaPackDesc, SaTaps, SaFinArgs, SaBiasMulti, SaWredMulti,
+                                    SaFlats)):
             if _lib.sa_abi_sizeof(i) != C.sizeof(rec):
                 raise SaHipError(f"{rec.__name__}: binding has {C.sizeof(rec)} bytes, {LIB_PATH} "
                                  f"{_lib.sa_abi_sizeof(i)} -- rebuild the library (stale build?)")

@@ -329,7 +329,12 @@ class Brain:
                 if self.gc_freeze and self.step == self.GC_FREEZE_STEP and not self.__dict__.get("_gc_frozen"):
                     settle_python_heap()
                     self._gc_frozen = True
-            self.avg_train_loss = float(self.avg_train_loss)          # the epoch's one host read
+            # the epoch's one host read waits for the GPU anyway: drain the lazy non-finite counter with it, so
+            # that a non-finite loss on the epoch's last steps counts against this epoch, not the next one
+            self.nonfinite_count += self._poll_nonfinite(wait=True)
+            if self.nonfinite_count > self.nonfinite_patience:
+                raise ValueError("Loss is not finite and patience is exhausted.")
+            self.avg_train_loss = float(self.avg_train_loss)
             self.on_stage_end(Stage.TRAIN, self.avg_train_loss, epoch)
             if valid_set is not None:
                 self.on_stage_start(Stage.VALID, epoch)

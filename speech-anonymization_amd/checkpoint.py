@@ -139,6 +139,8 @@ class Checkpointer:
             kv = dict(ln.split(": ", 1) for ln in open(bfn).read().strip().splitlines() if ": " in ln)
             brain.avg_train_loss = float(kv.get("avg_train_loss", 0.0))
             brain.step = int(kv.get("step", 0))
+        opt = self.recoverables.get("optimizer")
+        flags = self._run_flags(opt) if hasattr(opt, "param_groups") else None
         for key, obj in self.recoverables.items():
             fn = os.path.join(path, f"{key}.ckpt")
             if not os.path.exists(fn):
@@ -148,31 +150,42 @@ class Checkpointer:
             else:
                 obj.load_state_dict(torch.load(fn, map_location=device or "cpu", weights_only=True))
         if brain is not None and "optimizer" in self.recoverables:
-            self._rebind_optimizer(brain)
+            self._rebind_optimizer(brain, flags)
         return path
 
+    # per-group flags that say how THIS run's optimizer steps (fused kernel, foreach, device-side step
+    # counts); Optimizer.load_state_dict copies the checkpoint's groups over them wholesale
+    RUN_FLAGS = ("fused", "foreach", "capturable")
+
+    @classmethod
+    def _run_flags(cls, opt):
+        return [{k: g[k] for k in cls.RUN_FLAGS if k in g} for g in opt.param_groups]
+
     @staticmethod
-    def _rebind_optimizer(brain):
+    def _rebind_optimizer(brain, flags=None):
         """optimizer.load_state_dict replaces the param_groups wholesale: a checkpoint written by an
         eager run carries lr as a Python float and capturable=False, one written in hipGraph mode a
-        device tensor and capturable=True.  Put the groups back into the form THIS run's mode needs
-        (and Noam's host copy of the rate), whichever mode wrote the checkpoint."""
+        device tensor and capturable=True, and either one its writer's fused / foreach flags.  Put the
+        groups back into the form THIS run needs -- its own flags (`flags`, recorded before the load),
+        lr in its mode's form, Noam's host copy of the rate -- whichever run wrote the checkpoint, and
+        every Adam step count where the restored flags need it: on the parameter's device for the
+        fused and the capturable step, on the host for the plain one."""
         opt = brain.optimizer
         if opt is None:
             return
-        for g in opt.param_groups:
+        for i, g in enumerate(opt.param_groups):
+            if flags is not None:
+                g.update(flags[i])
             lr = float(g["lr"])
             opt._sa_host_lr = lr
             if getattr(brain, "hip_graph", False):
                 g["lr"] = torch.tensor(lr, dtype=torch.float32, device=brain.device)
-                if "capturable" in g:
-                    g["capturable"] = True
             else:
                 g["lr"] = lr
-                if "capturable" in g:
-                    g["capturable"] = False
-        for p_, st in opt.state.items():                   # Adam's step counters follow the mode too
-            if "step" in st and torch.is_tensor(st["step"]):
-                want = brain.device if getattr(brain, "hip_graph", False) else torch.device("cpu")
-                if st["step"].device != want:
-                    st["step"] = st["step"].to(want)
+            on_device = bool(g.get("fused")) or bool(g.get("capturable"))
+            for p_ in g["params"]:
+                st = opt.state.get(p_)
+                if st and torch.is_tensor(st.get("step")):
+                    want = p_.device if on_device else torch.device("cpu")
+                    if st["step"].device != want:
+                        st["step"] = st["step"].to(want)

@@ -531,6 +531,9 @@ class _ConvAEFn(torch.autograd.Function):
                       for st in sdist.StageBuckets.STAGES}
         run_encoder = need_stage["encoder"] or ctx.need_input_grad
         run_decoder = need_stage["decoder"] or run_encoder
+        # the buckets of an earlier backward must not outlive it (Brain._grad_flats would match them against this
+        # step's .grad, and they would stay pinned -- in the graph pool under hipGraph): finish() sets the new ones
+        model._last_flats = None
         buckets = sdist.StageBuckets(list(P.items()), dev, model._side_stream(dev))
         newg = buckets.view
 
@@ -726,14 +729,17 @@ class _ConvAEFn(torch.autograd.Function):
         if d_logp is None:
             d_logp = torch.zeros(B, 2, device=dev)
 
-        def finish():
+        def finish(d_feats=None):
             flush_bias()
             buckets.join()
             ctx.S = None
+            # (Brain.check_gradients clips the buckets directly when every .grad is still a view of one of them):
+            # the stages with anything to produce are the ones reduced on every return path
+            model._last_flats = [buckets.flat[st] for st in sdist.StageBuckets.STAGES if need_stage[st]]
             grads = tuple(G[k] if need[k] else None for k in names)
             G.clear()
             buckets.views.clear()
-            return (None, None, None) + grads
+            return (None, None, d_feats) + grads
 
         # ======================= sex classifier: FC head =======================
         def head_bwd():
@@ -895,14 +901,7 @@ class _ConvAEFn(torch.autograd.Function):
         flush_bias()
         if need_stage["encoder"]:
             buckets.reduce_stage("encoder")
-        buckets.join()
-        ctx.S = None
-        # (Brain.check_gradients clips the buckets directly when every .grad is still a view of one of them)
-        model._last_flats = [buckets.flat[st] for st in sdist.StageBuckets.STAGES if need_stage[st]]
-        grads = tuple(G[k] if need[k] else None for k in names)
         # autograd's AccumulateGrad adopts a gradient only when nothing else references it (it
-        # clones otherwise: 56 copies per step): drop this frame's references explicitly rather than
-        # rely on the frame being collected before the engine looks
-        G.clear()
-        buckets.views.clear()
-        return (None, None, d_feats) + grads
+        # clones otherwise: 56 copies per step): finish() drops this frame's references explicitly
+        # rather than rely on the frame being collected before the engine looks
+        return finish(d_feats)

@@ -668,6 +668,7 @@ extern "C" int sa_abi_sizeof(int which) {
     case 5: return (int)sizeof(SaFinArgs);
     case 6: return (int)sizeof(SaBiasMulti);
     case 7: return (int)sizeof(SaWredMulti);
+    case 8: return (int)sizeof(SaFlats);
     default: return -22;
   }
 }

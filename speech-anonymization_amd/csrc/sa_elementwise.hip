@@ -618,6 +618,8 @@ extern "C" int sa_reduce_finalize(const SaFinArgs* a, void* stream) {
 // speechbrain_convae_train.py:249) on the flat gradient buckets of a backward: total = sqrt(sum g^2) over
 // all of them, coef = min(1, max_norm / (total + 1e-6)), g *= coef -- two launches instead of the ~8 of the
 // foreach implementation over 56 tensors.  Deterministic: fixed partial layout, fixed summation order.
+// Non-finite norms follow torch: a NaN coef (NaN norm) is applied, so every element becomes NaN; an inf norm
+// gives coef 0 (finite elements -> 0, inf * 0 -> NaN).
 // ---------------------------------------------------------------------------------
 #define SA_CLIP_BLKS 64
 __global__ __launch_bounds__(256) void sa_clip_sumsq_kernel(SaFlats f, double* __restrict__ partials) {
@@ -647,7 +649,7 @@ __global__ __launch_bounds__(256) void sa_clip_scale_kernel(SaFlats f, const dou
   if (threadIdx.x == 0) {
     const float tn = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
     float c = max_norm / (tn + eps);
-    coef_s = c < 1.0f ? c : 1.0f;
+    coef_s = (c < 1.0f || c != c) ? c : 1.0f;               // NaN norm -> NaN coef, like torch's clamp(max=1)
     if (blockIdx.x == 0 && blockIdx.y == 0 && total_norm) *total_norm = tn;
   }
   __syncthreads();

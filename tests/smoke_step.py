@@ -26,7 +26,11 @@ def make_wave(B, N, seed=8886):
     return torch.from_numpy(np.clip(w, -1, 1).astype("float32"))
 
 
-def build(dtype, device, params=None):
+def build(dtype, device, params=None, checkpointer=None, run_opts=None, adam=None):
+    """the smoke Brain on `device`, after on_fit_start.  checkpointer: a Checkpointer that gets the model, the
+    normaliser, the Noam scheduler and the epoch counter as recoverables (so on_fit_start resumes from its newest
+    checkpoint, the optimizer included); run_opts: more of the Brain's run options (hip_graph=True ...); adam:
+    more keywords of torch.optim.Adam (fused=False: the plain optimizer instead of the fused one)."""
     import speech_anonymization_amd as pkg
     from speech_anonymization_amd import brain as B, convae, losses
     kw = dict(precision=dtype) if isinstance(dtype, str) else dict(dtype=dtype)
@@ -42,9 +46,13 @@ def build(dtype, device, params=None):
     hp["epoch_counter"].current = 1
     br = B.SexAnonymizationTraining(
         modules={"normalize": pkg.InputNormalization("global", update_until_epoch=4)},
-        opt_class=functools.partial(torch.optim.Adam, lr=0.001, betas=(0.9, 0.98), eps=1e-9),
-        hparams=hp, run_opts={"device": str(device)})
+        opt_class=functools.partial(torch.optim.Adam, lr=0.001, betas=(0.9, 0.98), eps=1e-9, **(adam or {})),
+        hparams=hp, run_opts=dict(run_opts or {}, device=str(device)), checkpointer=checkpointer)
     br.modules["ConvAE"] = model.to(device)
+    if checkpointer is not None:
+        for name, obj in (("ConvAE", model), ("normalize", br.modules["normalize"]),
+                          ("noam_annealing", hp["noam_annealing"]), ("counter", hp["epoch_counter"])):
+            checkpointer.add_recoverable(name, obj)
     br.on_fit_start()
     br.modules.train()
     return br

@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol():
 def test_ctypes_structs_match_header_field_order():
     from speech_anonymization_amd import _lib
     src = open(os.path.join(ROOT, "include", "sa_hip.h")).read()
-    for st in (_lib.SaConvArgs, _lib.SaWgradArgs, _lib.SaEwArgs, _lib.SaTaps):
+    for st in (_lib.SaConvArgs, _lib.SaWgradArgs, _lib.SaEwArgs, _lib.SaTaps, _lib.SaFlat, _lib.SaFlats):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (st.__name__, st.__name__), src, re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []
@@ -42,6 +42,19 @@ def test_ctypes_structs_match_header_field_order():
                 m = re.search(r"(\w+)\s*(\[[^\]]*\])*\s*$", part.strip())
                 names.append(m.group(1))
         assert names == [f[0] for f in st._fields_], st.__name__
+
+
+def test_record_sizes_match_the_library():
+    """sa_abi_sizeof(i) for every argument record the bindings mirror, in the order _lib.load() checks them
+    (SaFlats: sa_clip_grads); an unknown record is -EINVAL"""
+    from speech_anonymization_amd import _lib
+    lib = _lib.load()
+    recs = (_lib.SaConvArgs, _lib.SaWgradArgs, _lib.SaEwArgs, _lib.SaPackDesc, _lib.SaTaps, _lib.SaFinArgs,
+            _lib.SaBiasMulti, _lib.SaWredMulti, _lib.SaFlats)
+    for i, rec in enumerate(recs):
+        assert lib.sa_abi_sizeof(i) == ctypes.sizeof(rec), rec.__name__
+    assert ctypes.sizeof(_lib.SaFlats) == 8 + 16 * _lib.FLATS_MAX
+    assert lib.sa_abi_sizeof(len(recs)) == -22
 
 
 def test_comm_entry_points_before_init():

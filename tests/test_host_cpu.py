@@ -239,6 +239,53 @@ def test_checkpoint_names_are_unique_and_resume_restores_optimizer(tmp_path):
     assert br2.step == 3 and abs(br2.avg_train_loss - 0.25) < 1e-12
 
 
+@pytest.mark.parametrize("writer_capturable,reader_capturable", [(True, False), (False, True)],
+                         ids=["capturable-to-plain", "plain-to-capturable"])
+def test_resume_keeps_the_readers_optimizer_flags(tmp_path, writer_capturable, reader_capturable):
+    """Optimizer.load_state_dict copies the checkpoint's param groups wholesale; the resumed run keeps its OWN
+    fused / foreach / capturable flags and puts every Adam step count where they need it (the parameter's
+    device for capturable or fused, the host for the plain optimizer).  On the CPU this checks the flags and the
+    placement only (tests/test_train_step_gpu.py resumes real fused and capturable runs on the GPU)."""
+    from speech_anonymization_amd.brain import Brain
+    from speech_anonymization_amd.checkpoint import Checkpointer
+    import functools
+
+    def make(capturable):
+        torch.manual_seed(0)
+        lin = torch.nn.Linear(4, 3)
+        ck = Checkpointer(str(tmp_path / "save"), {"model": lin})
+        br = Brain(modules={"lin": lin}, run_opts={"device": "cpu"}, checkpointer=ck,
+                   opt_class=functools.partial(torch.optim.Adam, lr=1e-2, capturable=capturable))
+        return br, lin, ck
+
+    br, lin, ck = make(False)
+    br.on_fit_start()
+    for _ in range(2):
+        lin(torch.ones(2, 4)).sum().backward()
+        br.optimizer.step(); br.optimizer.zero_grad()
+    for g in br.optimizer.param_groups:         # (torch's capturable Adam cannot step on the CPU: the flag only)
+        g["capturable"] = writer_capturable
+    ck.save(br)
+    want = {k: v.clone() for k, v in br.optimizer.state[lin.weight].items()}
+
+    br2, lin2, _ = make(reader_capturable)
+    br2.on_fit_start()
+    opt = br2.optimizer
+    for g in opt.param_groups:
+        assert {k: g[k] for k in ("fused", "foreach", "capturable")} == dict(fused=None, foreach=None,
+                                                                              capturable=reader_capturable)
+        assert isinstance(g["lr"], float) and opt._sa_host_lr == g["lr"]
+        for p in g["params"]:
+            st = opt.state[p]
+            assert st["step"].device == p.device and float(st["step"]) == 2.0
+    st = opt.state[lin2.weight]
+    assert torch.equal(st["exp_avg"], want["exp_avg"]) and torch.equal(st["exp_avg_sq"], want["exp_avg_sq"])
+    if not reader_capturable:
+        lin2(torch.ones(2, 4)).sum().backward()
+        opt.step()                                      # steps in the reader's own form
+        assert float(st["step"]) == 3.0
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` without a torchrun environment starts its two ranks itself (before
     anything touches a GPU), they rendezvous (gloo here), take the MAX over ranks and rank 0's JSON

@@ -1405,3 +1405,117 @@ def test_fused_gradient_clip_equals_torch(scale):
     if float(tn_ref) <= 5.0:
         assert torch.equal(got, torch.cat(before))
     assert float((got - want).abs().max()) <= 3e-7 * float(want.abs().max())
+
+
+_CLIP_SIZES = None
+
+
+def _clip_sizes():
+    """flat sizes of the edge test: around one thread, one wave and one 64-workgroup sweep of the kernels, plus the
+    three stage buckets of the ConvAE's backward (decoder, sex classifier, encoder: StageBuckets of a built model)"""
+    global _CLIP_SIZES
+    if _CLIP_SIZES is None:
+        from speech_anonymization_amd import convae, distributed as sdist
+        model = convae.ConvAutoencoder(pooling_noise=None, precision="bf16x3")
+        b = sdist.StageBuckets(list(model.named_parameters()), torch.device("cpu"))
+        _CLIP_SIZES = [1, 255, 256, 257, 16384, 16385] + [b.flat[st].numel() for st in sdist.StageBuckets.STAGES]
+    return _CLIP_SIZES
+
+
+def _clip_case(case, sizes, max_norm, gen):
+    """fp32 host flats of the value case"""
+    base = [torch.randn(n, generator=gen, dtype=torch.float64) for n in sizes]
+    if case == "zero":
+        return [torch.zeros(n) for n in sizes]
+    if case in ("below", "above", "far_above"):
+        target = max_norm * {"below": 1 - 2.0 ** -20, "above": 1 + 2.0 ** -20, "far_above": 1e4}[case]
+        nrm = float(sum((b * b).sum() for b in base)) ** 0.5
+        return [(b * (target / nrm)).float() for b in base]
+    if case == "wide_range":
+        return [(b * (1e15 if i == 0 else 1e-3)).float() for i, b in enumerate(base)]
+    out = [(b * 1e-2).float() for b in base]
+    if case == "nan":
+        out[-1][sizes[-1] // 2] = float("nan")
+    elif case == "pinf":
+        out[0][-1] = float("inf")
+    elif case == "ninf":
+        out[0][-1] = float("-inf")
+    elif case == "nan_inf":
+        out[0][0] = float("nan")
+        out[-1][-1] = float("inf")
+    return out
+
+
+_CLIP_CASES = [(c, k) for c in ("zero", "below", "above", "far_above", "wide_range", "nan", "pinf", "ninf")
+               for k in (1, 2, 3, 4)] + [("nan_inf", k) for k in (2, 3, 4)]
+
+
+@pytest.mark.parametrize("case,nflats", _CLIP_CASES, ids=[f"{c}-{k}flats" for c, k in _CLIP_CASES])
+def test_fused_gradient_clip_edges(case, nflats):
+    """sa_clip_grads on 1..SA_FLATS_MAX flats at the edges: sizes around one thread, one wave and one sweep of the
+    64 workgroups of a flat, and the real stage buckets (every start of the size list, so each size appears in
+    every flat slot); norm 0, just below / just above max_norm (1 -+ 2^-20 of it), far above, a wide dynamic range
+    (one flat ~1e15, the others ~1e-3), one NaN, one +inf, one -inf, a NaN and an inf in different flats.
+    Finite cases against an fp64 reference g * min(1, max_norm / (|g| + eps)): the norm to 2e-6, every element
+    to 8 fp32 ulp (2^-21 relative), bit-unchanged when the coefficient is 1.  Every case against
+    torch.nn.utils.clip_grad_norm_ on the same values as separate device tensors: finite cases to the fp64
+    tolerance twice over; non-finite ones the same class of norm (NaN / inf), the same NaN mask, every other
+    element equal (a NaN norm makes every gradient NaN, an inf norm makes finite entries 0 and infinite ones NaN).
+    Each case runs twice and must give the same bits (the kernel's summation order is fixed).
+    Boundary, not tested: norms whose fp32 squares overflow (|g| >~ 1e19).  The kernel sums squares in fp32 per
+    thread and in fp64 across threads, torch in fp32 throughout, so which of them overflows to inf there depends
+    on how the values are laid out."""
+    from speech_anonymization_amd import ops
+    d = dev()
+    max_norm, eps = 5.0, 1e-6
+    sizes_all = _clip_sizes()
+    gen = torch.Generator().manual_seed(17 + 31 * nflats + len(case))
+    finite = case in ("zero", "below", "above", "far_above", "wide_range")
+    for start in range(len(sizes_all)):
+        sizes = [sizes_all[(start + j) % len(sizes_all)] for j in range(nflats)]
+        tag = (case, sizes)
+        host = _clip_case(case, sizes, max_norm, gen)
+        runs = []
+        for _ in range(2):
+            flats = [h.to(d) for h in host]
+            tn = ops.clip_flats(flats, max_norm, eps)
+            torch.cuda.synchronize()
+            runs.append((float(tn), torch.cat(flats).cpu()))
+        (tn, got), (tn2, got2) = runs
+        assert np.float32(tn).tobytes() == np.float32(tn2).tobytes(), tag
+        assert torch.equal(got.view(torch.int32), got2.view(torch.int32)), tag
+        # torch's clip on the same values held as separate parameters (pieces of every flat)
+        ref_params = []
+        for h in host:
+            for lo, hi in ((0, 7), (7, 300), (300, h.numel())):
+                if hi > lo and lo < h.numel():
+                    p = torch.nn.Parameter(torch.zeros(min(hi, h.numel()) - lo, device=d))
+                    p.grad = h[lo:min(hi, h.numel())].to(d)
+                    ref_params.append(p)
+        tn_t = float(torch.nn.utils.clip_grad_norm_(ref_params, max_norm))
+        want_t = torch.cat([p.grad for p in ref_params]).cpu()
+        src = torch.cat(host)
+        if finite:
+            g64 = src.double()
+            n64 = float((g64 * g64).sum()) ** 0.5
+            coef = min(1.0, max_norm / (n64 + eps))
+            if case == "below":
+                assert coef == 1.0 and n64 > max_norm * (1 - 2.0 ** -19), tag
+            if case == "above":
+                assert coef < 1.0 and n64 < max_norm * (1 + 2.0 ** -19), tag
+            if case == "zero":
+                assert tn == 0.0, tag
+            assert abs(tn - n64) <= 2e-6 * n64, (tag, tn, n64)
+            assert abs(tn_t - n64) <= 2e-6 * n64, (tag, tn_t, n64)
+            want = g64 * coef
+            err = (got.double() - want).abs()
+            assert bool((err <= 2.0 ** -21 * want.abs()).all()), (tag, float((err / want.abs()).max()))
+            assert bool(((got.double() - want_t.double()).abs() <= 2.0 ** -20 * want.abs()).all()), tag
+            if coef == 1.0:
+                assert torch.equal(got, src) and torch.equal(want_t, src), tag
+        else:
+            assert (np.isnan(tn), np.isinf(tn)) == (np.isnan(tn_t), np.isinf(tn_t)), (tag, tn, tn_t)
+            assert np.isnan(tn) or np.isinf(tn), (tag, tn)
+            mask = torch.isnan(got)
+            assert torch.equal(mask, torch.isnan(want_t)), (tag, int(mask.sum()), int(torch.isnan(want_t).sum()))
+            assert bool((got[~mask] == want_t[~mask]).all()), tag        # (0.0 == -0.0)
