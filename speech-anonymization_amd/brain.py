@@ -129,10 +129,6 @@ class Brain:
         # buckets when every gradient lives there (check_gradients / _grad_flats); same arithmetic up to the
         # order of the sum of squares
         self.fused_clip = bool(run_opts.get("fused_clip", os.environ.get("SA_FUSED_CLIP", "1") == "1"))
-        # calibrate_xcd (default OFF; SA_CALIBRATE_XCD=1): see on_fit_start.  Measured: the per-XCD medians of one
-        # launch carry 2-3 % of noise, as much as the effect (odd XCDs ~4 % slower than even ones on every chip
-        # seen) -- the calibrated step was 1 % SLOWER (8.85 vs 8.74 ms); the mechanism stays for experiments
-        self.calibrate_xcd = bool(run_opts.get("calibrate_xcd", os.environ.get("SA_CALIBRATE_XCD", "0") == "1"))
         self.distributed_launch = bool(run_opts.get("distributed_launch", sdist.is_distributed()))
         self.modules = torch.nn.ModuleDict(modules or {})
         # dp_batch_sizes (default "equal"): how the data-parallel ranks' batches relate.  The data
@@ -169,12 +165,6 @@ class Brain:
         for m in self.modules.values():
             if hasattr(m, "dp_batch_sizes"):
                 m.dp_batch_sizes = self.dp_batch_sizes
-        if self.calibrate_xcd and self.device.type == "cuda":
-            # once per process: the XCDs of a chip run the persistent convolution kernels at different speeds
-            # (up to 12 %); their workgroups get tile ranges in proportion (ops.calibrate_xcd, ~0.1 s)
-            from . import ops
-            if ops._xcd_weights is None:
-                ops.calibrate_xcd(self.device)
         self.init_optimizers()
         if self.checkpointer is not None:
             if self.optimizer is not None:

@@ -26,12 +26,6 @@
 #include <type_traits>
 #include "sa_common.h"
 
-// -DSA_ABL=<mask>: timing-only ablation builds (tools/conv_ablate.py; WRONG numerics, never shipped):
-//   1 no MFMA   2 weight fragments loaded once   4 no epilogue   8 no prologue transform
-//   16 A fragments loaded once   32 no prologue row loads
-#ifndef SA_ABL
-#define SA_ABL 0
-#endif
 // -DSA_CONV_STAMPS: diagnostic build (tools/conv_stamps.py) that stamps s_memtime at the phase
 // boundaries of a few workgroups; no stamp exists in the normal build.
 #ifdef SA_CONV_STAMPS
@@ -100,7 +94,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
     for (int i = 0; i < NIT; ++i) {
       const int r = r0 + i * C::RPPI, g = gbase + r;
       raw[i] = make_uint4(0, 0, 0, 0);
-      if (!(SA_ABL & 32) || a.B < 0)
       if (r < a.nrows && g >= 0 && g < a.Lin) raw[i] = *reinterpret_cast<const uint4*>(xb + (size_t)g * CIN);
     }
     // PRO2 (normalisation-backward prologue, SaConvArgs.nb_*): the rows are d z of the layer above;
@@ -114,7 +107,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
       for (int i = 0; i < NIT; ++i) {
         const int r = r0 + i * C::RPPI, g = gbase + r;
         raw2[i] = make_uint4(0, 0, 0, 0);
-        if (!(SA_ABL & 32) || a.B < 0)
         if (r < a.nrows && g >= 0 && g < a.Lin) raw2[i] = *reinterpret_cast<const uint4*>(x2 + (size_t)g * CIN);
       }
 #pragma unroll
@@ -158,9 +150,7 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
         }
       }
     };
-    if ((SA_ABL & 8) && a.B > 0) {
-      stage_rows([](float*, int, int) {});
-    } else if constexpr (PRO2) {
+    if constexpr (PRO2) {
       stage_rows([&](float* f, int i, int g) {
         float y[VEC];
         tr::unpack(raw2[i], y);
@@ -316,13 +306,10 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
       load_a(0, 0);
 #pragma unroll
       for (int ku = 0; ku < KU; ++ku) {
-        if (ku + 1 < KU && (!(SA_ABL & 16) || a.B < 0)) load_a((ku + 1) & 1, ku + 1);
+        if (ku + 1 < KU) load_a((ku + 1) & 1, ku + 1);
 #pragma unroll
         for (int mt = 0; mt < C::MT; ++mt) {
-          if constexpr ((SA_ABL & 1) != 0) {
-            asm volatile("" :: "v"(ah[ku & 1][mt]), "v"(bq[0][ku]));
-            if constexpr (P::NPL == 2) asm volatile("" :: "v"(al[ku & 1][mt]), "v"(bq[1][ku]));
-          } else if constexpr (P::NPL == 2) {
+          if constexpr (P::NPL == 2) {
             acc[v][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ku & 1][mt], bq[0][ku], acc[v][mt], 0, 0, 0);
             acc[v][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ku & 1][mt], bq[1][ku], acc[v][mt], 0, 0, 0);
             acc[v][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ku & 1][mt], bq[0][ku], acc[v][mt], 0, 0, 0);
@@ -334,28 +321,16 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
     };
     Frag b0[P::NPL][KU], b1[P::NPL][KU];
     load_group(b0, 0);
-    if ((SA_ABL & 2) && a.B > 0) load_group(b1, 1);
     for (int g = 0; g < G; g += 2) {
-      if (g + 1 < G && (!(SA_ABL & 2) || a.B < 0)) load_group(b1, g + 1);
+      if (g + 1 < G) load_group(b1, g + 1);
       compute_group(b0, g);
       if (g + 1 < G) {
-        if (g + 2 < G && (!(SA_ABL & 2) || a.B < 0)) load_group(b0, g + 2);
+        if (g + 2 < G) load_group(b0, g + 2);
         compute_group(b1, g + 1);
       }
     }
   }
   SA_STAMP(3);
-  if ((SA_ABL & 4) && a.B > 0) {
-    float t = 0.0f;
-#pragma unroll
-    for (int v = 0; v < C::VPW; ++v)
-#pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t += acc[v][mt][i];
-    if (t == 1.2345e-33f) reinterpret_cast<float*>(a.y)[tid] = t;       // keeps the accumulators live
-    return;
-  }
   constexpr int NOT = TM / C::RPPO;
   const int ec = tid % C::CHO, er0 = tid / C::CHO;
   __syncthreads();                                   // every wave is done reading As

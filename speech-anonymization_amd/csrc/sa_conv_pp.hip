@@ -4,7 +4,7 @@
 // conv1d / conv_transpose1d forward and data gradients the reference reaches from
 // models/ConvAutoEncoder.py:141-172 and :33-43); different execution structure:
 //
-// Measured on the one-tile-per-workgroup kernel (tools/conv_ablate.py, 128->128, B = 32): removing
+// Measured on the one-tile-per-workgroup kernel (timing-only ablation builds, 128->128, B = 32): removing
 // the MFMAs saves 122 us, the row loads 76 us, the weight-fragment loads 61 us, the epilogue 37 us
 // of 332 us -- the parts add up, i.e. they do not overlap.  The 3-4 workgroups resident on a CU
 // fall into lock-step (they contend for the same unit in every phase, so a lagging one catches up
@@ -30,11 +30,6 @@
 // Policies f32 and bf16x3 (fp32 storage); bf16 storage and bf16x1f stay on sa_conv_gemm.hip.
 #include <type_traits>
 #include "sa_conv_cfg.h"
-// -DSA_ABL=<mask>: timing-only ablation builds (WRONG numerics, never shipped): 1 no MFMA, 2 weight
-// fragments loaded once, 4 no epilogue stores, 16 A fragments loaded once, 32 no row loads, 64 no a_out
-#ifndef SA_ABL
-#define SA_ABL 0
-#endif
 
 // -DSA_PP_STAMPS: diagnostic build (tools/pp_stamps.py): s_memtime at the phase boundaries of one
 // workgroup (wave 0 of each group); no stamp exists in the normal build.
@@ -142,7 +137,6 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
         const int i = pass * NPP + ii;
         const int r = r0 + i * C::RPPI, g = gbase + r;
         raw[ii] = make_uint4(0, 0, 0, 0);
-        if (!(SA_ABL & 32) || a.B < 0)
         if (i < NIT && r < a.nrows && g >= 0 && g < a.Lin) raw[ii] = *reinterpret_cast<const uint4*>(xb + (size_t)g * CIN);
       }
       if constexpr (PRO2) {
@@ -151,7 +145,6 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
           const int i = pass * NPP + ii;
           const int r = r0 + i * C::RPPI, g = gbase + r;
           raw2[ii] = make_uint4(0, 0, 0, 0);
-          if (!(SA_ABL & 32) || a.B < 0)
           if (i < NIT && r < a.nrows && g >= 0 && g < a.Lin) raw2[ii] = *reinterpret_cast<const uint4*>(x2 + (size_t)g * CIN);
         }
       }
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
   auto mfma_tile = [&](int t) {
     const int b = t / a.ntiles, tile = t % a.ntiles, m0 = tile * C::BMB;
     if constexpr (sizeof(LT) == 2) {
-      if (a.a_out && (!(SA_ABL & 64) || a.B < 0)) {               // bf16 operand cache for sa_wgrad: the (hi) plane of the owned rows
+      if (a.a_out) {                                              // bf16 operand cache for sa_wgrad: the (hi) plane of the owned rows
         constexpr int CH16 = CIN / 8;
         const int own_lo = m0 * SA;
         int own_hi = tile == a.ntiles - 1 ? a.Lin : (m0 + C::BMB) * SA;
@@ -308,12 +301,9 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        if (s + 2 < NS && (!(SA_ABL & 16) || a.B < 0)) load_a((s + 2) % 3, s + 2);
+        if (s + 2 < NS) load_a((s + 2) % 3, s + 2);
         const int ku = s / C::MT, mt = s % C::MT;
-        if constexpr ((SA_ABL & 1) != 0) {
-          asm volatile("" :: "v"(ah[s % 3]), "v"(bq[0][ku]));
-          if constexpr (P::NPL == 2) asm volatile("" :: "v"(al[s % 3]), "v"(bq[1][ku]));
-        } else if constexpr (P::NPL == 2) {
+        if constexpr (P::NPL == 2) {
           acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s % 3], bq[0][ku], acc[mt], 0, 0, 0);
           acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s % 3], bq[1][ku], acc[mt], 0, 0, 0);
           acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s % 3], bq[0][ku], acc[mt], 0, 0, 0);
@@ -335,11 +325,11 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
     for (; g + 1 < G; g += 2) {
       // the scheduling barriers keep each refill AHEAD of the group it overlaps (hipcc otherwise
       // sinks the loads to just before their use, i.e. no prefetch at all)
-      if (!(SA_ABL & 2) || a.B < 0 || g == 0) load_group(b1, g + 1);
+      load_group(b1, g + 1);
       __builtin_amdgcn_sched_barrier(0);
       compute_group(b0, g);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SA_ABL & 2) || a.B < 0) load_group(b0, g + 2 < G ? g + 2 : G - 1);
+      load_group(b0, g + 2 < G ? g + 2 : G - 1);
       __builtin_amdgcn_sched_barrier(0);
       compute_group(b1, g + 1);
       __builtin_amdgcn_sched_barrier(0);
@@ -349,15 +339,6 @@ __global__ __launch_bounds__(512 * NG, TM == 64 ? 4 : 2 * NG) void sa_conv_pp_ke
 
   // ================= epilogue of tile t, straight from the accumulator registers =================
   auto epilogue = [&](int t) {
-    if ((SA_ABL & 4) && a.B > 0) {
-      float tt = 0.0f;
-#pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tt += acc[mt][i];
-      if (tt == 1.2345e-33f) reinterpret_cast<float*>(a.y)[tid] = tt;     // keeps the accumulators live
-      return;
-    }
     const int b = t / a.ntiles, tile = t % a.ntiles, m0 = tile * C::BMB;
     int lanev = lane;
     asm volatile("" : "+v"(lanev));                    // (see stage_tile)

@@ -34,19 +34,14 @@
 // tools/ws_stamps.py (-DSA_WS_STAMPS: cycles per phase), tools/ws_check.py (bits against the
 // one-tile kernel).
 //
-// Launches it does not cover stay on sa_conv_gemm.hip: the data gradients.  A fused data gradient
-// reads two more fp32 tiles per output tile (the stored forward tensor for the normalisation-backward
-// prologue, and it again + a second gradient in the backward epilogue): 70 KB more LDS or 64 more
-// registers per lane than this structure has left (512 registers: 320 weights, 64 accumulators +
-// their epilogue copy, 24 A fragments, the rest transform state), and with one wave per SIMD its
-// heavier transform and epilogue would be instruction-issue-bound.  The prologue alone (MODE 2) is
-// kept, bit-equal, behind -DSA_WS_PRO2.
+// It does not cover the data gradients (sa_conv_wsd.hip, or the one-tile kernel of sa_conv_gemm.hip).
+// A fused data gradient reads two more fp32 tiles per output tile (the stored forward tensor for the
+// normalisation-backward prologue, and it again + a second gradient in the backward epilogue): 70 KB
+// more LDS or 64 more registers per lane than this structure has left (512 registers: 320 weights, 64
+// accumulators + their epilogue copy, 24 A fragments, the rest transform state), and with one wave per
+// SIMD its heavier transform and epilogue would be instruction-issue-bound.
 #include <type_traits>
 #include "sa_conv_cfg.h"
-
-#ifndef SA_ABL
-#define SA_ABL 0
-#endif
 
 // -DSA_WS_STAMPS: diagnostic build (tools/ws_stamps.py): s_memtime at the phase boundaries of one
 // workgroup's wave 0; no stamp exists in the normal build.
@@ -63,8 +58,6 @@ extern "C" int sa_ws_dbg_read(unsigned long long* out) {
 #endif
 
 #include "sa_conv_ws_common.h"
-
-extern unsigned long long g_ws_xcd_weights;                  // (defined below, next to its setter)
 
 namespace {
 
@@ -85,14 +78,13 @@ namespace {
 //                 every step's first MFMA.
 // Tiles at the ends of an utterance (rows outside it: clamped DMA addresses, zeroed operand rows,
 // ownership checks), partial output tiles and a workgroup's first tile take a plain path.
-// MODE: 0 no transform, 1 affine (per utterance, channel) + x*sigmoid(x), 2 normalisation-backward
-// prologue (nb_*: d y = c1*dz + c2*y + c3 [* (y > 0)] over two input tensors)
+// MODE (2 is not used): 0 no transform, 1 affine (per utterance, channel) + x*sigmoid(x),
 // 3: mode 1 + pro_stats (per-tile sum / sum of squares of the transformed rows the tile owns),
 // 4: mode 1 + a second, per-channel affine (the classifier's input BatchNorm behind the activation)
 // 5: one per-channel affine only (the dilated TDNN layers: BatchNorm of the layer below in front)
 template <int MODE, int NT, int HALO, int CC = 128, int CO = CC, int SA = 1, int UU = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long long xw) {
+void sa_conv_ws_kernel(SaConvArgs a, int total_tiles) {
   typedef WsGeo<CC, NT, HALO, CO, SA, UU> G;
   constexpr int WS_CO = G::CO, WS_SA = G::SA, WS_BM = G::BM;
   static_assert(UU == 1 || MODE == 0, "transposed layers: plain rows");
@@ -104,12 +96,10 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
                 WS_FT = G::FT, WS_SUBS = G::SUBS;
   (void)WS_ROWS; (void)NWM;
   static_assert(MODE == 0 || MODE == 5 || NT == 5, "the staged transforms need the 240-slot tile");
-  constexpr bool PRO2 = MODE == 2;
   constexpr bool SWISH = MODE == 1 || MODE == 3 || MODE == 4;   // affine (per utterance, channel) + x*sigmoid(x)
   constexpr bool PSTAT = MODE == 3, AFF2 = MODE == 4 || MODE == 5;   // (mode 5: the second affine alone)
-  constexpr bool COLRED = PRO2 || PSTAT;                    // per-tile column reductions through the LDS scratch
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // LDS: [operand buffer 0][operand buffer 1][raw tile x][raw tile nb_x (PRO2)][column-reduction scratch (PRO2, pro_stats)]
+  // LDS: [operand buffer 0][operand buffer 1][raw tile x][column-reduction scratch (pro_stats)]
   bf16_t* const planes = reinterpret_cast<bf16_t*>(smem);
   unsigned char* const raw = smem + 2 * WS_BUF_BYTES;
   const unsigned raw_lds = (unsigned)(uintptr_t)(lds_byte*)raw;
@@ -120,24 +110,9 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   const int ntap_ = a.taps.ntaps[ph_];                      // (transposed layers: 3 and 2)
   // This workgroup's contiguous tile range, cut at equal COST in quarter tiles: an iteration whose NEXT or
   // next-but-one tile is an edge tile (the last tiles of an utterance; the wrap into the next one) runs
-  // un-overlapped and costs `pq` (about 2.25 tiles, measured with tools/wsd_stamps.py on the data-gradient
-  // kernel, which shares this structure), an overlapped one 4; every tile carries its own cost, and a launch
-  // ends with its slowest workgroup.
-#ifdef SA_WS_OLD_RANGES
-  int first, last;
-  {                                                         // (A/B build only: round 2's ranges, one surcharge behind each utterance)
-    const unsigned long long U = (unsigned long long)a.ntiles + 4u;
-    const unsigned long long ctot = (unsigned long long)(total_tiles / a.ntiles) * U;
-    auto inv = [&](unsigned long long c) {
-      const unsigned long long k = c / U, r = c - k * U;
-      const unsigned long long t = k * (unsigned)a.ntiles + (r < (unsigned)a.ntiles ? r : (unsigned)a.ntiles);
-      return (int)(t < (unsigned)total_tiles ? t : (unsigned)total_tiles);
-    };
-    first = inv(ctot * blockIdx.x / gridDim.x);
-    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * (blockIdx.x + 1) / gridDim.x);
-    (void)xw;
-  }
-#else
+  // un-overlapped and costs `pq` quarter tiles (WS_PLAIN_QCOST, measured on the data-gradient kernel, which
+  // shares this structure), an overlapped one 4; every tile carries its own cost, and a launch ends with its
+  // slowest workgroup.
   int first, last;
   {
     const int e_num = a.Lin - WS_ROWS - a.rowmin, e_den = WS_BM * WS_SA;
@@ -146,7 +121,8 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
     int nt = a.ntiles + 1 - e_hi;                           // tiles t with t + 2 > e_hi
     if (nt > a.ntiles) nt = a.ntiles;
     if (nt < 0) nt = 0;
-    const unsigned long long pq = (unsigned)(bcost & 0xffff), ni = (unsigned)(a.ntiles - nt);
+    constexpr unsigned long long pq = WS_PLAIN_QCOST;
+    const unsigned long long ni = (unsigned)(a.ntiles - nt);
     const unsigned long long U = pq * (unsigned)nt + 4 * ni;
     const unsigned long long ctot = (unsigned long long)(total_tiles / a.ntiles) * U;
     auto inv = [&](unsigned long long c) {                  // tiles wholly in front of cost position c
@@ -155,21 +131,9 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
       t += k * (unsigned)a.ntiles;
       return (int)(t < (unsigned)total_tiles ? t : (unsigned)total_tiles);
     };
-    // (workgroup i runs on XCD i % 8; its share of the cost follows the weight of its XCD: see sa_conv_wsd.hip)
-    unsigned S8 = 0;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) S8 += (unsigned)(xw >> (8 * x)) & 255u;
-    auto prefix = [&](unsigned i) {
-      unsigned pfx = (i >> 3) * S8;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) pfx += x < (int)(i & 7) ? (unsigned)(xw >> (8 * x)) & 255u : 0u;
-      return (unsigned long long)pfx;
-    };
-    const unsigned long long wtot = prefix(gridDim.x);
-    first = inv(ctot * prefix(blockIdx.x) / wtot);
-    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * prefix(blockIdx.x + 1) / wtot);
+    first = inv(ctot * blockIdx.x / gridDim.x);
+    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * (blockIdx.x + 1) / gridDim.x);
   }
-#endif
   if (first >= last) return;
 
   // ---- the weights: this wave's 32 output columns, all taps / channels, hi and lo images ----
@@ -257,7 +221,7 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   auto is_edge = [&](Tile T) { return T.tile < edge_lo || T.tile > edge_hi; };
 
   // per-utterance transform constants (reloaded when the tile range crosses an utterance)
-  float s1[4], t1[4], k1[4], k2[4], k3[4], s2[4], t2[4];
+  float s1[4], t1[4], s2[4], t2[4];
   int cur_b = -1;
   if constexpr (AFF2) {                                     // per channel: loaded once
 #pragma unroll
@@ -276,15 +240,10 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
         s1[j] = a.s1[(size_t)b * WS_C + ch + j];
         t1[j] = a.t1[(size_t)b * WS_C + ch + j];
       }
-      if constexpr (PRO2) {
-        const size_t q = (size_t)b * a.nb_bstride + ch + j;
-        k1[j] = a.nb_c1[q]; k2[j] = a.nb_c2[q]; k3[j] = a.nb_c3[q];
-      }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                          // waited for here, not in the filler slots
       if constexpr (SWISH) asm volatile("" : "+v"(s1[j]), "+v"(t1[j]));
-      if constexpr (PRO2) asm volatile("" : "+v"(k1[j]), "+v"(k2[j]), "+v"(k3[j]));
     }
     cur_b = b;
   };
@@ -292,7 +251,7 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   // ---- LDS-DMA of piece j of this wave (rows 2i, 2i+1; i = wave + 4j) of tile T ----
   // uniform per-tile bases of the slots (set once per iteration, opaque: hipcc otherwise recomputes
   // them -- two scalar multiplies and a 64-bit add chain -- in every slot)
-  const char* xbase_d = nullptr; const char* x2base_d = nullptr;    // rows of the DMA tile (x, nb_x)
+  const char* xbase_d = nullptr;                                     // rows of the DMA tile
   char* aobase_t = nullptr;                                          // a_out rows of the transform tile
   char* ybase_e = nullptr;                                           // y rows of the epilogue tile
   auto row_ptr = [&](const void* p, int row, int row_bytes) {
@@ -300,36 +259,29 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
     asm volatile("" : "+s"(r));
     return r;
   };
-  auto dma_piece = [&](Tile T, bool edge, int j, int part = 2) {
+  auto dma_piece = [&](Tile T, bool edge, int j) {
     const int i = wave_ + 4 * j;
     if (j == WS_DPW - 1 && i >= WS_NDMA) return;
     const int g0 = T.tile * (WS_BM * WS_SA) + a.rowmin;
     if (!edge) {
-      if (part != 1) ws_dma16s(xbase_d + j * 4096, dma_off, raw_lds + i * 1024);
-      if constexpr (PRO2) {
-        if (part != 0) ws_dma16s(x2base_d + j * 4096, dma_off, raw_lds + WS_RAW_BYTES + i * 1024);
-      }
+      ws_dma16s(xbase_d + j * 4096, dma_off, raw_lds + i * 1024);
     } else {
       WS_IDS;
       int g = g0 + RPP * i + lane / LPR;
       g = g < 0 ? 0 : (g >= a.Lin ? a.Lin - 1 : g);        // rows outside the utterance: any valid address (zeroed in the transform)
       const size_t off = ((size_t)T.b * a.Lin + g) * (WS_C * 4) + (lane % LPR) * 16;
       ws_dma16(reinterpret_cast<const char*>(a.x) + off, raw_lds + i * 1024);
-      if constexpr (PRO2) ws_dma16(reinterpret_cast<const char*>(a.nb_x) + off, raw_lds + WS_RAW_BYTES + i * 1024);
     }
   };
 
   // ---- transform of a piece, in sub-steps (each small enough for one filler slot) ----
-  f32x4 vx[1], vy[1];                                      // the raw piece being transformed (the next one is read as soon as stage 0 has consumed it)
+  f32x4 vx[1];                                             // the raw piece being transformed (the next one is read as soon as stage 0 has consumed it)
   float f[4], csum[4], csq[4];
   uint2 phi, plo;                                          // hi / lo bf16 quadruples of the piece
   unsigned pl_cur = 0;                                     // LDS byte offset of this lane's first row in the transform tile's buffer
-  auto piece_read = [&](int j, int part = 2) {              // 0: x, 1: nb_x (PRO2), 2: both
+  auto piece_read = [&](int j) {
     if (j == WS_DPW - 1 && wave_ + 4 * j >= WS_NDMA) return;
-    if (part != 1) vx[0] = *reinterpret_cast<const f32x4*>(raw + (raw_off + j * 4096));
-    if constexpr (PRO2) {
-      if (part != 0) vy[0] = *reinterpret_cast<const f32x4*>(raw + (raw_off + WS_RAW_BYTES + j * 4096));
-    }
+    vx[0] = *reinterpret_cast<const f32x4*>(raw + (raw_off + j * 4096));
   };
   auto own_range = [&](Tile T, int& lo, int& hi) {
     lo = T.tile * (WS_BM * WS_SA);
@@ -370,12 +322,6 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
       }
     }
     if constexpr (MODE == 5) v = fmaf(v, s2[q], t2[q]);
-    if constexpr (PRO2) {
-      const float y = vy[0][q];
-      v = fmaf(k1[q], v, fmaf(k2[q], y, k3[q]));
-      if (a.nb_relu_mask) v = y > 0.0f ? v : 0.0f;
-      if (a.nb_colsum && owns(T, edge, j)) csum[q] += v;
-    }
     if (edge) {                                            // rows outside the utterance are zero operands
       const int g = T.tile * (WS_BM * WS_SA) + a.rowmin + (int)row0 + 4 * RPP * j;
       if (!(g >= 0 && g < a.Lin)) v = 0.0f;
@@ -393,7 +339,7 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   //   3 w = 1 + w | 4 w = rcp(w) | 5 f = z * w | 6 (second affine) f = f*s2 + t2
   //   split levels: 0 hi = bf16 pairs | 1 hi as floats | 2 f - hi | 3 lo = bf16 pairs
   float z[4], w[4];
-  auto piece_level = [&](Tile T, int j, int lv) {
+  auto piece_level = [&](int j, int lv) {
     if (j == WS_DPW - 1 && wave_ + 4 * j >= WS_NDMA) return;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -404,16 +350,11 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
       } else if constexpr (SWISH) {                        // the operations of sa_swish, in its order
         if (lv == 0) z[q] = fmaf(vx[0][q], s1[q], t1[q]);
         if (lv == 1) w[q] = z[q] * -1.4426950408889634f;
-        if (lv == 2) w[q] = (SA_ABL & 128) ? w[q] * 0.5f : __builtin_amdgcn_exp2f(w[q]);     // (128: timing-only, no transcendentals)
+        if (lv == 2) w[q] = __builtin_amdgcn_exp2f(w[q]);
         if (lv == 3) w[q] = 1.0f + w[q];
-        if (lv == 4) w[q] = (SA_ABL & 128) ? w[q] * 0.25f : __builtin_amdgcn_rcpf(w[q]);
+        if (lv == 4) w[q] = __builtin_amdgcn_rcpf(w[q]);
         if (lv == 5) f[q] = z[q] * w[q];
         if constexpr (AFF2) { if (lv == 6) f[q] = fmaf(f[q], s2[q], t2[q]); }
-      } else {                                             // PRO2 (experiment build)
-        if (lv == 0) z[q] = fmaf(k2[q], vy[0][q], k3[q]);
-        if (lv == 1) f[q] = fmaf(k1[q], vx[0][q], z[q]);
-        if (lv == 2) { if (a.nb_relu_mask) f[q] = vy[0][q] > 0.0f ? f[q] : 0.0f; }
-        if (lv == 3) { if (a.nb_colsum && owns(T, false, j)) csum[q] += f[q]; }
       }
     }
   };
@@ -453,33 +394,29 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
     if (j == WS_DPW - 1 && wave_ + 4 * j >= WS_NDMA) return;
     if (has_ao && owns(T, edge, j)) ws_store_b64(aobase_t + j * (4 * RPP * WS_C * 2), ao_off, phi);
   };
-  // per-tile column reductions of the transform (PRO2: column sums of d y; pro_stats: sum and sum of
-  // squares of the transformed rows): fold the two row halves of the wave, one LDS slot per wave,
-  // summed in wave order by 128 threads after the tile barrier
-  constexpr int NRED = PSTAT ? 2 : 1;
+  // pro_stats, per-tile column reductions of the transform (sum and sum of squares of the transformed
+  // rows): fold the two row halves of the wave, one LDS slot per wave, summed in wave order by 128
+  // threads after the tile barrier
+  constexpr int NRED = 2;
   auto colsum_put = [&](int it) {
-    if constexpr (COLRED) {
-      if (PSTAT || a.nb_colsum) {
-        float* colred = reinterpret_cast<float*>(raw + (PRO2 ? 2 : 1) * WS_RAW_BYTES) + (size_t)(it & 1) * 4 * WS_C * NRED;
+    if constexpr (PSTAT) {
+      float* colred = reinterpret_cast<float*>(raw + WS_RAW_BYTES) + (size_t)(it & 1) * 4 * WS_C * NRED;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float v = csum[q] + __int_as_float(__builtin_amdgcn_ds_bpermute((int)swap_off, __float_as_int(csum[q])));
-          if (lane_ < 32) colred[(wave_ * WS_C + (lane_ & 31) * 4 + q) * NRED] = v;
-          csum[q] = 0.0f;
-          if constexpr (PSTAT) {
-            const float u = csq[q] + __int_as_float(__builtin_amdgcn_ds_bpermute((int)swap_off, __float_as_int(csq[q])));
-            if (lane_ < 32) colred[(wave_ * WS_C + (lane_ & 31) * 4 + q) * NRED + 1] = u;
-            csq[q] = 0.0f;
-          }
-        }
+      for (int q = 0; q < 4; ++q) {
+        const float v = csum[q] + __int_as_float(__builtin_amdgcn_ds_bpermute((int)swap_off, __float_as_int(csum[q])));
+        if (lane_ < 32) colred[(wave_ * WS_C + (lane_ & 31) * 4 + q) * NRED] = v;
+        csum[q] = 0.0f;
+        const float u = csq[q] + __int_as_float(__builtin_amdgcn_ds_bpermute((int)swap_off, __float_as_int(csq[q])));
+        if (lane_ < 32) colred[(wave_ * WS_C + (lane_ & 31) * 4 + q) * NRED + 1] = u;
+        csq[q] = 0.0f;
       }
     }
   };
   auto colsum_out = [&](int t, int it) {                    // after the barrier that follows colsum_put(it)
-    if constexpr (COLRED) {
-      if ((PSTAT || a.nb_colsum) && tid < WS_C) {
-        const float* colred = reinterpret_cast<const float*>(raw + (PRO2 ? 2 : 1) * WS_RAW_BYTES) + (size_t)(it & 1) * 4 * WS_C * NRED;
-        float* dst = PSTAT ? a.pro_stats : a.nb_colsum;
+    if constexpr (PSTAT) {
+      if (tid < WS_C) {
+        const float* colred = reinterpret_cast<const float*>(raw + WS_RAW_BYTES) + (size_t)(it & 1) * 4 * WS_C * NRED;
+        float* dst = a.pro_stats;
 #pragma unroll
         for (int r = 0; r < NRED; ++r)
           dst[((size_t)t * WS_C + tid) * NRED + r] =
@@ -501,7 +438,7 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   auto epi_store = [&](int n) {                             // slot form, full tiles: the store of value n
     const int m = n >> 4, i = n & 15;
     const int ro = m * 32 + (i & 3) + 8 * (i >> 2);         // row in the tile, before the lane half's +4
-    if constexpr ((SA_ABL & 64) == 0) ws_store_b32(ybase_e + ro * (UU * WS_CO * 4), y_off, eval);   // (64: timing-only build without the stores)
+    ws_store_b32(ybase_e + ro * (UU * WS_CO * 4), y_off, eval);
   };
   auto epi_accum = [&](int n) {                             // ... its statistics, and value n+1 formed
     // (asm: hipcc otherwise sinks all 32 accumulations into the statistics slot, behind its branch)
@@ -578,14 +515,12 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
   {
     const bool ec = is_edge(Tc), en = is_edge(Tn);
     xbase_d = row_ptr(a.x, Tc.irow, WS_C * 4);
-    if constexpr (PRO2) x2base_d = row_ptr(a.nb_x, Tc.irow, WS_C * 4);
     aobase_t = const_cast<char*>(row_ptr(a.a_out, Tc.irow, WS_C * 2));
     pl_cur = pl_off;
 #pragma unroll
     for (int j = 0; j < WS_DPW; ++j) dma_piece(Tc, ec, j);
     xbase_d = row_ptr(a.x, Tn.irow, WS_C * 4);
-    if constexpr (PRO2) x2base_d = row_ptr(a.nb_x, Tn.irow, WS_C * 4);
-    if (SWISH || PRO2) load_consts(Tc.b);
+    if (SWISH) load_consts(Tc.b);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int j = 0; j < WS_DPW; ++j) {
@@ -639,10 +574,9 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
     // tile is overlapped like the others)
     // (not with pro_stats: that instance's register allocation tips into scratch with the first iteration in
     // the overlapped body -- tools/ws_audit.py --, so its first tile stays plain)
-    const bool slotE = (PSTAT || (bcost & 0x10000) ? doE : true) && !partialE, slotT = !edgeT, slotD = !edgeT && !edgeD;
-    if ((SWISH || PRO2) && Tn.b != cur_b) load_consts(Tn.b);
+    const bool slotE = (PSTAT ? doE : true) && !partialE, slotT = !edgeT, slotD = !edgeT && !edgeD;
+    if (SWISH && Tn.b != cur_b) load_consts(Tn.b);
     xbase_d = row_ptr(a.x, Tnn.irow, WS_C * 4);
-    if constexpr (PRO2) x2base_d = row_ptr(a.nb_x, Tnn.irow, WS_C * 4);
     aobase_t = const_cast<char*>(row_ptr(a.a_out, Tn.irow, WS_C * 2));
     ybase_e = const_cast<char*>(row_ptr(a.y, Tp.orow, WS_CO * 4));
     stbase_e = const_cast<char*>(row_ptr(a.stats, Tp.srow, WS_CO * 8));
@@ -662,7 +596,7 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
       constexpr bool FAST = decltype(fast_c)::value;
       auto filler = [&](auto f_c) {
         constexpr int fs = decltype(f_c)::value;
-        if constexpr ((SA_ABL & 8) != 0 || !FAST) return;
+        if constexpr (!FAST) return;
         if constexpr (fs < 32) {
           epi_store(fs); epi_accum(fs);
         } else if constexpr (fs == 32 || fs == 33) {
@@ -684,22 +618,20 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
           // next one is read in slot 1) and the operand planes of piece j are written in slots 6 / 7
           // of piece j+1, i.e. slots 0 / 1 of a step (the last piece's after the loop)
           constexpr int j = (fs - WS_FT) / 18, k = (fs - WS_FT) % 18;
-          constexpr int NA = AFF2 ? 7 : 6;                  // arithmetic levels of this mode (PRO2: 4, padded)
+          constexpr int NA = AFF2 ? 7 : 6;                  // arithmetic levels of this mode
           if constexpr (j > 0 && (k == 6 || k == 7)) piece_write(j - 1, k - 6);
-          if constexpr (k < NA) piece_level(Tn, j, k);
-          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1, 0);
-          if constexpr (j + 1 < WS_DPW && k == 13 && PRO2) piece_read(j + 1, 1);
+          if constexpr (k < NA) piece_level(j, k);
+          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1);
           if constexpr (k >= 8 && k < 12) piece_split(j, k - 8);
           if constexpr (k == 14) piece_cache(Tn, false, j);
           if constexpr (k == 15) piece_pstat(Tn, j);
-          if constexpr (k == 16) dma_piece(Tnn, false, j, 0);
-          if constexpr (k == 17 && PRO2) dma_piece(Tnn, false, j, 1);
+          if constexpr (k == 16) dma_piece(Tnn, false, j);
         } else if constexpr (fs >= WS_FT && WS_SUBS == 4) {
           // 72 slots per tile (64 -> 32 transposed): 4 slots per piece, plain rows
           constexpr int j = (fs - WS_FT) / 4, k = (fs - WS_FT) % 4;
           if constexpr (j > 0 && k < 2) piece_write(j - 1, k);
-          if constexpr (k == 0) { piece_level(Tn, j, 0); piece_split(j, 0); }
-          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1, 0);
+          if constexpr (k == 0) { piece_level(j, 0); piece_split(j, 0); }
+          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1);
           if constexpr (k == 1) piece_split(j, 1);
           if constexpr (k == 2) { piece_split(j, 2); piece_split(j, 3); }
           if constexpr (k == 3) { piece_cache(Tn, false, j); dma_piece(Tnn, false, j); }
@@ -708,18 +640,18 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
           // step, two dependence levels per slot (over-full on purpose: these launches are HBM-bound)
           constexpr int j = (fs - WS_FT) / 6, k = (fs - WS_FT) % 6;
           if constexpr (j > 0 && k < 2) piece_write(j - 1, k);
-          if constexpr (k == 0) { piece_level(Tn, j, 0); piece_level(Tn, j, 1); }
-          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1, 0);
-          if constexpr (k == 1) { piece_level(Tn, j, 2); piece_level(Tn, j, 3); }
-          if constexpr (k == 2) { piece_level(Tn, j, 4); piece_level(Tn, j, 5); }
+          if constexpr (k == 0) { piece_level(j, 0); piece_level(j, 1); }
+          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1);
+          if constexpr (k == 1) { piece_level(j, 2); piece_level(j, 3); }
+          if constexpr (k == 2) { piece_level(j, 4); piece_level(j, 5); }
           if constexpr (k == 3) { piece_split(j, 0); piece_split(j, 1); }
           if constexpr (k == 4) { piece_split(j, 2); piece_split(j, 3); }
           if constexpr (k == 5) { piece_cache(Tn, false, j); dma_piece(Tnn, false, j); }
         } else if constexpr (fs >= WS_FT) {                 // 12 slots per piece = two steps: one arithmetic level
           constexpr int j = (fs - WS_FT) / 12, k = (fs - WS_FT) % 12;
           if constexpr (j > 0 && k < 2) piece_write(j - 1, k);                  // (before this piece's split overwrites hi / lo)
-          if constexpr (k == 0) piece_level(Tn, j, 0);
-          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1, 0);
+          if constexpr (k == 0) piece_level(j, 0);
+          if constexpr (j + 1 < WS_DPW && k == 1) piece_read(j + 1);
           if constexpr (k >= 2 && k < 6) piece_split(j, k - 2);
           if constexpr (k == 9) piece_cache(Tn, false, j);
           if constexpr (k == 10) dma_piece(Tnn, false, j);
@@ -742,34 +674,28 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
 #define WS_AL(M) if constexpr (more) { __builtin_amdgcn_sched_barrier(0); load_al(s + 1, M); load_ah(s + 1, M); }
 #define WS_AH(M)
 #define WS_SLOT(I) __builtin_amdgcn_sched_barrier(0); filler(std::integral_constant<int, 6 * s + (I)>{}); __builtin_amdgcn_sched_barrier(0)
-        if constexpr ((SA_ABL & 1) != 0) {
-          asm volatile("" :: "v"(ah[sl][0]), "v"(al[0]), "v"(ah[sl][1]), "v"(al[1]));
-          WS_AL(0); WS_AL(1); WS_AH(0); WS_AH(1);
-          WS_SLOT(0); WS_SLOT(1); WS_SLOT(2); WS_SLOT(3); WS_SLOT(4); WS_SLOT(5);
+        if constexpr (s == 0) {
+          asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc[0]) : "v"(al[0]), "a"(Bh[0][0]));
+          WS_AL(0); WS_SLOT(0);
+          asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc[1]) : "v"(al[1]), "a"(Bh[0][0]));
+          WS_AL(1); WS_SLOT(1);
+        } else if constexpr (s < WS_NAGPR_FRAGS) {
+          WS_MFMA1(0, al[0], "a", Bh[tp][k]); WS_AL(0); WS_SLOT(0);
+          WS_MFMA1(1, al[1], "a", Bh[tp][k]); WS_AL(1); WS_SLOT(1);
         } else {
-          if constexpr (s == 0) {
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc[0]) : "v"(al[0]), "a"(Bh[0][0]));
-            WS_AL(0); WS_SLOT(0);
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc[1]) : "v"(al[1]), "a"(Bh[0][0]));
-            WS_AL(1); WS_SLOT(1);
-          } else if constexpr (s < WS_NAGPR_FRAGS) {
-            WS_MFMA1(0, al[0], "a", Bh[tp][k]); WS_AL(0); WS_SLOT(0);
-            WS_MFMA1(1, al[1], "a", Bh[tp][k]); WS_AL(1); WS_SLOT(1);
-          } else {
-            WS_MFMA1(0, al[0], "v", Bh[tp][k]); WS_AL(0); WS_SLOT(0);
-            WS_MFMA1(1, al[1], "v", Bh[tp][k]); WS_AL(1); WS_SLOT(1);
-          }
-          if constexpr (s < WS_NAGPR_FRAGS) {
-            WS_MFMA1(0, ah[sl][0], "a", Bl[tp][k]); WS_AH(0); WS_SLOT(2);
-            WS_MFMA1(1, ah[sl][1], "a", Bl[tp][k]); WS_AH(1); WS_SLOT(3);
-            WS_MFMA1(0, ah[sl][0], "a", Bh[tp][k]); WS_SLOT(4);
-            WS_MFMA1(1, ah[sl][1], "a", Bh[tp][k]); WS_SLOT(5);
-          } else {
-            WS_MFMA1(0, ah[sl][0], "v", Bl[tp][k]); WS_AH(0); WS_SLOT(2);
-            WS_MFMA1(1, ah[sl][1], "v", Bl[tp][k]); WS_AH(1); WS_SLOT(3);
-            WS_MFMA1(0, ah[sl][0], "v", Bh[tp][k]); WS_SLOT(4);
-            WS_MFMA1(1, ah[sl][1], "v", Bh[tp][k]); WS_SLOT(5);
-          }
+          WS_MFMA1(0, al[0], "v", Bh[tp][k]); WS_AL(0); WS_SLOT(0);
+          WS_MFMA1(1, al[1], "v", Bh[tp][k]); WS_AL(1); WS_SLOT(1);
+        }
+        if constexpr (s < WS_NAGPR_FRAGS) {
+          WS_MFMA1(0, ah[sl][0], "a", Bl[tp][k]); WS_AH(0); WS_SLOT(2);
+          WS_MFMA1(1, ah[sl][1], "a", Bl[tp][k]); WS_AH(1); WS_SLOT(3);
+          WS_MFMA1(0, ah[sl][0], "a", Bh[tp][k]); WS_SLOT(4);
+          WS_MFMA1(1, ah[sl][1], "a", Bh[tp][k]); WS_SLOT(5);
+        } else {
+          WS_MFMA1(0, ah[sl][0], "v", Bl[tp][k]); WS_AH(0); WS_SLOT(2);
+          WS_MFMA1(1, ah[sl][1], "v", Bl[tp][k]); WS_AH(1); WS_SLOT(3);
+          WS_MFMA1(0, ah[sl][0], "v", Bh[tp][k]); WS_SLOT(4);
+          WS_MFMA1(1, ah[sl][1], "v", Bh[tp][k]); WS_SLOT(5);
         }
 #undef WS_MFMA1
 #undef WS_SLOT
@@ -846,9 +772,6 @@ void sa_conv_ws_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long l
 #undef WS_IDS
 }
 
-// extra cost of an utterance end, in tiles (see the kernel's range computation)
-int g_ws_bcost = 9;
-
 template <int MODE, int NT = 5, int HALO = 4, int CC = 128, int CO = CC, int SA = 1, int UU = 1>
 int launch_ws(const SaConvArgs& a, hipStream_t st) {
   typedef WsGeo<CC, NT, HALO, CO, SA, UU> G;
@@ -871,8 +794,7 @@ int launch_ws(const SaConvArgs& a, hipStream_t st) {
       (omin > 0 || omax < 0 || (args.ntiles - 1) * G::BM * SA + omin + WS_ROWS < a.Lin))
     return -22;                                           // every input row must be staged by the tile that owns it
   if ((long)a.B * a.Lin >= (1L << 31) - 64 || (long)a.B * a.Lout >= (1L << 31) - 64) return -22;   // 32-bit row indices in the kernel
-  const size_t lds = 2 * WS_BUF_BYTES + (MODE == 2 ? 2 : 1) * WS_RAW_BYTES +
-                     (MODE == 2 ? 2 * 4 * WS_C * 4 : MODE == 3 ? 2 * 4 * WS_C * 8 : G::COMBINE == 2 ? 2 * 4 * 32 * 8 : 0);
+  const size_t lds = 2 * WS_BUF_BYTES + WS_RAW_BYTES + (MODE == 3 ? 2 * 4 * WS_C * 8 : G::COMBINE == 2 ? 2 * 4 * 32 * 8 : 0);
   auto kern = sa_conv_ws_kernel<MODE, NT, HALO, CC, CO, SA, UU>;
   static bool attr_set = false;
   static int n_cu = 0;
@@ -888,33 +810,12 @@ int launch_ws(const SaConvArgs& a, hipStream_t st) {
   }
   const int total = args.ntiles * a.B;
   const int nwg = total < n_cu ? total : n_cu;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, args, g_ws_bcost, total, g_ws_xcd_weights);
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, args, total);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
 
 }  // namespace
-
-// relative speed of the eight XCDs under the persistent kernels, one byte each (64 = nominal)
-unsigned long long g_ws_xcd_weights = 0x4040404040404040ull;
-
-extern "C" int sa_conv_ws_set_xcd_weights(const unsigned char* w8) {
-  if (!w8) return -22;
-  unsigned long long v = 0;
-  for (int x = 0; x < 8; ++x) {
-    if (w8[x] < 16) return -22;                              // (a zero weight would starve an XCD's workgroups)
-    v |= (unsigned long long)w8[x] << (8 * x);
-  }
-  g_ws_xcd_weights = v;
-  return 0;
-}
-
-extern "C" int sa_conv_ws_set_bcost(int tiles) {
-  // (bit 16, timing A/B only: the first tile of every range takes the plain path, as before round 3's overlap of it)
-  if ((tiles & 0xffff) < 4 || (tiles & 0xffff) > 64 || (tiles & ~0x1ffff)) return -22;
-  g_ws_bcost = tiles;
-  return 0;
-}
 
 // Does the weight-stationary kernel serve this launch?  (sa_conv_gemm.hip asks before routing.)
 bool sa_conv_ws_covers(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a) {
@@ -947,11 +848,7 @@ bool sa_conv_ws_covers(int dtype, int cin, int cout, int sa, int u, const SaConv
   // pairs): the tile's own rows must start at an even staged row
   if ((a->a_out || a->nb_colsum || a->pro_stats) && (omin > 0 || (omin & 1))) return false;
   if (a->tile_rows && a->tile_rows != (cout == 64 ? 128 : 64)) return false;
-#ifndef SA_WS_PRO2
-  if (a->nb_x) return false;                              // data gradients stay on the one-tile kernel (header)
-#else
-  if (a->nb_x) return nt == 5 && !a->s1 && !a->swish && a->nb_c1 && a->nb_c2 && a->nb_c3;
-#endif
+  if (a->nb_x) return false;                              // data gradients: sa_conv_wsd.hip or the one-tile kernel (header)
   if (nt == 3)                                            // the dilated TDNN layers: per-channel affine in front, or nothing
     return !a->s1 && !a->swish && !a->pro_stats && (a->s2 || !a->t2);
   if ((a->s2 || a->t2) && (!a->s2 || !a->s1 || a->pro_stats)) return false;    // second affine: behind affine + activation only
@@ -979,9 +876,6 @@ int sa_conv_ws_dispatch(int cin, int cout, const SaConvArgs* a, hipStream_t st) 
     if (omax - omin == 4) return a->s2 ? launch_ws<5, 3, 4>(*a, st) : launch_ws<0, 3, 4>(*a, st);
     return a->s2 ? launch_ws<5, 3, 6>(*a, st) : launch_ws<0, 3, 6>(*a, st);
   }
-#ifdef SA_WS_PRO2                                         // experiment build: MODE 2 without a fused epilogue
-  if (a->nb_x) return launch_ws<2>(*a, st);
-#endif
   if (a->s1 && a->pro_stats) return launch_ws<3>(*a, st);
   if (a->s1 && a->s2) return launch_ws<4>(*a, st);
   if (a->s1) return launch_ws<1>(*a, st);

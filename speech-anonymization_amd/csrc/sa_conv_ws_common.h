@@ -49,6 +49,11 @@ struct WsGeo {
   static_assert(FT > 34 && FT % 6 == 0, "epilogue slots / step alignment");
 };
 
+// cost of a plain (un-overlapped) iteration in quarter tiles, an overlapped one costing 4: the weight of
+// the tiles at the ends of an utterance when a launch's tile ranges are cut (about 2.25 tiles, measured
+// with tools/wsd_stamps.py; 9..16 time the same)
+constexpr unsigned WS_PLAIN_QCOST = 9;
+
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 
 // one 1-KiB piece: lane l's 16 bytes land at lds_dst + 16*l (cdna_hip_programming.md 5.7: M0 is

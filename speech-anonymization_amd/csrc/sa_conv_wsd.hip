@@ -40,13 +40,6 @@
 // a tile body, loaded registers untouched between load and wait).
 #include "sa_conv_ws_common.h"
 
-// -DSA_WSD_ABL=<mask>: timing-only ablation builds (tools/wsd_ablate.py; WRONG results, never shipped):
-//   1 no epilogue stream (waits, levels, stores, loads, statistics)   2 no transform stream (incl. refill DMA)
-//   4 no MFMA   8 no counted waits   16 no epilogue loads and waits   32 no epilogue stores
-#ifndef SA_WSD_ABL
-#define SA_WSD_ABL 0
-#endif
-
 // -DSA_WSD_STAMPS: diagnostic build (tools/wsd_stamps.py): s_memtime at the section boundaries of one
 // workgroup's wave 0; no stamp exists in the normal build.
 #ifdef SA_WSD_STAMPS
@@ -72,14 +65,6 @@ extern "C" int sa_wsd_wg_read(unsigned long long* out) {
 #define WSD_STAMP_RT(it, i)
 #define WSD_WG_STAMP(i)
 #endif
-
-extern unsigned long long g_ws_xcd_weights;                  // (sa_conv_ws.hip)
-// entry / exit time (s_memrealtime, 100 MHz) of every workgroup of the LAST launch: what
-// sa_conv_ws_calibrate_read hands to the host for the per-XCD weights of the tile ranges
-__device__ unsigned long long sa_wsd_life[512 * 2];
-#define WSD_LIFE(i) do { if (threadIdx.x == 0 && blockIdx.x < 512) { \
-  unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-  sa_wsd_life[blockIdx.x * 2 + (i)] = t_; } } while (0)
 
 namespace {
 
@@ -161,7 +146,7 @@ __device__ static inline void wsd_dma16i(const void* gbase, unsigned voff, unsig
 // the reserved registers.
 #define WSD_XR0 240
 template <int NT, int HALO, int PRO, int EP>
-__device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int total_tiles, unsigned long long xw) {
+__device__ __forceinline__ void wsd_body(const SaConvArgs& a, int total_tiles) {
   typedef WsGeo<128, NT, HALO> G;
   typedef WsdSched<NT, HALO, PRO, EP> Sch;
   constexpr int WS_C = 128, WS_TM = 64, WS_KSTEPS = G::KSTEPS, WS_PITCH = G::PITCH, RPP = G::RPP, LPR = G::LPR;
@@ -188,23 +173,8 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
   // sits at the start of an utterance or within the last few tiles runs un-overlapped, about 2.25 times
   // as long (tools/wsd_stamps.py), and the launch ends with its slowest workgroup (at B = 10, a dozen
   // tiles per workgroup, a cost of the utterance END alone left lifetimes between 82 and 152 us).  The
-  // ranges are cut at equal COST in quarter tiles: 4 per overlapped tile, `pq` per plain one, each tile
-  // carrying its own cost (plain tiles: [0, nh) and [ntiles - nt, ntiles) of every utterance).
-#ifdef SA_WS_OLD_RANGES
-  int first, last;
-  {                                                         // (A/B build only: round 2's ranges, one surcharge behind each utterance)
-    const unsigned long long U = (unsigned long long)a.ntiles + 5u;
-    const unsigned long long ctot = (unsigned long long)(total_tiles / a.ntiles) * U;
-    auto inv = [&](unsigned long long c) {
-      const unsigned long long k = c / U, r = c - k * U;
-      const unsigned long long t = k * (unsigned)a.ntiles + (r < (unsigned)a.ntiles ? r : (unsigned)a.ntiles);
-      return (int)(t < (unsigned)total_tiles ? t : (unsigned)total_tiles);
-    };
-    first = inv(ctot * blockIdx.x / gridDim.x);
-    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * (blockIdx.x + 1) / gridDim.x);
-    (void)xw;
-  }
-#else
+  // ranges are cut at equal COST in quarter tiles: 4 per overlapped tile, `pq` (WS_PLAIN_QCOST) per plain
+  // one, each tile carrying its own cost (plain tiles: [0, nh) and [ntiles - nt, ntiles) of every utterance).
   int first, last;
   {
     // (the thresholds of `fast` below, from the launch geometry alone)
@@ -218,7 +188,8 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
     const int f_lo = e_lo > 2 ? e_lo - 1 : 1;
     int nh = f_lo, nt = a.ntiles - 1 - f_hi;
     if (f_hi < f_lo) { nh = a.ntiles; nt = 0; }             // (a short utterance: every tile is plain)
-    const unsigned long long pq = (unsigned)(bcost & 0xffff), ni = (unsigned)(a.ntiles - nh - nt);
+    constexpr unsigned long long pq = WS_PLAIN_QCOST;
+    const unsigned long long ni = (unsigned)(a.ntiles - nh - nt);
     const unsigned long long U = pq * (unsigned)(nh + nt) + 4 * ni;
     const unsigned long long ctot = (unsigned long long)(total_tiles / a.ntiles) * U;
     auto inv = [&](unsigned long long c) {                  // tiles wholly in front of cost position c
@@ -230,24 +201,10 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
       t += k * (unsigned)a.ntiles;
       return (int)(t < (unsigned)total_tiles ? t : (unsigned)total_tiles);
     };
-    // (workgroup i runs on XCD i % 8, and the XCDs of one chip do not run this kernel at one speed: its share
-    // of the cost follows the weight of its XCD -- sa_conv_ws_set_xcd_weights, measured per process)
-    unsigned S8 = 0;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) S8 += (unsigned)(xw >> (8 * x)) & 255u;
-    auto prefix = [&](unsigned i) {
-      unsigned pfx = (i >> 3) * S8;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) pfx += x < (int)(i & 7) ? (unsigned)(xw >> (8 * x)) & 255u : 0u;
-      return (unsigned long long)pfx;
-    };
-    const unsigned long long wtot = prefix(gridDim.x);
-    first = inv(ctot * prefix(blockIdx.x) / wtot);
-    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * prefix(blockIdx.x + 1) / wtot);
+    first = inv(ctot * blockIdx.x / gridDim.x);
+    last = blockIdx.x + 1 == gridDim.x ? total_tiles : inv(ctot * (blockIdx.x + 1) / gridDim.x);
   }
-#endif
   if (first >= last) return;
-  WSD_LIFE(0);
   WSD_STAMP(63, 0); WSD_STAMP_RT(63, 8); WSD_WG_STAMP(0);
 
   // ---- the weights: this wave's 32 output columns, all taps / channels, hi and lo images ----
@@ -735,7 +692,7 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
     // pending section (rows 32..63 of tile t-1) run on an undefined accumulator with Tp = Tc -- they store
     // into rows 32..63 and the statistics slab of THIS tile, which the next iteration's real pending
     // section overwrites (same wave, same addresses, stores retire in order); its loads read this tile's rows.
-    const bool fast = (doE || !(bcost & 0x10000)) && Tc.tile >= fast_lo && Tc.tile <= fast_hi;
+    const bool fast = Tc.tile >= fast_lo && Tc.tile <= fast_hi;
     const Tile Tnn = t + 2 < last ? next_tile(Tn) : Tn;       // (clamped: Tn is already the last tile then)
     const bool edgeT = is_edge(Tn), edgeD = is_edge(Tnn);   // (plain iterations only)
     WSD_STAMP(it, 9);
@@ -803,7 +760,7 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
           else { WSD_STEP16(xcur); if constexpr (EP == 4) WSD_STEP16(gcur); }
         }
         // ---- epilogue stream: value v enters at slot E0 + v*EII, one level per slot ----
-        if constexpr (fs >= Sch::E0 && fs < Sch::EEND && !(SA_WSD_ABL & 1)) {
+        if constexpr (fs >= Sch::E0 && fs < Sch::EEND) {
           ws_static_for<0, 16>([&](auto v_c) {
             constexpr int v = decltype(v_c)::value, lv = fs - (Sch::E0 + v * Sch::EII);
             (void)&ssum; (void)&ssq; (void)&y_off;
@@ -812,7 +769,6 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
                 // the previous section issued this value's load(s) in its slot LB + v
                 // (the comment names the registers for tools/wsd_audit.py)
                 constexpr int N = Sch::nwait(sec ^ 1, v);
-                if constexpr (!(SA_WSD_ABL & (8 | 16)))
                 asm volatile("s_waitcnt vmcnt(%0) ; landed v%c1" :: "n"(N), "n"(WSD_XR0 + v) : "memory");
               }
               epi_level(std::integral_constant<int, he>{}, v_c, std::integral_constant<int, lv>{});
@@ -820,19 +776,19 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
           });
         }
         // ---- store burst: values 2k, 2k+1 in slot SB + k ----
-        if constexpr (fs >= Sch::SB && fs < Sch::SB + 8 && !(SA_WSD_ABL & (1 | 32))) {
+        if constexpr (fs >= Sch::SB && fs < Sch::SB + 8) {
           constexpr int k2 = 2 * (fs - Sch::SB);
           epi_store(std::integral_constant<int, k2>{}, ycur);
           epi_store(std::integral_constant<int, k2 + 1>{}, ycur);
           if constexpr (k2 == 6) WSD_STEP16(ycur);
         }
-        if constexpr (sec == 0 && fs == Sch::EEND && !(SA_WSD_ABL & 1)) epi_stats();
+        if constexpr (sec == 0 && fs == Sch::EEND) epi_stats();
         if constexpr (sec == 1 && fs == 0) WSD_STAMP(it, 1);
         if constexpr (fs == Sch::SB) WSD_STAMP(it, 6 + sec);
         // ---- transform stream ----
         constexpr int np = sec == 0 ? Sch::NP0 : Sch::NP1, jb = sec == 0 ? 0 : Sch::NP0;
-        if constexpr (fs == Sch::T0 - 3 && !(SA_WSD_ABL & 2)) piece_read(jb);
-        if constexpr (fs >= Sch::T0 && fs < Sch::T0 + np * Sch::SUBS && !(SA_WSD_ABL & 2)) {
+        if constexpr (fs == Sch::T0 - 3) piece_read(jb);
+        if constexpr (fs >= Sch::T0 && fs < Sch::T0 + np * Sch::SUBS) {
           constexpr int p = (fs - Sch::T0) / Sch::SUBS, k = (fs - Sch::T0) % Sch::SUBS, j = jb + p;
           if constexpr (PRO2) {
             if constexpr (k < 3) piece_level(Tn, j, k);
@@ -855,7 +811,7 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
         // column sums of the transformed tile: behind the last piece's sums, an LDS slot of section 1
         if constexpr (PRO2 && sec == 1 && fs == Sch::T0 + Sch::NP1 * Sch::SUBS) colsum_put(it + 1);
         // ---- loads for the next section's epilogue: rows 32*sec .. of the current tile ----
-        if constexpr (fs >= Sch::LB && fs < Sch::LB + 16 && !(SA_WSD_ABL & (1 | 16))) {
+        if constexpr (fs >= Sch::LB && fs < Sch::LB + 16) {
           epi_load(std::integral_constant<int, fs - Sch::LB>{}, xcur, gcur);
           if constexpr (fs - Sch::LB == 7) { WSD_STEP16(xcur); if constexpr (EP == 4) WSD_STEP16(gcur); }
         }
@@ -869,18 +825,10 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
         constexpr int tp = s / WS_KSTEPS, k = s % WS_KSTEPS, sl = S & 1;
         constexpr bool more = S + 1 < 2 * Sch::NS;
         __builtin_amdgcn_sched_barrier(0);
-#if SA_WSD_ABL & 4
-#define WSD_MFMA(A, BC, B) asm volatile("" : "+v"(acc[sec]) : "v"(A), BC(B))
-#else
 #define WSD_MFMA(A, BC, B) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[sec]) : "v"(A), BC(B))
-#endif
 #define WSD_SLOT(I) __builtin_amdgcn_sched_barrier(0); \
         filler(std::integral_constant<int, sec>{}, std::integral_constant<int, 3 * s + (I)>{}); __builtin_amdgcn_sched_barrier(0)
-#if SA_WSD_ABL & 4
-#define WSD_MFMA_LIT(A, R) asm volatile("" : "+v"(acc[sec]) : "v"(A))
-#else
 #define WSD_MFMA_LIT(A, R) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, a[" R "], %0" : "+v"(acc[sec]) : "v"(A))
-#endif
         constexpr bool hand = s >= WS_NAGPR_FRAGS && s < WS_NAGPR_FRAGS + WS_NHAND;
         if constexpr (s == 0) {
           asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc[sec]) : "v"(al), "a"(Bh[0][0]));
@@ -949,7 +897,6 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
     epi_stats();
   }
   WSD_STAMP(63, 3); WSD_STAMP_RT(63, 9); WSD_WG_STAMP(1);
-  WSD_LIFE(1);
 #undef WS_IDS
 #undef WSD_IMM
 #undef WSD_Q
@@ -959,12 +906,9 @@ __device__ __forceinline__ void wsd_body(const SaConvArgs& a, int bcost, int tot
 
 template <int NT, int HALO, int PRO, int EP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) __attribute__((amdgpu_num_vgpr(240)))
-void sa_conv_wsd_kernel(SaConvArgs a, int bcost, int total_tiles, unsigned long long xw) {
-  wsd_body<NT, HALO, PRO, EP>(a, bcost, total_tiles, xw);
+void sa_conv_wsd_kernel(SaConvArgs a, int total_tiles) {
+  wsd_body<NT, HALO, PRO, EP>(a, total_tiles);
 }
-
-// extra cost of an utterance end, in tiles (see wsd_body; tools/wsd_ablate.py --bcost sweeps it)
-int g_wsd_bcost = 9;
 
 template <int NT, int HALO, int PRO, int EP>
 int launch_wsd(const SaConvArgs& a, hipStream_t st) {
@@ -1001,7 +945,7 @@ int launch_wsd(const SaConvArgs& a, hipStream_t st) {
   }
   const int total = args.ntiles * a.B;
   const int nwg = total < n_cu ? total : n_cu;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, args, g_wsd_bcost, total, g_ws_xcd_weights);
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, st, args, total);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
@@ -1050,18 +994,6 @@ int wsd_variant(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a
 }
 
 }  // namespace
-
-extern "C" int sa_conv_wsd_set_bcost(int tiles) {
-  // (bit 16, timing A/B only: the first tile of every range takes the plain path, as before round 3's overlap of it)
-  if ((tiles & 0xffff) < 4 || (tiles & 0xffff) > 64 || (tiles & ~0x1ffff)) return -22;
-  g_wsd_bcost = tiles;
-  return 0;
-}
-
-extern "C" int sa_conv_ws_calibrate_read(unsigned long long* life512x2) {
-  if (!life512x2) return -22;
-  return -(int)hipMemcpyFromSymbol(life512x2, HIP_SYMBOL(sa_wsd_life), sizeof(sa_wsd_life));
-}
 
 // Does the fused data-gradient kernel serve this launch?  (sa_conv_gemm.hip asks before routing.)
 bool sa_conv_wsd_covers(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a) {

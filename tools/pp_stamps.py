@@ -4,11 +4,10 @@ import sys, os, ctypes as C, subprocess
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 src = os.path.join(R, "speech-anonymization_amd", "csrc")
-abl = int(os.environ.get("PP_ABL", "0"))
-so = os.path.join(R, "build", "abl", f"libsa_pp_stamps_{abl}.so")
+so = os.path.join(R, "build", "abl", "libsa_pp_stamps.so")
 if not os.path.exists(so) or os.environ.get("PP_REBUILD"):
     os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -std=c++17 -DSA_PP_STAMPS -DSA_ABL={abl} -shared -o {so} sa_conv_gemm.hip sa_conv_pp.hip sa_wgrad.hip sa_small.hip sa_elementwise.hip sa_head.hip sa_fbank.hip sa_mi.hip", shell=True)
+    subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -std=c++17 -DSA_PP_STAMPS -shared -o {so} sa_conv_gemm.hip sa_conv_pp.hip sa_wgrad.hip sa_small.hip sa_elementwise.hip sa_head.hip sa_fbank.hip sa_mi.hip", shell=True)
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
 import numpy as np
@@ -59,7 +58,7 @@ torch.cuda.synchronize(); t_0 = time.perf_counter()
 for _ in range(20):
     run()
 torch.cuda.synchronize()
-print(f"ABL={abl} {which}: {(time.perf_counter() - t_0) / 20 * 1e6:.1f} us per launch")
+print(f"{which}: {(time.perf_counter() - t_0) / 20 * 1e6:.1f} us per launch")
 for h in range(int(os.environ.get("PP_ROWS", "8"))):
     for g in range(2):
         r = a[g, h]

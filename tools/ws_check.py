@@ -1,6 +1,6 @@
 """Weight-stationary conv kernel against the one-tile kernel on the same inputs (bit-equal outputs
 expected: same operand split, same accumulation order).  "nb" / "dgrad" run on the one-tile kernel in
-both arms unless the library was built with -DSA_WS_PRO2.  python tools/ws_check.py [B] [L]"""
+both arms (no weight-stationary instantiation serves them).  python tools/ws_check.py [B] [L]"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
