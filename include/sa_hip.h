@@ -368,6 +368,41 @@ int sa_time_pool_bwd(const float* x, const float* lens, const float* g, const fl
 int sa_leaky_affine_bwd(const float* dy, const float* x, const float* s, float slope, int M, int C,
                         float* dx, void* stream);
 
+/* ---- the x-vector classifier in TRAIN mode (sa_xvector_train.hip; gender_classifier_train.py):
+ * TDNN block z = LeakyReLU(conv_same_reflect(x) + bias), y = BatchNorm1d_train(z) = s*z + t with the
+ * statistics over all B*T frames.  No float atomics: every reduction is fixed-order partials.
+ * sa_xv_tdnn_fwd_train: x [B][T][Cin] (s_in / t_in: the previous block's BatchNorm affine applied at
+ *   staging, both null for block 0), wp = the sa_tdnn_fwd image -> z [B][T][Cout] and fp32 partials
+ *   part [B][ntiles][Cout][2] = (sum z, sum z^2) per 128-frame tile (ntiles = sa_xv_tdnn_ntiles(T)).
+ * sa_xv_colsums: fp64 partials part [ceil(M/rows_per)][N][2] = (sum v, sum v*h) over row chunks of
+ *   G [M][N]; v = G, or with c1..c3 v = (c1*G + c2*H + c3) * (H > 0 ? 1 : slope) also stored to out;
+ *   h = H (or v), normalised (h - hmean)*hrstd when hmean != null.  The rows go to sa_fin_bn_fwd,
+ *   sa_fin_norm_bwd or sa_fin_bias as R partial rows.
+ * sa_xv_tdnn_wgrad: part [nsplit][K][Cout][Cin] = per-split sums over rows r = b*T + t of
+ *   dpre[r][co] * x'[b][refl(t + k*dil - pad)][ci] (x' = s_in*x + t_in); rows_per % 32 == 0,
+ *   nsplit*rows_per >= B*T, Cin % 4 == 0, Cout % 4 == 0.  sa_xv_wgrad_reduce adds the splits in
+ *   order (fp64) into dW [Cout][Cin][K] (the torch Conv1d layout).
+ * sa_xv_tdnn_dgrad: dpre [B][T][Cy] -> dxe [B][T + dil*(K-1)][Cin] with the sa_tdnn_bwd_input image;
+ *   then sa_tdnn_fold.
+ * sa_xv_pool_affine: pooled [B][2C] of y = s*z + t from pz = sa_time_pool(z) (no noise): mean
+ *   s*mean_z + t (+ the noise offset), std |s|*std_z + eps.  sa_xv_pool_affine_bwd: g [B][2C] ->
+ *   gz (std half times sign(s)) for sa_time_pool_bwd(z, lens, gz, pz), which then yields d loss / d y. */
+int sa_xv_tdnn_fwd_train(const float* x, const float* s_in, const float* t_in, const void* wp, const float* bias,
+                         float* z, float* part, int B, int T, int Cin, int Cout, int Npad, int K, int dil,
+                         float slope, void* stream);
+int sa_xv_tdnn_ntiles(int T);
+int sa_xv_colsums(const float* G, const float* H, const float* hmean, const float* hrstd, const float* c1,
+                  const float* c2, const float* c3, float slope, float* out, int M, int N, int rows_per,
+                  double* part, void* stream);
+int sa_xv_tdnn_wgrad(const float* dpre, const float* x, const float* s_in, const float* t_in, float* part, int B,
+                     int T, int Cin, int Cout, int K, int dil, int nsplit, int rows_per, void* stream);
+int sa_xv_wgrad_reduce(const float* part, int nsplit, int K, int Cout, int Cin, float* dW, void* stream);
+int sa_xv_tdnn_dgrad(const float* dpre, const void* wp, float* dxe, int B, int T, int Cy, int Cred, int Cin,
+                     int Npad, int K, int dil, void* stream);
+int sa_xv_pool_affine(const float* pz, const float* s, const float* t, const float* noise, int B, int C,
+                      float eps, float* pooled, void* stream);
+int sa_xv_pool_affine_bwd(const float* g, const float* s, int B, int C, float* gz, void* stream);
+
 /* ---- k-NN mutual information (sa_mi.hip): utils/ClusterMI.py:88-121,
  * utils/GroupSamplingMI.py:49-61, utils/mi_loss.py:14-17 ------------------------------ */
 int sa_cluster_mi(const float* X, const long long* y, const long long* idx, int iters, int n, int D,

@@ -123,6 +123,8 @@ SYMBOLS = [
     "sa_comm_unique_id", "sa_comm_init", "sa_comm_world", "sa_comm_allreduce", "sa_comm_allreduce_inline", "sa_comm_join", "sa_comm_ncalls",
     "sa_comm_destroy", "sa_head_fwd", "sa_head_bwd", "sa_head_max_rows",
     "sa_add_layernorm_fwd", "sa_layernorm_bwd", "sa_reflect_pad_fwd", "sa_reflect_pad_bwd", "sa_ln_leaky_fwd", "sa_ln_leaky_bwd", "sa_bias_multi", "sa_asr_block0_fwd", "sa_asr_block0_bwd", "sa_wgrad_reduce_multi", "sa_clip_grads",
+    "sa_xv_tdnn_fwd_train", "sa_xv_tdnn_ntiles", "sa_xv_colsums", "sa_xv_tdnn_wgrad", "sa_xv_wgrad_reduce",
+    "sa_xv_tdnn_dgrad", "sa_xv_pool_affine", "sa_xv_pool_affine_bwd",
 ]
 
 _lib = None

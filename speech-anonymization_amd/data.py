@@ -87,3 +87,29 @@ def synthetic_dataset(n_utts, batch_size, n_samples=161120, seed=8886, rank=0, w
         for f, a in ((220.0, 0.2), (1000.0, 0.1), (3400.0, 0.05)):
             w += a * torch.sin(2 * torch.pi * f * t)[None, :]
         yield Batch(w.clamp(-1, 1).float(), torch.ones(b), torch.arange(b) % 2)
+
+
+def synthetic_gender_dataset(n_utts, batch_size, n_samples=16000, seed=1986):
+    """utterances of two classes separable by pitch, for the gender-classifier recipe without a
+    dataset: a harmonic series (8 partials, random decaying amplitudes and phases) at a
+    fundamental of 100-140 Hz for class M (0) or 190-250 Hz for class F (1), plus white noise;
+    relative lengths in [0.6, 1] (zero-padded tail).  Deterministic in `seed`."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.arange(n_samples, dtype=torch.float64) / 16000.0
+    for i in range(0, n_utts, batch_size):
+        b = min(batch_size, n_utts - i)
+        label = torch.randint(0, 2, (b,), generator=g)
+        lo = torch.where(label == 0, 100.0, 190.0).double()
+        hi = torch.where(label == 0, 140.0, 250.0).double()
+        f0 = lo + (hi - lo) * torch.rand(b, generator=g, dtype=torch.float64)
+        w = 0.02 * torch.randn(b, n_samples, generator=g, dtype=torch.float64)
+        for h in range(1, 9):
+            amp = 0.3 / h * (0.5 + torch.rand(b, 1, generator=g, dtype=torch.float64))
+            ph = 2 * torch.pi * torch.rand(b, 1, generator=g, dtype=torch.float64)
+            w += amp * torch.sin(2 * torch.pi * h * f0[:, None] * t[None, :] + ph)
+        lens = 0.6 + 0.4 * torch.rand(b, generator=g)
+        lens[0] = 1.0                                       # the longest utterance sets the padded length
+        n = (lens * n_samples).round().long()
+        for k in range(b):
+            w[k, n[k]:] = 0.0
+        yield Batch(w.clamp(-1, 1).float(), n.float() / n_samples, label)

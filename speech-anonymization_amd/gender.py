@@ -1,0 +1,181 @@
+"""The external x-vector gender classifier's training recipe (the reference's
+gender_classifier_train.py:58-216 and its config, restated; settings in this repository's
+speechbrain_configs/gender_classifier.yaml, objects made by build()): Fbank ->
+global InputNormalization -> Xvector -> Classifier, mean NLL loss, Adam, speechbrain's
+ReduceLROnPlateau on the validation loss, and the checkpoint with the lowest classification
+``error`` kept.  A checkpoint directory holds embedding_model.ckpt / classifier.ckpt (the key sets
+of xvector.EncoderClassifier, strict), normalizer.ckpt, counter.ckpt, optimizer.ckpt, CKPT.yaml and
+label_encoder.txt, so it is directly usable as ``speechbrain_convae_train.py
+--external_classifier_ckpt DIR`` (the classifier of ACC_external in both model types, and the frozen
+classifier of model_type endtoend).
+
+Labels are data.SEX (M = 0, F = 1), the indices the ConvAE recipe compares ACC_external against.
+The reference's CategoricalEncoder numbers the classes in order of first appearance instead, which
+can swap them; the mapping used is written next to the weights (label_encoder.txt).
+
+Waveform augmentation (EnvCorrupt: an OpenRIR download; TimeDomainSpecAugment) is out of scope:
+the recipe trains without it."""
+import functools
+import os
+
+import torch
+
+from . import features, losses, xvector
+from .brain import Brain, EpochCounter, FileTrainLogger, Stage
+from .checkpoint import Checkpointer
+from .data import SEX
+
+
+class ReduceLROnPlateau:
+    """speechbrain.nnet.schedulers.ReduceLROnPlateau (v0.5.x), restated -- parity unpinned.
+    Until epoch ``dont_halve_until_epoch`` the rate is kept and the anchor follows the loss; after
+    it, a loss at or below the anchor resets the patience counter and becomes the anchor, a worse
+    loss uses up one unit of patience, and once patience is spent the rate is multiplied by
+    ``factor`` and the counter reset.  The result is bounded below by ``lr_min``."""
+
+    def __init__(self, lr_min=1e-8, factor=0.5, patience=2, dont_halve_until_epoch=65):
+        self.lr_min, self.factor, self.patience = lr_min, factor, patience
+        self.dont_halve_until_epoch = dont_halve_until_epoch
+        self.patience_counter, self.losses, self.anchor = 0, [], 99999
+
+    def __call__(self, optim_list, current_epoch, current_loss):
+        for opt in optim_list:
+            current_lr = opt.param_groups[0]["lr"]
+            current_lr = float(current_lr) if torch.is_tensor(current_lr) else current_lr
+            if current_epoch <= self.dont_halve_until_epoch:
+                next_lr = current_lr
+                self.anchor = current_loss
+            elif current_loss <= self.anchor:
+                self.patience_counter = 0
+                next_lr = current_lr
+                self.anchor = current_loss
+            elif self.patience_counter < self.patience:
+                self.patience_counter += 1
+                next_lr = current_lr
+            else:
+                next_lr = current_lr * self.factor
+                self.patience_counter = 0
+            next_lr = max(next_lr, self.lr_min)
+        self.losses.append(current_loss)
+        return current_lr, next_lr
+
+    def state_dict(self):
+        return {"losses": list(self.losses), "anchor": self.anchor, "patience_counter": self.patience_counter}
+
+    def load_state_dict(self, sd):
+        self.losses, self.anchor = list(sd["losses"]), sd["anchor"]
+        self.patience_counter = sd["patience_counter"]
+
+
+def update_learning_rate(optimizer, new_lr):
+    """speechbrain.nnet.schedulers.update_learning_rate"""
+    for g in optimizer.param_groups:
+        if torch.is_tensor(g["lr"]):
+            g["lr"].fill_(new_lr)
+        else:
+            g["lr"] = new_lr
+
+
+def write_label_encoder(path):
+    """the class indices, in the text format of speechbrain's CategoricalEncoder.save"""
+    with open(os.path.join(path, "label_encoder.txt"), "w") as f:
+        for k, v in sorted(SEX.items(), key=lambda kv: kv[1]):
+            f.write(f"'{k}' => {v}\n")
+        f.write("================\n'starting_index' => 0\n")
+
+
+def load_external_classifier(ckpt_dir, device=None):
+    """xvector.EncoderClassifier from a checkpoint directory of this recipe (strict keys), eval mode"""
+    clf = xvector.EncoderClassifier()
+    clf.embedding_model.load_state_dict(torch.load(os.path.join(ckpt_dir, "embedding_model.ckpt"),
+                                                   map_location="cpu", weights_only=True), strict=True)
+    clf.classifier.load_state_dict(torch.load(os.path.join(ckpt_dir, "classifier.ckpt"), map_location="cpu",
+                                              weights_only=True), strict=True)
+    clf.eval()
+    return clf.to(device) if device is not None else clf
+
+
+def build(hp):
+    """the recipe's objects from the plain settings of speechbrain_configs/gender_classifier.yaml
+    (seeded first, so the initial weights follow ``seed``); returned as hparams entries."""
+    torch.manual_seed(int(hp["seed"]))
+    fb, xv, pl = hp["fbank"], hp["xvector"], hp["plateau"]
+    emb = xvector.Xvector(in_channels=fb["n_mels"], lin_neurons=xv["embedding_dim"], tdnn_channels=xv["channels"],
+                          tdnn_kernel_sizes=xv["kernel_sizes"], tdnn_dilations=xv["dilations"])
+    cl = xvector.Classifier(input_shape=[None, None, xv["embedding_dim"]], lin_neurons=xv["embedding_dim"],
+                            out_neurons=hp["classes"])
+    norm = features.InputNormalization(norm_type="global")
+    counter = EpochCounter(hp["number_of_epochs"])
+    out = hp["output_folder"]
+    return {
+        "modules": {"compute_features": features.Fbank(fb["sample_rate"], fb["n_fft"], fb["n_mels"]),
+                    "mean_var_norm": norm, "embedding_model": emb, "classifier": cl},
+        "epoch_counter": counter,
+        "compute_cost": losses.NLLLoss(),
+        "opt_class": functools.partial(torch.optim.Adam, lr=float(hp["adam_lr"])),
+        "lr_annealing": ReduceLROnPlateau(factor=pl["factor"], patience=pl["patience"],
+                                          dont_halve_until_epoch=pl["hold_until_epoch"]),
+        "train_logger": FileTrainLogger(os.path.join(out, "train_log.txt")),
+        "checkpointer": Checkpointer(os.path.join(out, "save"), {"embedding_model": emb, "classifier": cl,
+                                                                 "normalizer": norm, "counter": counter}),
+    }
+
+
+class GenderBrain(Brain):
+    """gender_classifier_train.py:58-216 on the Brain base (fused Adam, clipping at max_grad_norm,
+    the lazy finite check, checkpoint resume)."""
+
+    def prepare_features(self, wavs, lens, stage):
+        feats = self.modules.compute_features(wavs)
+        # no epoch is passed (reference :104): the global statistics follow every training batch
+        return self.modules.mean_var_norm(feats, lens)
+
+    def compute_forward(self, batch, stage):
+        batch = batch.to(self.device)
+        wavs, lens = batch.sig
+        feats = self.prepare_features(wavs, lens, stage)
+        return xvector.train_log_probs(self.modules.embedding_model, self.modules.classifier, feats, lens)
+
+    def compute_objectives(self, predictions, batch, stage):
+        label = batch.gender.to(self.device)
+        logp = predictions.squeeze(1)
+        loss = self.hparams.compute_cost(logp, label)
+        if stage != Stage.TRAIN:
+            self.n_err += int((logp.argmax(dim=-1) != label).sum())
+            self.n_utt += int(label.numel())
+        return loss
+
+    def on_stage_start(self, stage, epoch=None):
+        self.n_err, self.n_utt = 0, 0
+
+    def on_stage_end(self, stage, stage_loss, epoch=None):
+        if stage == Stage.TRAIN:
+            self.train_loss = stage_loss
+            return
+        stats = {"loss": stage_loss, "error": self.n_err / max(1, self.n_utt)}
+        self.last_stats = stats
+        logger = getattr(self.hparams, "train_logger", None)
+        if stage == Stage.VALID:
+            old_lr, new_lr = self.hparams.lr_annealing([self.optimizer], epoch, stage_loss)
+            update_learning_rate(self.optimizer, new_lr)
+            if logger is not None:
+                logger.log_stats({"Epoch": epoch, "lr": old_lr}, train_stats={"loss": self.train_loss},
+                                 valid_stats=stats)
+            if self.checkpointer is not None:
+                path = self.checkpointer.save_and_keep_only(meta=stats, min_keys=["error"])
+                write_label_encoder(path)
+        elif logger is not None:
+            logger.log_stats({"Epoch loaded": self.hparams.epoch_counter.current}, test_stats=stats)
+
+    def on_evaluate_start(self, max_key=None, min_key=None):
+        """speechbrain's evaluate(): the model of the best checkpoint by max_key / min_key"""
+        if self.checkpointer is None:
+            return
+        ckpts = self.checkpointer.find_checkpoints(max_key=max_key, min_key=min_key)
+        if not ckpts:
+            return
+        self.best_checkpoint = ckpts[0]
+        for name in ("embedding_model", "classifier", "mean_var_norm"):
+            fn = os.path.join(ckpts[0], ("normalizer" if name == "mean_var_norm" else name) + ".ckpt")
+            sd = torch.load(fn, map_location="cpu", weights_only=True)
+            self.modules[name].load_state_dict(sd)

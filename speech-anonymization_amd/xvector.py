@@ -265,6 +265,250 @@ class _XvFn(torch.autograd.Function):
         return None, gh, None
 
 
+def _colsums(G, H=None, mean=None, rstd=None, coef=None, out=None, slope=0.01):
+    """fp64 per-channel partial rows [R, N, 2] of sa_xv_colsums over G [M, N] (see include/sa_hip.h)."""
+    M, N = G.shape
+    nchunk = min(64, -(-M // 256))
+    rows_per = -(-M // nchunk)
+    part = torch.empty(-(-M // rows_per), N, 2, dtype=torch.float64, device=G.device)
+    c1, c2, c3 = coef if coef is not None else (None, None, None)
+    L.check(L.load().sa_xv_colsums(L.ptr(G), L.ptr(H), L.ptr(mean), L.ptr(rstd), L.ptr(c1), L.ptr(c2), L.ptr(c3),
+                                   C.c_float(slope), L.ptr(out), M, N, rows_per, L.ptr(part), L.stream()),
+            "sa_xv_colsums")
+    return part
+
+
+def _bn_train_stats(part, norm, count):
+    """fp64 finaliser of the batch statistics: (mean, rstd, scale, shift); updates the running
+    statistics (momentum, unbiased variance) and num_batches_tracked like torch's BatchNorm."""
+    f = ops.fin_bn_fwd(part, norm.num_features, float(count), norm.weight, norm.bias, norm.running_mean,
+                       norm.running_var, norm.eps, norm.momentum)
+    norm.num_batches_tracked.add_(1)
+    return f
+
+
+def _bn_leaky_bwd(dy, z, norm, f, count, dgamma, dbeta, dpre):
+    """BatchNorm(train) then LeakyReLU backward on z = leaky(pre) [M, N]: the BatchNorm sums and the
+    folded coefficients (fp64), then dpre = leak'(z) * (c1*dy + c2*z + c3); returns the fp64
+    partial rows of sum dpre (the bias gradient of the layer before)."""
+    mean, rstd = f[0], f[1]
+    sums = _colsums(dy, z, mean, rstd)
+    coef = ops.fin_norm_bwd(sums, None, norm.num_features, norm.num_features, float(count), norm.weight, mean,
+                            rstd, dgamma=dgamma, dbeta=dbeta)
+    return _colsums(dy, z, coef=coef, out=dpre)
+
+
+def _fin_bias(part, db):
+    return ops.fin_bias(part, part.shape[0], part.shape[1], db)
+
+
+def _tdnn_train(x, s_in, t_in, conv, slope=0.01):
+    """z = leaky(conv(s_in*x + t_in) + bias) and the fp32 (sum z, sum z^2) tile partials."""
+    lib = L.load()
+    B, T, Cin = x.shape
+    Cout = conv.conv.out_channels
+    _stale(conv)
+    img, npad = _packed(conv)
+    z = torch.empty(B, T, Cout, dtype=torch.float32, device=x.device)
+    part = torch.empty(1, B * lib.sa_xv_tdnn_ntiles(T), 2 * Cout, dtype=torch.float32, device=x.device)
+    L.check(lib.sa_xv_tdnn_fwd_train(L.ptr(x), L.ptr(s_in), L.ptr(t_in), L.ptr(img), L.ptr(conv.conv.bias),
+                                     L.ptr(z), L.ptr(part), B, T, Cin, Cout, npad, conv.kernel_size, conv.dilation,
+                                     C.c_float(slope), L.stream()), "sa_xv_tdnn_fwd_train")
+    _stale(conv)
+    return z, ops.sum_partials(part, 1, n=2 * Cout)
+
+
+def _stale(conv):
+    """drop the cached operand images of a trained Conv1d.  torch's fused Adam updates the
+    parameters in place without bumping their version counter, so the (data_ptr, _version) key of
+    _packed / _packed_dgrad cannot see an optimizer step: the train path repacks every step and
+    leaves the cache empty behind it, so that an eval-mode call after the step packs the new
+    weights."""
+    conv._img_key = conv._dimg_key = None
+
+
+def _wgrad_split(M, tiles):
+    """(nsplit, rows_per): ~512 workgroups, rows_per a multiple of 32."""
+    nsplit = max(1, min(512 // max(1, tiles), -(-M // 256)))
+    rows_per = -(-(-(-M // nsplit)) // 32) * 32
+    return -(-M // rows_per), rows_per
+
+
+def _tdnn_wgrad(dpre, x, s_in, t_in, conv, dW):
+    lib = L.load()
+    B, T, Cin = x.shape
+    Cout, K, dil = conv.conv.out_channels, conv.kernel_size, conv.dilation
+    nsplit, rows_per = _wgrad_split(B * T, -(-Cout // 128) * -(-Cin // 128) * K)
+    part = torch.empty(nsplit, K, Cout, Cin, dtype=torch.float32, device=x.device)
+    L.check(lib.sa_xv_tdnn_wgrad(L.ptr(dpre), L.ptr(x), L.ptr(s_in), L.ptr(t_in), L.ptr(part), B, T, Cin, Cout,
+                                 K, dil, nsplit, rows_per, L.stream()), "sa_xv_tdnn_wgrad")
+    L.check(lib.sa_xv_wgrad_reduce(L.ptr(part), nsplit, K, Cout, Cin, L.ptr(dW), L.stream()),
+            "sa_xv_wgrad_reduce")
+    return dW
+
+
+def _tdnn_dgrad(dpre, conv):
+    lib = L.load()
+    B, T, Cy = dpre.shape
+    Cin, K, dil = conv.conv.in_channels, conv.kernel_size, conv.dilation
+    _stale(conv)
+    img, (cred, npad) = _packed_dgrad(conv)
+    pad = dil * (K - 1) // 2
+    dxe = torch.empty(B, T + 2 * pad, Cin, dtype=torch.float32, device=dpre.device)
+    L.check(lib.sa_xv_tdnn_dgrad(L.ptr(dpre), L.ptr(img), L.ptr(dxe), B, T, Cy, cred, Cin, npad, K, dil,
+                                 L.stream()), "sa_xv_tdnn_dgrad")
+    if pad == 0:
+        return dxe
+    dx = torch.empty(B, T, Cin, dtype=torch.float32, device=dpre.device)
+    L.check(lib.sa_tdnn_fold(L.ptr(dxe), L.ptr(dx), B, T, Cin, pad, L.stream()), "sa_tdnn_fold")
+    return dx
+
+
+def _leaky(x, s=None, t=None, slope=0.01):
+    y = torch.empty_like(x)
+    L.check(L.load().sa_leaky_affine(L.ptr(x), L.ptr(s), L.ptr(t), C.c_float(slope), x.shape[0], x.shape[1],
+                                     L.ptr(y), L.stream()), "sa_leaky_affine")
+    return y
+
+
+def train_parameters(xv, cl):
+    """the 30 trainable tensors in the order _XvTrainFn takes them"""
+    out = []
+    nb = (len(xv.blocks) - 2) // 3
+    for i in range(nb):
+        c, n = xv.blocks[3 * i].conv, xv.blocks[3 * i + 2].norm
+        out += [c.weight, c.bias, n.weight, n.bias]
+    lin = xv.blocks[-1].w
+    blk = cl.DNN["block_0"]
+    out += [lin.weight, lin.bias, cl.norm.norm.weight, cl.norm.norm.bias, blk.linear.w.weight,
+            blk.linear.w.bias, blk.norm.norm.weight, blk.norm.norm.bias, cl.out.w.weight, cl.out.w.bias]
+    return out
+
+
+class _XvTrainFn(torch.autograd.Function):
+    """Xvector + Classifier in TRAIN mode: log-probabilities [B, classes] as a function of all 30
+    parameters (BatchNorms on batch statistics, their running statistics updated).  Forward and
+    backward on libsa_hip.so (sa_xvector_train.hip, sa_head.hip); no gradient to the features."""
+
+    @staticmethod
+    def forward(ctx, xv, cl, feats, lens, noise, *params):
+        lib = L.load()
+        x = feats.detach().contiguous().float()
+        B, T, _ = x.shape
+        nb = (len(xv.blocks) - 2) // 3
+        zs, fs, h, s_in, t_in = [], [], x, None, None
+        for i in range(nb):
+            z, sums = _tdnn_train(h, s_in, t_in, xv.blocks[3 * i])
+            f = _bn_train_stats(sums, xv.blocks[3 * i + 2].norm, B * T)
+            zs.append(z)
+            fs.append(f)
+            h, s_in, t_in = z, f[2], f[3]
+        Cc = h.shape[2]
+        lens_d = None if lens is None else lens.to(h.device).float().contiguous()
+        pz = torch.empty(B, 2 * Cc, dtype=torch.float32, device=h.device)
+        L.check(lib.sa_time_pool(L.ptr(h), L.ptr(lens_d), None, B, T, Cc, C.c_float(1e-5), L.ptr(pz), L.stream()),
+                "sa_time_pool")
+        pooled = torch.empty_like(pz)
+        L.check(lib.sa_xv_pool_affine(L.ptr(pz), L.ptr(s_in), L.ptr(t_in), L.ptr(noise), B, Cc, C.c_float(1e-5),
+                                      L.ptr(pooled), L.stream()), "sa_xv_pool_affine")
+        lin = xv.blocks[-1].w
+        emb = ops.dense(pooled, lin.weight, lin.bias, lin.out_features, lin.in_features)
+        blk = cl.DNN["block_0"]
+        u1 = _leaky(emb)
+        f1 = _bn_train_stats(_colsums(u1), cl.norm.norm, B)
+        v1 = _leaky(emb, f1[2], f1[3])
+        h1 = ops.dense(v1, blk.linear.w.weight, blk.linear.w.bias, blk.linear.w.out_features,
+                       blk.linear.w.in_features)
+        u2 = _leaky(h1)
+        f2 = _bn_train_stats(_colsums(u2), blk.norm.norm, B)
+        v2 = _leaky(h1, f2[2], f2[3])
+        logits = ops.dense(v2, cl.out.w.weight, cl.out.w.bias, cl.out.w.out_features, cl.out.w.in_features)
+        logp = ops.log_softmax(logits)
+        ctx.mods = (xv, cl)
+        ctx.saved = (x, zs, fs, lens_d, pz, pooled, u1, f1, v1, u2, f2, v2, logp)
+        return logp
+
+    @staticmethod
+    def backward(ctx, d_logp):
+        lib = L.load()
+        xv, cl = ctx.mods
+        x, zs, fs, lens_d, pz, pooled, u1, f1, v1, u2, f2, v2, logp = ctx.saved
+        ctx.saved = None
+        params = train_parameters(xv, cl)
+        grads = [torch.empty_like(p) for p in params]
+        B, T, _ = x.shape
+        nb = len(zs)
+        (gW, gb, gg1, gb1, gW1, gbl1, gg2, gb2, gWo, gbo) = grads[4 * nb:]
+        blk = cl.DNN["block_0"]
+        lin = xv.blocks[-1].w
+        # ---- head: out Linear <- BatchNorm/LeakyReLU <- Linear <- BatchNorm/LeakyReLU <- embedding Linear
+        g = ops.log_softmax_bwd(d_logp.contiguous().float(), logp)
+        ops.dense_wgrad(g, v2, gWo)
+        _fin_bias(_colsums(g), gbo)
+        g = ops.dense(g, cl.out.w.weight, None, cl.out.w.in_features, cl.out.w.out_features, transpose_w=True)
+        gp = torch.empty_like(g)
+        _fin_bias(_bn_leaky_bwd(g, u2, blk.norm.norm, f2, B, gg2, gb2, gp), gbl1)
+        ops.dense_wgrad(gp, v1, gW1)
+        g = ops.dense(gp, blk.linear.w.weight, None, blk.linear.w.in_features, blk.linear.w.out_features,
+                      transpose_w=True)
+        gp = torch.empty_like(g)
+        _fin_bias(_bn_leaky_bwd(g, u1, cl.norm.norm, f1, B, gg1, gb1, gp), gb)
+        ops.dense_wgrad(gp, pooled, gW)
+        gpool = ops.dense(gp, lin.weight, None, lin.in_features, lin.out_features, transpose_w=True)
+        # ---- statistics pooling of the last block's BatchNorm output
+        Cc = zs[-1].shape[2]
+        f = fs[-1]
+        gz = torch.empty_like(gpool)
+        L.check(lib.sa_xv_pool_affine_bwd(L.ptr(gpool), L.ptr(f[2]), B, Cc, L.ptr(gz), L.stream()),
+                "sa_xv_pool_affine_bwd")
+        dy = torch.empty_like(zs[-1])
+        L.check(lib.sa_time_pool_bwd(L.ptr(zs[-1]), L.ptr(lens_d), L.ptr(gz), L.ptr(pz), B, T, Cc, C.c_float(1e-5),
+                                     L.ptr(dy), L.stream()), "sa_time_pool_bwd")
+        # ---- TDNN blocks, last to first
+        for i in reversed(range(nb)):
+            conv, norm = xv.blocks[3 * i], xv.blocks[3 * i + 2].norm
+            gw, gbias, ggam, gbet = grads[4 * i: 4 * i + 4]
+            z = zs[i]
+            dpre = torch.empty_like(z)
+            bsum = _bn_leaky_bwd(dy.view(B * T, -1), z.view(B * T, -1), norm, fs[i], B * T, ggam, gbet,
+                                 dpre.view(B * T, -1))
+            _fin_bias(bsum, gbias)
+            xin, s_in, t_in = (x, None, None) if i == 0 else (zs[i - 1], fs[i - 1][2], fs[i - 1][3])
+            _tdnn_wgrad(dpre, xin, s_in, t_in, conv, gw)
+            if i > 0:
+                dy = _tdnn_dgrad(dpre, conv)
+            _stale(conv)
+        return (None, None, None, None, None) + tuple(grads)
+
+
+def train_log_probs(embedding_model, classifier, feats, lens=None):
+    """log-probabilities [B, 1, classes] of Xvector -> Classifier.  With both modules in training
+    mode (a mismatch raises), grad enabled and trainable parameters: the train path (_XvTrainFn; batch statistics, running
+    statistics updated, pooling noise drawn per call unless ``pooling_noise`` is a tensor), which
+    fills the gradients of all 30 parameters.  Otherwise the eval-mode forward."""
+    if embedding_model.training != classifier.training:
+        raise ValueError("embedding_model and classifier must both be in training mode or both in eval mode")
+    params = train_parameters(embedding_model, classifier)
+    if not (embedding_model.training and torch.is_grad_enabled() and any(p.requires_grad for p in params)):
+        return classifier(embedding_model(feats, lens))
+    if not feats.is_cuda:
+        raise L.SaHipError("the x-vector classifier runs on the GPU only (no CPU fallback)")
+    B = feats.shape[0]
+    if B < 2:
+        raise ValueError("Expected more than 1 value per channel when training (batch of one utterance)")
+    noise = embedding_model.pooling_noise
+    Cc = embedding_model.blocks[-5].conv.out_channels
+    if torch.is_tensor(noise):
+        noise = noise.to(feats.device).float().contiguous()
+    elif noise:
+        g = torch.randn(B, Cc, device=feats.device)
+        g = g - g.min()
+        noise = (g / g.max()).contiguous()
+    else:
+        noise = None
+    return _XvTrainFn.apply(embedding_model, classifier, feats, lens, noise, *params).unsqueeze(1)
+
+
 class EncoderClassifier(nn.Module):
     """embedding_model + classifier with the fork's classify_batch_feats()."""
 

@@ -21,6 +21,9 @@ CLASS_MAP = {
     "speechbrain.lobes.features.Fbank": "speech_anonymization_amd.features.Fbank",
     "speechbrain.processing.features.InputNormalization": "speech_anonymization_amd.features.InputNormalization",
     "speechbrain.nnet.schedulers.NoamScheduler": "speech_anonymization_amd.brain.NoamScheduler",
+    "speechbrain.nnet.schedulers.ReduceLROnPlateau": "speech_anonymization_amd.gender.ReduceLROnPlateau",
+    "speechbrain.lobes.models.Xvector.Xvector": "speech_anonymization_amd.xvector.Xvector",
+    "speechbrain.lobes.models.Xvector.Classifier": "speech_anonymization_amd.xvector.Classifier",
     "speechbrain.utils.epoch_loop.EpochCounter": "speech_anonymization_amd.brain.EpochCounter",
     "speechbrain.utils.train_logger.FileTrainLogger": "speech_anonymization_amd.brain.FileTrainLogger",
     "speechbrain.utils.checkpoints.Checkpointer": "speech_anonymization_amd.checkpoint.Checkpointer",

@@ -9,8 +9,9 @@
         speechbrain_convae_train.py speechbrain_configs/convae.yaml --distributed_launch
 
 Extra options of this build: ``--synthetic N`` trains on N synthetic utterances per epoch instead
-of CSV manifests (there is no dataset on the GPU box).  The frozen-ASR utility loss, the external
-x-vector evaluation and WER are not part of this path."""
+of CSV manifests (there is no dataset on the GPU box).  ``--external_classifier_ckpt DIR`` (a
+checkpoint of gender_classifier_train.py) adds the ACC_external / ACC_external_orig columns.  The
+frozen-ASR utility loss and WER are not part of this path."""
 import os
 import sys
 
@@ -32,17 +33,18 @@ def main(argv):
     if sdist.if_main_process():
         os.makedirs(hparams["output_folder"], exist_ok=True)
 
+    # a checkpoint directory of gender_classifier_train.py (embedding_model.ckpt / classifier.ckpt, strict
+    # keys): the external classifier of ACC_external / ACC_external_orig in both model types (reference
+    # :261-269) and the frozen in-graph classifier of model_type endtoend
+    ck = hparams.get("external_classifier_ckpt")
+    if ck:
+        from speech_anonymization_amd.gender import load_external_classifier
+        hparams["external_classifier"] = load_external_classifier(ck)
     if hparams["model_type"] == "convae":
         model = convae.ConvAutoencoder(precision=hparams.get("precision", "bf16x3"))
     elif hparams["model_type"] == "endtoend":              # reference :551-558 (EndToEnd.ConvReconstruction)
         from speech_anonymization_amd import endtoend, xvector
-        clf = xvector.EncoderClassifier()
-        ck = hparams.get("external_classifier_ckpt")       # directory with embedding_model.ckpt / classifier.ckpt
-        if ck:
-            clf.embedding_model.load_state_dict(torch.load(os.path.join(ck, "embedding_model.ckpt"),
-                                                           map_location="cpu", weights_only=True))
-            clf.classifier.load_state_dict(torch.load(os.path.join(ck, "classifier.ckpt"),
-                                                      map_location="cpu", weights_only=True))
+        clf = load_external_classifier(ck) if ck else xvector.EncoderClassifier()
         model = endtoend.ConvReconstruction(clf, precision=hparams.get("precision", "bf16x3"))
     else:
         raise SystemExit("this path implements model_type convae and endtoend (SURVEY.md 8)")
