@@ -40,7 +40,13 @@ def total_loss(recon_l, sex_l, util_l, conf_l, w, model_type="convae"):
 
 
 def cosine_similarity_loss(x1, x2):
-    """sum(1 - cos(x1, x2; dim=2, eps=1e-6)) / S   -- divides by S = shape[1], not B*S."""
+    """sum(1 - cos(x1, x2; dim=2, eps=1e-6)) / S   -- divides by S = shape[1], not B*S.
+
+    The cosine is the INSTALLED torch's (kept: gen_golden.py asserts bit-equality with the
+    reference's own class, which runs on the same torch).  For a row with a norm below eps that
+    departs from the reference's pinned torch 1.10: 1.10 clamps the product, x1.x2 /
+    sqrt(max(|x1|^2 |x2|^2, eps^2)), torch >= 1.12 clamps each norm.  The HIP kernels follow 1.10;
+    on such rows tests/ref64.py (the 1.10 formula in fp64) is the arbiter, not this function."""
     sim = F.cosine_similarity(x1, x2, dim=2, eps=1e-6)
     loss = 1 - sim
     return torch.sum(loss) / loss.shape[1]
@@ -49,7 +55,10 @@ def cosine_similarity_loss(x1, x2):
 def pairwise_cosine_dists(x):
     """What utils/ClusterMI.py:_pairwise_dists produces with cosine_distance_2d: a symmetric
     N x N matrix d[i,j] = 1 - cos(x_i, x_j) with a zero diagonal (the reference fills it
-    with N/2 rolls; the values are those of F.cosine_similarity(dim=1, eps=1e-8))."""
+    with N/2 rolls; the values are those of F.cosine_similarity(dim=1, eps=1e-8)).
+    As in cosine_similarity_loss this is the installed torch's cosine: rows with a norm below eps
+    (1e-8 here) are clamped per norm, where torch 1.10 and sa_cluster_mi clamp the product of the
+    squared norms; tests/ref64.py is the arbiter for such rows."""
     N = x.shape[0]
     d = torch.zeros(N, N)
     for i in range(N):

@@ -642,6 +642,12 @@ def recon_loss(a, b, kind, want_grad=True):
     """kind "l1" | "mse"; returns (loss[1], grad like a or None)."""
     lib = L.load()
     n = a.numel()
+    # the kernel reads float4: a contiguous view at a storage offset that is not a multiple of four
+    # elements (x.reshape(-1)[1:]) is copied to a fresh, aligned allocation (never in the train step)
+    if a.data_ptr() % 16:
+        a = a.clone()
+    if b.data_ptr() % 16:
+        b = b.clone()
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     grad = torch.empty_like(a) if want_grad else None
     ws = torch.empty(lib.sa_loss_workspace_bytes() // 8, dtype=torch.float64, device=a.device)
