@@ -403,6 +403,61 @@ int sa_xv_pool_affine(const float* pz, const float* s, const float* t, const flo
                       float eps, float* pooled, void* stream);
 int sa_xv_pool_affine_bwd(const float* g, const float* s, int B, int C, float* gz, void* stream);
 
+/* ---- model_type fcae (sa_fcae.hip): the reference's FullyConnectedAutoencoder, models/FullyConnected.py:65-104,
+ * 118-159, fp32.  feats [B][T][80]; T >= 2; tiles of 64 frames that never cross an utterance.
+ *   wb: HOST array of 16 device pointers, the weights then the biases of encoder.0/2/4, decoder.0/2/4,
+ *     sex_classifier.initial.0/2 (nn.Linear layout).  hw: HOST array of 16 device pointers of classify:
+ *     0.weight 0.bias 1.weight 1.bias 1.running_mean 1.running_var 3.weight 3.bias 5.weight 5.bias 6.weight
+ *     6.bias 6.running_mean 6.running_var 7.weight 7.bias.
+ *   sa_fc_tiles(T): tiles per utterance.  sa_fc_groups(B, T): workgroups G of the two backward frame passes.
+ *   sa_fc_nparam(): floats of one weight-gradient record (the 8 weights, then the 8 biases, in wb order).
+ *   sa_fc_nhead(): floats of dhead (d 0.weight 0.bias 1.weight 1.bias 3.weight 3.bias 5.weight 5.bias 6.weight
+ *     6.bias 7.weight 7.bias).  sa_fc_max_rows(): largest B of the head launches (larger: -EINVAL).
+ * forward:
+ *   sa_fc_enc_fwd: h1 [B][T][60], h2 [B][T][40] (post-ReLU), z [B][T][20]; bnpart [B*tiles][20][2] (fp64 sum, sum of
+ *     squares per BatchNorm channel; element (t, j) of an utterance is in channel (20 t + j) / T).
+ *   sa_fc_bn_fin: bnf [4][20] = mean, rstd, scale, shift; train != 0: batch statistics + running update,
+ *     else the running statistics (bnpart unused).
+ *   sa_fc_mid_fwd: a1, u [B][T][40] (initial, post-ReLU), d1 [B][T][40], d2 [B][T][60] (decoder, post-ReLU),
+ *     recon [B][T][80]; poolpart [B*tiles][2][40] (fp64 sum, sum of squares of u over the tile's frames).
+ *   sa_fc_head_fwd: pooled [B][80] = (mean + 1e-5 ((1 - 9) noise + 9) if noise [B][40] != NULL, unbiased std + 1e-5),
+ *     pst [B][80] = (mean, std) without either offset, h1 [B][40] (pre-BatchNorm), f1 [4][40], h2 [B][40]
+ *     (post-ReLU), h3 [B][20] (pre-BatchNorm), f2 [4][20], logp [B][2].
+ * backward:
+ *   sa_fc_head_bwd: dlogp [B][2] -> dhead, dpooled [B][80] (the BatchNorm statistics are recomputed from h1 / h3 in
+ *     fp64 by the forward's own operations; f1 / f2 are only the forward's record of them).
+ *   sa_fc_mid_bwd: d_recon [B][T][80], dpooled -> dzdec (decoder's d z), dzn (d of the BatchNorm output) [B][T][20];
+ *     wpart [G][nparam] (decoder.* and initial.* slices), bnbpart [G][20][2] (fp64 sum dy, sum dy * zhat).
+ *   sa_fc_bn_bwd_fin: coef [3][20] of d z = c1 dzn + c2 z + c3 (GradReverse folded in), dgamma, dbeta [20].
+ *   sa_fc_enc_bwd: wpart (encoder.* slices).  No gradient to feats.
+ *   sa_fc_wreduce: grads [nparam] = the G records added in order (fp64). */
+int sa_fc_tiles(int T);
+int sa_fc_groups(int B, int T);
+int sa_fc_nparam(void);
+int sa_fc_nhead(void);
+int sa_fc_max_rows(void);
+int sa_fc_enc_fwd(const float* feats, const void* const* wb, float* h1, float* h2, float* z, double* bnpart,
+                  int B, int T, void* stream);
+int sa_fc_bn_fin(const double* bnpart, int npart, const float* gamma, const float* beta, float* run_mean,
+                 float* run_var, float* bnf, int B, int T, int train, float eps, float momentum, void* stream);
+int sa_fc_mid_fwd(const float* z, const float* bnf, const void* const* wb, float* a1, float* u, float* d1,
+                  float* d2, float* recon, double* poolpart, int B, int T, void* stream);
+int sa_fc_head_fwd(const double* poolpart, const float* noise, const void* const* hw, float* pooled, float* pst,
+                   float* h1, float* f1, float* h2, float* h3, float* f2, float* logp, int B, int T, int train,
+                   float eps, float momentum, void* stream);
+int sa_fc_head_bwd(const float* dlogp, const float* logp, const float* pooled, const float* h1,
+                   const float* h2, const float* h3, const void* const* hw, float* dhead,
+                   float* dpooled, int B, int train, float eps, void* stream);
+int sa_fc_mid_bwd(const float* d_recon, const float* dpooled, const float* pst, const float* z, const float* bnf,
+                  const float* a1, const float* u, const float* d1, const float* d2, const void* const* wb,
+                  float* dzn, float* dzdec, float* wpart, double* bnbpart, int B, int T, void* stream);
+int sa_fc_bn_bwd_fin(const double* bnbpart, int npart, const float* gamma, const float* bnf, float* coef,
+                     float* dgamma, float* dbeta, int B, int T, int train, void* stream);
+int sa_fc_enc_bwd(const float* feats, const float* h1, const float* h2, const float* z, const float* dzn,
+                  const float* dzdec, const float* coef, const void* const* wb, float* wpart, int B, int T,
+                  void* stream);
+int sa_fc_wreduce(const float* wpart, int G, float* grads, void* stream);
+
 /* ---- k-NN mutual information (sa_mi.hip): utils/ClusterMI.py:88-121,
  * utils/GroupSamplingMI.py:49-61, utils/mi_loss.py:14-17 ------------------------------ */
 int sa_cluster_mi(const float* X, const long long* y, const long long* idx, int iters, int n, int D,

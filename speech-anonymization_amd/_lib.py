@@ -125,6 +125,9 @@ SYMBOLS = [
     "sa_add_layernorm_fwd", "sa_layernorm_bwd", "sa_reflect_pad_fwd", "sa_reflect_pad_bwd", "sa_ln_leaky_fwd", "sa_ln_leaky_bwd", "sa_bias_multi", "sa_asr_block0_fwd", "sa_asr_block0_bwd", "sa_wgrad_reduce_multi", "sa_clip_grads",
     "sa_xv_tdnn_fwd_train", "sa_xv_tdnn_ntiles", "sa_xv_colsums", "sa_xv_tdnn_wgrad", "sa_xv_wgrad_reduce",
     "sa_xv_tdnn_dgrad", "sa_xv_pool_affine", "sa_xv_pool_affine_bwd",
+    "sa_fc_tiles", "sa_fc_groups", "sa_fc_nparam", "sa_fc_nhead", "sa_fc_max_rows", "sa_fc_enc_fwd", "sa_fc_bn_fin",
+    "sa_fc_mid_fwd", "sa_fc_head_fwd", "sa_fc_head_bwd", "sa_fc_mid_bwd", "sa_fc_bn_bwd_fin", "sa_fc_enc_bwd",
+    "sa_fc_wreduce",
 ]
 
 _lib = None

@@ -2,7 +2,7 @@
 """Entry point with the reference's command line (speechbrain_convae_train.py:1-8,514-615):
 
     python speechbrain_convae_train.py speechbrain_configs/convae.yaml \
-        --device cuda:0 --model_type convae --folder <output_dir> [--key value overrides]
+        --device cuda:0 --model_type [convae / fcae / endtoend] --folder <output_dir> [--key value overrides]
 
     # data-parallel on one node (one process per GPU, RCCL):
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -22,12 +22,28 @@ from speech_anonymization_amd import brain as B, convae, data, distributed as sd
 from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
 
 
+MODEL_TYPES = ("convae", "fcae", "endtoend")
+
+
+def check_model_type(model_type, run_opts, environ=None):
+    """what can be refused before anything touches a GPU or a process group"""
+    environ = os.environ if environ is None else environ
+    if model_type not in MODEL_TYPES:
+        raise SystemExit(f"unknown model_type {model_type!r}: this path implements convae, fcae and endtoend")
+    if model_type == "fcae":
+        if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("model_type fcae runs on one GPU: data parallelism is not implemented for it")
+        if run_opts.get("hip_graph"):
+            raise SystemExit("model_type fcae does not support --hip_graph (its step is nine launches)")
+
+
 def main(argv):
     hparams_file, run_opts, overrides = parse_arguments(argv)
     synthetic = overrides.pop("synthetic", None)
     n_samples = int(overrides.pop("synthetic_samples", 161120))
     with open(hparams_file) as fin:
         hparams = load_hyperpyyaml(fin, overrides)
+    check_model_type(hparams["model_type"], run_opts)
     rank, local_rank, world = sdist.ddp_init_group(run_opts)
     run_opts.setdefault("device", f"cuda:{local_rank}")
     if sdist.if_main_process():
@@ -46,8 +62,9 @@ def main(argv):
         from speech_anonymization_amd import endtoend, xvector
         clf = load_external_classifier(ck) if ck else xvector.EncoderClassifier()
         model = endtoend.ConvReconstruction(clf, precision=hparams.get("precision", "bf16x3"))
-    else:
-        raise SystemExit("this path implements model_type convae and endtoend (SURVEY.md 8)")
+    else:                                                  # reference :556-558 (FullyConnected.FullyConnectedAutoencoder)
+        from speech_anonymization_amd import fcae          # fp32 whatever `precision` says
+        model = fcae.FullyConnectedAutoencoder(80, hparams["batch_size"])
 
     sa_brain = B.SexAnonymizationTraining(modules=hparams["modules"], opt_class=hparams["Adam"],
                                           hparams=hparams, run_opts=run_opts,
