@@ -423,6 +423,11 @@ int sa_xv_pool_affine_bwd(const float* g, const float* s, int B, int C, float* g
  *   sa_fc_head_fwd: pooled [B][80] = (mean + 1e-5 ((1 - 9) noise + 9) if noise [B][40] != NULL, unbiased std + 1e-5),
  *     pst [B][80] = (mean, std) without either offset, h1 [B][40] (pre-BatchNorm), f1 [4][40], h2 [B][40]
  *     (post-ReLU), h3 [B][20] (pre-BatchNorm), f2 [4][20], logp [B][2].
+ * inference:
+ *   sa_fc_recon_fwd: recon [B][T][80] = decoder(encoder(feats)) in ONE launch (grid B x tiles): the six layers through
+ *     the forward's own tile products, activations in two LDS buffers, nothing else written.  Bit-identical to the
+ *     recon of sa_fc_enc_fwd + sa_fc_mid_fwd.  No classifier branch, so none of its limits: any B >= 1
+ *     (sa_fc_max_rows does not apply; B <= 65535, the grid's extent), T >= 1.
  * backward:
  *   sa_fc_head_bwd: dlogp [B][2] -> dhead, dpooled [B][80] (the BatchNorm statistics are recomputed from h1 / h3 in
  *     fp64 by the forward's own operations; f1 / f2 are only the forward's record of them).
@@ -442,6 +447,7 @@ int sa_fc_bn_fin(const double* bnpart, int npart, const float* gamma, const floa
                  float* run_var, float* bnf, int B, int T, int train, float eps, float momentum, void* stream);
 int sa_fc_mid_fwd(const float* z, const float* bnf, const void* const* wb, float* a1, float* u, float* d1,
                   float* d2, float* recon, double* poolpart, int B, int T, void* stream);
+int sa_fc_recon_fwd(const float* feats, const void* const* wb, float* recon, int B, int T, void* stream);
 int sa_fc_head_fwd(const double* poolpart, const float* noise, const void* const* hw, float* pooled, float* pst,
                    float* h1, float* f1, float* h2, float* h3, float* f2, float* logp, int B, int T, int train,
                    float eps, float momentum, void* stream);

@@ -152,6 +152,10 @@ class ConvAutoencoder(nn.Module):
         # walking the module tree costs ~0.15 ms a call: the (names, parameters) lists are cached
         # and revalidated against the owners' registries (56 identity checks, ~5 us), so replacing
         # ANY parameter object (load into a sub-module, .to(), pruning, ...) is noticed
+        names, params = self._named_params()
+        return _ConvAEFn.apply(self, names, feats, *params)
+
+    def _named_params(self):
         c = self.__dict__.get("_np_cache")
         if c is None or any(o[n] is not p for o, n, p in c[2]):
             names, params, owners = [], [], []
@@ -162,7 +166,24 @@ class ConvAutoencoder(nn.Module):
                         params.append(p)
                         owners.append((mod._parameters, pname, p))
             c = self.__dict__["_np_cache"] = (tuple(names), tuple(params), owners)
-        return _ConvAEFn.apply(self, c[0], feats, *c[1])
+        return c[0], c[1]
+
+    @torch.no_grad()
+    def reconstruct(self, feats):
+        """recon [B, T, 80] for inference: the launches of the eval-mode forward's reconstruction path
+        (conv1toC, the eight convolutions, convCto1, the InstanceNorm finalisers) with the same arguments,
+        hence the bits of ``model.eval(); model(feats)[0]`` -- in train mode too, since this path holds only
+        InstanceNorm.  The classifier branch does not run: no running statistic or step counter moves,
+        nothing is kept for a backward.  Refuses what forward refuses."""
+        if not torch.is_tensor(feats) or feats.dim() != 3:
+            raise SaHipError("ConvAutoencoder expects feats [B, T, 80]")
+        x0, B, T, Ltot = _input_rows(feats)
+        P = dict(zip(*self._named_params()))
+        W = _packed(self, P)
+        pw = lambda k, kind: W[(k, kind)]
+        cg, inorm = _launchers(self, P, B)
+        y, _, _ = _encoder_launches(self, P, pw, cg, inorm, x0, Ltot, False)
+        return _decoder_launches(P, pw, cg, inorm, y[5], Ltot)[-1].view(B, T, 80)
 
     def _wgrad_stream(self, device):
         if getattr(self, "_wgs", None) is None and device.type == "cuda":
@@ -324,6 +345,82 @@ def _noise(model, B, device):
     return (g / g.max()).contiguous()
 
 
+def _input_rows(feats):
+    """feats [B, T, 80] -> (x0 [B, T*80] fp32, B, T, T*80); the refusals of forward and reconstruct"""
+    B, T, Fd = feats.shape
+    Ltot = T * Fd
+    if Fd != 80 or Ltot % 4:
+        raise SaHipError("ConvAutoencoder expects feats [B, T, 80] with T*80 divisible by 4")
+    if not feats.is_cuda:
+        raise SaHipError("ConvAutoencoder runs on the GPU only (no CPU fallback)")
+    return feats.detach().reshape(B, Ltot).contiguous().float(), B, T, Ltot
+
+
+def _launchers(model, P, B, A=None):
+    """(cg, inorm): a convolution launch and an InstanceNorm finaliser as forward and reconstruct issue them.
+    A: dict that receives the bf16 operand cache of the weight gradients (None: no cache)."""
+    def cg(x, w, key, *args, **kw):
+        if A is not None and key is not None and P[key].requires_grad:
+            A[key] = kw["a_out"] = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        out = _conv(x, w, *args, **kw)
+        if model.store_bf16_probe in (1, 2) or (model.store_bf16_probe == 4 and str(key).startswith("decoder")):
+            y_ = out[0] if isinstance(out, tuple) else out
+            if y_.dtype == torch.float32:
+                y_.copy_(y_.bfloat16())
+        return out
+
+    def inorm(stats, n, prefix, C):
+        if model.fused_finalize or model.fused_in_fwd:
+            return ops.reduce_finalize(L.FIN_IN_FWD, stats, B, C, count=n, gamma=P[prefix + ".weight"],
+                                       beta=P[prefix + ".bias"])
+        sums = ops.sum_partials(stats, B)
+        return ops.fin_in_fwd(sums, B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
+    return cg, inorm
+
+
+def _encoder_launches(model, P, pw, cg, inorm, x0, Ltot, want_pro_stats):
+    """encoder + decoder.0 -> ([y0..y5], [n1..n4], a4_stats or None).  decoder.0 belongs here: it stages the
+    transformed encoder output, and in train mode leaves the statistics the classifier's input BatchNorm
+    needs as a by-product of its prologue (want_pro_stats)."""
+    L2, L4 = Ltot // 2, Ltot // 4
+    y0 = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], model.act_dtype)
+    if model.store_bf16_probe in (1, 2) and y0.dtype == torch.float32:
+        y0.copy_(y0.bfloat16())
+    y1, st = cg(y0, pw("encoder.2.weight", "conv_fwd"), "encoder.2.weight", P["encoder.2.bias"], 32, 64, 2, 1,
+                ops.taps_conv(K5, 1, 2), L2, swish=True, want_stats=True)
+    n1 = inorm(st, L2, "encoder.3", 64)
+    y2, st = cg(y1, pw("encoder.5.weight", "conv_fwd"), "encoder.5.weight", P["encoder.5.bias"], 64, 64, 1, 1,
+                ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True)
+    n2 = inorm(st, L2, "encoder.6", 64)
+    y3, st = cg(y2, pw("encoder.8.weight", "conv_fwd"), "encoder.8.weight", P["encoder.8.bias"], 64, 128, 2, 1,
+                ops.taps_conv(K5, 1, 2), L4, s1=n2[2], t1=n2[3], swish=True, want_stats=True)
+    n3 = inorm(st, L4, "encoder.9", 128)
+    y4, st = cg(y3, pw("encoder.11.weight", "conv_fwd"), "encoder.11.weight", P["encoder.11.bias"], 128, 128, 1, 1,
+                ops.taps_conv(K5, 1, 2), L4, s1=n3[2], t1=n3[3], swish=True, want_stats=True)
+    n4 = inorm(st, L4, "encoder.12", 128)
+    y5 = cg(y4, pw("decoder.0.weight", "conv_fwd"), "decoder.0.weight", P["decoder.0.bias"], 128, 128, 1, 1,
+            ops.taps_conv(K5, 1, 2), L4, s1=n4[2], t1=n4[3], swish=True, want_pro_stats=want_pro_stats)
+    a4_stats = None
+    if want_pro_stats:
+        y5, a4_stats = y5
+    return [y0, y1, y2, y3, y4, y5], [n1, n2, n3, n4], a4_stats
+
+
+def _decoder_launches(P, pw, cg, inorm, y5, Ltot):
+    """decoder.1 ... decoder.8 -> (y6, n6, y7, y8, n8, recon [B, Ltot])"""
+    L2 = Ltot // 2
+    y6, st = cg(y5, pw("decoder.1.weight", "convT_fwd"), "decoder.1.weight", P["decoder.1.bias"], 128, 64, 1, 2,
+                ops.UP2, L2, want_stats=True)
+    n6 = inorm(st, L2, "decoder.2", 64)
+    y7 = cg(y6, pw("decoder.4.weight", "conv_fwd"), "decoder.4.weight", P["decoder.4.bias"], 64, 64, 1, 1,
+            ops.taps_conv(K5, 1, 2), L2, s1=n6[2], t1=n6[3], swish=True)
+    y8, st = cg(y7, pw("decoder.5.weight", "convT_fwd"), "decoder.5.weight", P["decoder.5.bias"], 64, 32, 1, 2,
+                ops.UP2, Ltot, want_stats=True)
+    n8 = inorm(st, Ltot, "decoder.6", 32)
+    recon = ops.convCto1(y8, P["decoder.8.weight"], P["decoder.8.bias"], n8[2], n8[3], True)
+    return y6, n6, y7, y8, n8, recon
+
+
 class _ConvAEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, names, feats, *params):
@@ -333,15 +430,9 @@ class _ConvAEFn(torch.autograd.Function):
         P = dict(zip(names, params))
         dt = model.act_dtype
         train = model.training
-        B, T, Fd = feats.shape
-        Ltot = T * Fd
-        if Fd != 80 or Ltot % 4:
-            raise SaHipError("ConvAutoencoder expects feats [B, T, 80] with T*80 divisible by 4")
-        if not feats.is_cuda:
-            raise SaHipError("ConvAutoencoder runs on the GPU only (no CPU fallback)")
+        x0, B, T, Ltot = _input_rows(feats)
         L2, L4 = Ltot // 2, Ltot // 4
         S = {}                                                  # saved for backward
-        x0 = feats.detach().reshape(B, Ltot).contiguous().float()
         W = _packed(model, P)
         pw = lambda k, kind: W[(k, kind)]
         # activation cache: each conv also writes its transformed input rows in bf16, the operand
@@ -350,24 +441,8 @@ class _ConvAEFn(torch.autograd.Function):
         cache_a = (train and model.cache_wgrad_operand and any(ctx.needs_input_grad)
                    and ops.WGRAD_CODE[model.precision] in (L.BF16X1F, L.BF16) and model.kcode != L.FP8)
 
-        def cg(x, w, key, *args, **kw):
-            if cache_a and key is not None and P[key].requires_grad:
-                A[key] = kw["a_out"] = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-            out = _conv(x, w, *args, **kw)
-            if model.store_bf16_probe in (1, 2) or (model.store_bf16_probe == 4 and str(key).startswith("decoder")):
-                y_ = out[0] if isinstance(out, tuple) else out
-                if y_.dtype == torch.float32:
-                    y_.copy_(y_.bfloat16())
-            return out
-
+        cg, inorm = _launchers(model, P, B, A if cache_a else None)
         ff = model.fused_finalize
-
-        def inorm(stats, n, prefix, C):
-            if ff or model.fused_in_fwd:
-                return ops.reduce_finalize(L.FIN_IN_FWD, stats, B, C, count=n, gamma=P[prefix + ".weight"],
-                                           beta=P[prefix + ".bias"])
-            sums = ops.sum_partials(stats, B)
-            return ops.fin_in_fwd(sums, B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
 
         def bn_stats(stats, count, mod, prefix, C, ci):
             """train-mode BatchNorm from the per-tile partial statistics of the producing launch"""
@@ -401,28 +476,9 @@ class _ConvAEFn(torch.autograd.Function):
         # SyncBatchNorm: one tiny all-reduce, device-resident; None on one process
         gc = model._bn_global_counts([B * L4, B * La, B * Lb, B * Lc, B, B], feats.device) if train else None
         cdev = lambda i: None if gc is None else gc[i:i + 1]
-        # ---------------- encoder ----------------
-        y0 = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], dt)
-        if model.store_bf16_probe in (1, 2) and y0.dtype == torch.float32:
-            y0.copy_(y0.bfloat16())
-        y1, st = cg(y0, pw("encoder.2.weight", "conv_fwd"), "encoder.2.weight", P["encoder.2.bias"], 32, 64, 2, 1,
-                               ops.taps_conv(K5, 1, 2), L2, swish=True, want_stats=True)
-        n1 = inorm(st, L2, "encoder.3", 64)
-        y2, st = cg(y1, pw("encoder.5.weight", "conv_fwd"), "encoder.5.weight", P["encoder.5.bias"], 64, 64, 1, 1,
-                               ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True)
-        n2 = inorm(st, L2, "encoder.6", 64)
-        y3, st = cg(y2, pw("encoder.8.weight", "conv_fwd"), "encoder.8.weight", P["encoder.8.bias"], 64, 128, 2, 1,
-                               ops.taps_conv(K5, 1, 2), L4, s1=n2[2], t1=n2[3], swish=True, want_stats=True)
-        n3 = inorm(st, L4, "encoder.9", 128)
-        y4, st = cg(y3, pw("encoder.11.weight", "conv_fwd"), "encoder.11.weight", P["encoder.11.bias"], 128, 128, 1, 1,
-                               ops.taps_conv(K5, 1, 2), L4, s1=n3[2], t1=n3[3], swish=True, want_stats=True)
-        n4 = inorm(st, L4, "encoder.12", 128)
-        # decoder.0 goes first: it stages the same transformed encoder output the classifier's input
-        # BatchNorm needs statistics of, and leaves them as a by-product of its prologue
-        y5 = cg(y4, pw("decoder.0.weight", "conv_fwd"), "decoder.0.weight", P["decoder.0.bias"], 128, 128, 1, 1,
-                ops.taps_conv(K5, 1, 2), L4, s1=n4[2], t1=n4[3], swish=True, want_pro_stats=train)
-        if train:
-            y5, a4_stats = y5
+        # ---------------- encoder (and decoder.0: it stages the same transformed encoder output the
+        # classifier's input BatchNorm needs statistics of) ----------------
+        (y0, y1, y2, y3, y4, y5), (n1, n2, n3, n4), a4_stats = _encoder_launches(model, P, pw, cg, inorm, x0, Ltot, train)
         # ---------------- sex classifier (GradReverse = identity forward) ----------------
         bn_n = bn_stats(a4_stats if train else None, B * L4, cls.norm, "sex_classifier.norm", 128, 0)
         r0, st = cg(y4, pw("sex_classifier.tdnn.0.weight", "conv_fwd"), "sex_classifier.tdnn.0.weight",
@@ -474,15 +530,7 @@ class _ConvAEFn(torch.autograd.Function):
         if plan:                               # this rank's rows of the global log-probabilities
             logp = logp_all[plan[0]:plan[0] + B]
         # ---------------- decoder ----------------
-        y6, st = cg(y5, pw("decoder.1.weight", "convT_fwd"), "decoder.1.weight", P["decoder.1.bias"], 128, 64, 1, 2,
-                               ops.UP2, L2, want_stats=True)
-        n6 = inorm(st, L2, "decoder.2", 64)
-        y7 = cg(y6, pw("decoder.4.weight", "conv_fwd"), "decoder.4.weight", P["decoder.4.bias"], 64, 64, 1, 1,
-                           ops.taps_conv(K5, 1, 2), L2, s1=n6[2], t1=n6[3], swish=True)
-        y8, st = cg(y7, pw("decoder.5.weight", "convT_fwd"), "decoder.5.weight", P["decoder.5.bias"], 64, 32, 1, 2,
-                               ops.UP2, Ltot, want_stats=True)
-        n8 = inorm(st, Ltot, "decoder.6", 32)
-        recon = ops.convCto1(y8, P["decoder.8.weight"], P["decoder.8.bias"], n8[2], n8[3], True)
+        y6, n6, y7, y8, n8, recon = _decoder_launches(P, pw, cg, inorm, y5, Ltot)
         if hs is not None:
             main.wait_stream(hs)
             for tns in (H1, H2, logp_all, f1[0], f2[0]):      # allocated on the side stream, consumed on this one
@@ -496,7 +544,7 @@ class _ConvAEFn(torch.autograd.Function):
                  dims=(B, T, Ltot, L2, L4, La, Lb, Lc), train=train, W=W, A=A, gc=gc, fused_head=fused_head)
         ctx.S, ctx.model, ctx.names, ctx.params = S, model, names, params
         ctx.need_input_grad = feats.requires_grad
-        return recon.view(B, T, Fd), logp
+        return recon.view(B, T, 80), logp
 
     @staticmethod
     def backward(ctx, d_recon, d_logp):

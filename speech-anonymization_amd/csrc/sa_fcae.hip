@@ -16,6 +16,7 @@
 // The hidden activations are STORED by the forward (300 floats per frame) and read back by the backward.
 //
 // forward : sa_fc_enc_fwd -> sa_fc_bn_fin -> sa_fc_mid_fwd -> sa_fc_head_fwd
+// inference (reconstruction only): sa_fc_recon_fwd, one launch
 // backward: sa_fc_head_bwd -> sa_fc_mid_bwd -> sa_fc_bn_bwd_fin -> sa_fc_enc_bwd -> sa_fc_wreduce
 //
 // Statistics (BatchNorm channel sums, pooling sums) and the weight-gradient splits are accumulated per
@@ -373,6 +374,49 @@ __global__ __launch_bounds__(FC_NT) void fc_mid_fwd_kernel(const float* __restri
   stage_w<80, 60>(Wl, W.w[5], tid);
   __syncthreads();
   tile_gemm<60, 80>(D2, Wl, tid, [&](int m, int n, float v) {
+    if (m < nvalid) recon[(f0 + m) * 80 + n] = v + W.b[5][n];
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------
+// inference: recon = decoder(encoder(feats)) in one launch.  The six layers of sa_fc_enc_fwd and of
+// sa_fc_mid_fwd's decoder half, through the same tile_gemm instantiations (each output accumulated in the
+// same order: the same bits as the train forward's recon); the tile's activations alternate between two
+// LDS buffers and only recon leaves the workgroup.  No statistics, no classifier branch.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FC_NT) void fc_recon_fwd_kernel(const float* __restrict__ feats, FcW W,
+                                                             float* __restrict__ recon, int T) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* P = reinterpret_cast<float*>(smem);                     // [64][80]: feats, h2 [64][40], d1 [64][40]
+  float* Q = P + FC_TM * 80;                                     // [64][80]: h1 [64][60], z [64][20], d2 [64][60]
+  float* Wl = Q + FC_TM * 80;
+  const int tid = threadIdx.x, ti = blockIdx.x, b = blockIdx.y, t0 = ti * FC_TM;
+  const int nvalid = min(FC_TM, T - t0);
+  const size_t f0 = (size_t)b * T + t0;
+  load_tile<80>(P, feats + f0 * 80, nvalid, tid);
+  stage_w<60, 80>(Wl, W.w[0], tid);
+  __syncthreads();
+  tile_gemm<80, 60>(P, Wl, tid, [&](int m, int n, float v) { Q[m * 60 + n] = fmaxf(v + W.b[0][n], 0.0f); });
+  __syncthreads();
+  stage_w<40, 60>(Wl, W.w[1], tid);
+  __syncthreads();
+  tile_gemm<60, 40>(Q, Wl, tid, [&](int m, int n, float v) { P[m * 40 + n] = fmaxf(v + W.b[1][n], 0.0f); });
+  __syncthreads();
+  stage_w<20, 40>(Wl, W.w[2], tid);
+  __syncthreads();
+  tile_gemm<40, 20>(P, Wl, tid, [&](int m, int n, float v) { Q[m * 20 + n] = v + W.b[2][n]; });
+  __syncthreads();
+  stage_w<40, 20>(Wl, W.w[3], tid);
+  __syncthreads();
+  tile_gemm<20, 40>(Q, Wl, tid, [&](int m, int n, float v) { P[m * 40 + n] = fmaxf(v + W.b[3][n], 0.0f); });
+  __syncthreads();
+  stage_w<60, 40>(Wl, W.w[4], tid);
+  __syncthreads();
+  tile_gemm<40, 60>(P, Wl, tid, [&](int m, int n, float v) { Q[m * 60 + n] = fmaxf(v + W.b[4][n], 0.0f); });
+  __syncthreads();
+  stage_w<80, 60>(Wl, W.w[5], tid);
+  __syncthreads();
+  tile_gemm<60, 80>(Q, Wl, tid, [&](int m, int n, float v) {
     if (m < nvalid) recon[(f0 + m) * 80 + n] = v + W.b[5][n];
   });
 }
@@ -824,6 +868,9 @@ __global__ __launch_bounds__(FC_NT) void fc_wreduce_kernel(const float* __restri
 
 constexpr size_t LDS_ENC_FWD = fc_lds(200), LDS_MID_FWD = fc_lds(180);
 constexpr size_t LDS_MID_BWD = fc_lds(340) + 80 * sizeof(float), LDS_ENC_BWD = fc_lds(300);
+// two activation buffers of 64 x 80 floats + one staged matrix, without the fp64 reduction scratch of fc_lds()
+constexpr size_t LDS_RECON = ((size_t)FC_TM * 160 + WL_FLOATS) * sizeof(float);
+static_assert(LDS_RECON + 544 * sizeof(double) == fc_lds(160), "sa_fc_recon_fwd: LDS layout");
 
 template <class KERN>
 int fc_allow_lds(KERN kern, bool& done) {
@@ -858,6 +905,8 @@ inline FcHead fc_head(const void* const* hw) {
   return FcHead{c(0), c(1), c(2), c(3), m(4), m(5), c(6), c(7), c(8), c(9), c(10), c(11), m(12), m(13), c(14), c(15)};
 }
 inline bool fc_shape_ok(int B, int T) { return B >= 1 && T >= 2 && (long long)B * T * 80 < (1ll << 31); }
+// the reconstruction alone has no pooling (T - 1) and no head: one frame is enough, and B is the grid's y extent
+inline bool fc_recon_shape_ok(int B, int T) { return B >= 1 && B <= 65535 && T >= 1 && (long long)B * T * 80 < (1ll << 31); }
 
 }  // namespace
 
@@ -896,6 +945,15 @@ extern "C" int sa_fc_mid_fwd(const float* z, const float* bnf, const void* const
   if (int rc = fc_allow_lds(fc_mid_fwd_kernel, ok)) return rc;
   hipLaunchKernelGGL(fc_mid_fwd_kernel, dim3(sa_div_up(T, FC_TM), B), dim3(FC_NT), LDS_MID_FWD,
                      reinterpret_cast<hipStream_t>(stream), z, bnf, fc_w(wb), a1, u, d1, d2, recon, poolpart, T);
+  return fc_last();
+}
+
+extern "C" int sa_fc_recon_fwd(const float* feats, const void* const* wb, float* recon, int B, int T, void* stream) {
+  if (!feats || !fc_all(wb, 16) || !recon || !fc_recon_shape_ok(B, T)) return -22;
+  static bool ok = false;
+  if (int rc = fc_allow_lds(fc_recon_fwd_kernel, ok)) return rc;
+  hipLaunchKernelGGL(fc_recon_fwd_kernel, dim3(sa_div_up(T, FC_TM), B), dim3(FC_NT), LDS_RECON,
+                     reinterpret_cast<hipStream_t>(stream), feats, fc_w(wb), recon, T);
   return fc_last();
 }
 

@@ -56,6 +56,17 @@ class ConvReconstruction(nn.Module):
         self.sex_classifier.eval()                          # BatchNorm running statistics, always
         return self
 
+    @torch.no_grad()
+    def reconstruct(self, feats):
+        """recon [B, T, 80] for inference: the conv stack's launches with forward's arguments, hence the bits
+        of ``model(feats)[0]`` in train and eval mode alike (InstanceNorm only).  The frozen x-vector does not
+        run and nothing is kept for a backward.  Refuses what forward refuses."""
+        if not torch.is_tensor(feats) or feats.dim() != 3:
+            raise SaHipError("ConvReconstruction expects feats [B, T, 80]")
+        x0, B, T, Ltot = _input_rows(feats)
+        P = {k: p for k, p in self.named_parameters() if k.startswith("encoder.")}
+        return _recon_launches(self, P, x0, B, Ltot)[2].view(B, T, 80)
+
     def forward(self, feats):
         names, params = zip(*((k, p) for k, p in self.named_parameters() if k.startswith("encoder.")))
         recon = _ConvRecFn.apply(self, names, feats, *params)
@@ -63,48 +74,55 @@ class ConvReconstruction(nn.Module):
         return recon, logp
 
 
+def _input_rows(feats):
+    """feats [B, T, 80] -> (x0 [B, T*80] fp32, B, T, T*80); the refusals of forward and reconstruct"""
+    B, T, Fd = feats.shape
+    Ltot = T * Fd
+    if Fd != 80 or Ltot % 2:
+        raise SaHipError("ConvReconstruction expects feats [B, T, 80]")
+    if not feats.is_cuda:
+        raise SaHipError("ConvReconstruction runs on the GPU only (no CPU fallback)")
+    return feats.detach().reshape(B, Ltot).contiguous().float(), B, T, Ltot
+
+
+def _recon_launches(model, P, x0, B, Ltot):
+    """the conv stack's launches -> ([y0..y3], [n0..n3], recon [B, Ltot]); what forward and reconstruct run"""
+    dt, code = model.act_dtype, model.kcode
+    L2 = Ltot // 2
+
+    def pack(key, kind):
+        return ops.pack_weights(P[key].detach(), kind, dt, code)
+
+    def inorm(stats, n, prefix, C):
+        return ops.fin_in_fwd(ops.sum_partials(stats, B), B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
+
+    y0, st = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], dt, want_stats=True)
+    n0 = inorm(st, Ltot, "encoder.1", 32)
+    y1, st = ops.conv_gemm(y0, pack("encoder.3.weight", "conv_fwd"), P["encoder.3.bias"], 32, 64, 2, 1,
+                           ops.taps_conv(K5, 1, 2), L2, s1=n0[2], t1=n0[3], swish=True, want_stats=True,
+                           code=code)
+    n1 = inorm(st, L2, "encoder.4", 64)
+    y2, st = ops.conv_gemm(y1, pack("encoder.6.weight", "conv_fwd"), P["encoder.6.bias"], 64, 64, 1, 1,
+                           ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True,
+                           code=code)
+    n2 = inorm(st, L2, "encoder.7", 64)
+    y3, st = ops.conv_gemm(y2, pack("encoder.9.weight", "convT_fwd"), P["encoder.9.bias"], 64, 32, 1, 2,
+                           ops.UP2, Ltot, s1=n2[2], t1=n2[3], swish=True, want_stats=True, code=code)
+    n3 = inorm(st, Ltot, "encoder.10", 32)
+    recon = ops.convCto1(y3, P["encoder.12.weight"], P["encoder.12.bias"], n3[2], n3[3], True)
+    return [y0, y1, y2, y3], [n0, n1, n2, n3], recon
+
+
 class _ConvRecFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, names, feats, *params):
         ctx.set_materialize_grads(False)
-        P = dict(zip(names, params))
-        dt, code = model.act_dtype, model.kcode
-        B, T, Fd = feats.shape
-        Ltot = T * Fd
-        if Fd != 80 or Ltot % 2:
-            raise SaHipError("ConvReconstruction expects feats [B, T, 80]")
-        if not feats.is_cuda:
-            raise SaHipError("ConvReconstruction runs on the GPU only (no CPU fallback)")
-        L2 = Ltot // 2
-        x0 = feats.detach().reshape(B, Ltot).contiguous().float()
-
-        def pack(key, kind):
-            return ops.pack_weights(P[key].detach(), kind, dt, code)
-
-        def inorm(stats, n, prefix, C):
-            return ops.fin_in_fwd(ops.sum_partials(stats, B), B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
-
-        W = {("encoder.3.weight", "conv_fwd"): pack("encoder.3.weight", "conv_fwd"),
-             ("encoder.6.weight", "conv_fwd"): pack("encoder.6.weight", "conv_fwd"),
-             ("encoder.9.weight", "convT_fwd"): pack("encoder.9.weight", "convT_fwd")}
-        y0, st = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], dt, want_stats=True)
-        n0 = inorm(st, Ltot, "encoder.1", 32)
-        y1, st = ops.conv_gemm(y0, W[("encoder.3.weight", "conv_fwd")], P["encoder.3.bias"], 32, 64, 2, 1,
-                               ops.taps_conv(K5, 1, 2), L2, s1=n0[2], t1=n0[3], swish=True, want_stats=True,
-                               code=code)
-        n1 = inorm(st, L2, "encoder.4", 64)
-        y2, st = ops.conv_gemm(y1, W[("encoder.6.weight", "conv_fwd")], P["encoder.6.bias"], 64, 64, 1, 1,
-                               ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True,
-                               code=code)
-        n2 = inorm(st, L2, "encoder.7", 64)
-        y3, st = ops.conv_gemm(y2, W[("encoder.9.weight", "convT_fwd")], P["encoder.9.bias"], 64, 32, 1, 2,
-                               ops.UP2, Ltot, s1=n2[2], t1=n2[3], swish=True, want_stats=True, code=code)
-        n3 = inorm(st, Ltot, "encoder.10", 32)
-        recon = ops.convCto1(y3, P["encoder.12.weight"], P["encoder.12.bias"], n3[2], n3[3], True)
-        ctx.S = dict(x0=x0, y=[y0, y1, y2, y3], n=[n0, n1, n2, n3], dims=(B, T, Ltot, L2))
+        x0, B, T, Ltot = _input_rows(feats)
+        y, n, recon = _recon_launches(model, dict(zip(names, params)), x0, B, Ltot)
+        ctx.S = dict(x0=x0, y=y, n=n, dims=(B, T, Ltot, Ltot // 2))
         ctx.model, ctx.names, ctx.params = model, names, params
         ctx.need_input_grad = feats.requires_grad
-        return recon.view(B, T, Fd)
+        return recon.view(B, T, 80)
 
     @staticmethod
     def backward(ctx, d_recon):

@@ -152,6 +152,18 @@ def mid_fwd(z, bnf, wb):
     return a1, u, d1, d2, recon, poolpart
 
 
+def recon_fwd(feats, wb):
+    """feats [B,T,80] -> recon [B,T,80] = decoder(encoder(feats)), one launch, nothing else stored; the bits of
+    mid_fwd's recon.  Any B >= 1 and T >= 1 (no pooling, no head)."""
+    lib = L.load()
+    B, T, Fd = _f32(feats, "feats").shape
+    if Fd != 80 or T < 1 or B < 1:
+        raise SaHipError("fcae expects feats [B, T, 80] with B >= 1 and T >= 1")
+    recon = torch.empty(B, T, 80, device=feats.device)
+    L.check(lib.sa_fc_recon_fwd(L.ptr(feats), wb, L.ptr(recon), B, T, L.stream()), "sa_fc_recon_fwd")
+    return recon
+
+
 def _rows_ok(B):
     if B > max_rows():
         raise SaHipError(f"fcae: the classifier head runs as one workgroup of at most {max_rows()} utterances, "
@@ -354,6 +366,20 @@ class FullyConnectedAutoencoder(nn.Module):
         self.decoder = nn.Sequential(nn.Linear(20, 40), ReLU(), nn.Linear(40, 60), ReLU(), nn.Linear(60, 80))
         self.sex_classifier = FullyConnSexClassifier(2)
         self.pooling_noise = pooling_noise
+
+    @torch.no_grad()
+    def reconstruct(self, feats):
+        """recon [B, T, 80] = decoder(encoder(feats)) for inference, one launch (sa_fc_recon_fwd): the bits of
+        ``forward(feats)[0]``, in train and eval mode alike (the reconstruction path has no normalisation).
+        The classifier branch does not run, so no running statistic moves, nothing is kept for a backward, and
+        the head's limits do not apply: any B >= 1 (also B = 1 in train mode, B > sa_fc_max_rows) and T >= 1.
+        Refuses what forward refuses (CPU tensors, a feature width other than 80, other dtypes)."""
+        if not torch.is_tensor(feats) or not feats.is_cuda:
+            raise SaHipError("FullyConnectedAutoencoder runs on the GPU only (no CPU fallback)")
+        if feats.dim() != 3:
+            raise SaHipError("fcae expects feats [B, T, 80]")
+        P = {f"{k}.{s}": getattr(self.get_submodule(k), s).detach() for k in FRAME_LAYERS for s in ("weight", "bias")}
+        return recon_fwd(_f32(feats.detach(), "feats"), frame_table(P))
 
     def forward(self, feats):
         c = self.__dict__.get("_np_cache")

@@ -14,7 +14,10 @@ The reference's CategoricalEncoder numbers the classes in order of first appeara
 can swap them; the mapping used is written next to the weights (label_encoder.txt).
 
 Waveform augmentation (EnvCorrupt: an OpenRIR download; TimeDomainSpecAugment) is out of scope:
-the recipe trains without it."""
+the recipe trains without it.
+
+The second half of the module is the same recipe on RECONSTRUCTED features (the reference's
+gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser)."""
 import functools
 import os
 
@@ -179,3 +182,111 @@ class GenderBrain(Brain):
             fn = os.path.join(ckpts[0], ("normalizer" if name == "mean_var_norm" else name) + ".ckpt")
             sd = torch.load(fn, map_location="cpu", weights_only=True)
             self.modules[name].load_state_dict(sd)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the same recipe on reconstructed features (the reference's gender_classifier_train_recon.py)
+# ---------------------------------------------------------------------------------------------------
+RECON_MODEL_TYPES = ("convae", "fcae", "endtoend")
+RECON_NORMALIZERS = ("own", "checkpoint")
+
+
+def check_recon_options(settings, run_opts, environ=None):
+    """what gender_classifier_train_recon.py refuses before anything touches a GPU, one line each"""
+    environ = os.environ if environ is None else environ
+    mt = settings.get("model_type")
+    if mt not in RECON_MODEL_TYPES:
+        raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
+    if not settings.get("recon_ckpt"):
+        raise SystemExit("--recon_ckpt DIR is required: a CKPT+* directory of speechbrain_convae_train.py "
+                         "(model.ckpt, normalizer.ckpt)")
+    if settings.get("recon_normalizer", "own") not in RECON_NORMALIZERS:
+        raise SystemExit(f"unknown recon_normalizer {settings.get('recon_normalizer')!r}: own or checkpoint")
+    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("gender_classifier_train_recon runs on one GPU: data parallelism is not implemented for it")
+    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
+        raise SystemExit("gender_classifier_train_recon does not support --hip_graph")
+
+
+def build_anonymiser(model_type, precision="bf16x3", external_classifier=None, batch_size=None):
+    """the model class ``model_type`` names, as speechbrain_convae_train.py constructs it (on the CPU)"""
+    if model_type == "convae":
+        from .convae import ConvAutoencoder
+        return ConvAutoencoder(precision=precision)
+    if model_type == "endtoend":
+        from .endtoend import ConvReconstruction
+        return ConvReconstruction(external_classifier, precision=precision)
+    if model_type == "fcae":
+        from .fcae import FullyConnectedAutoencoder
+        return FullyConnectedAutoencoder(80, batch_size)
+    raise SystemExit(f"unknown model_type {model_type!r}: the anonymiser is one of convae, fcae and endtoend")
+
+
+def load_anonymiser(model, ckpt_dir):
+    """``model.ckpt`` of a CKPT+* directory of speechbrain_convae_train.py holds the state dict of the
+    recipe's torch.nn.ModuleList (keys prefixed ``0.``): into ``model``, strict.  A key mismatch (a checkpoint
+    of another model_type) exits in one line naming the first missing key.  -> model, frozen, eval mode"""
+    fn = os.path.join(ckpt_dir, "model.ckpt")
+    if not os.path.isfile(fn):
+        raise SystemExit(f"--recon_ckpt {ckpt_dir}: no model.ckpt there")
+    sd = torch.load(fn, map_location="cpu", weights_only=True)
+    sd = {k[2:]: v for k, v in sd.items() if k.startswith("0.")}
+    want = model.state_dict()
+    if isinstance(getattr(model, "sex_classifier", None), xvector.EncoderClassifier):
+        # endtoend: the frozen in-graph x-vector comes from --external_classifier_ckpt where the checkpoint
+        # does not carry it; reconstruct never runs it
+        for k, v in want.items():
+            if k.startswith("sex_classifier."):
+                sd.setdefault(k, v)
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise SystemExit(f"--recon_ckpt {ckpt_dir}: model.ckpt does not hold a {type(model).__name__}: "
+                         f"missing key {missing[0]!r} ({len(missing)} of {len(want)} keys missing; wrong --model_type?)")
+    unexpected = [k for k in sd if k not in want]
+    if unexpected:
+        raise SystemExit(f"--recon_ckpt {ckpt_dir}: model.ckpt does not hold a {type(model).__name__}: "
+                         f"unexpected key {unexpected[0]!r} (wrong --model_type?)")
+    try:
+        model.load_state_dict(sd, strict=True)
+    except RuntimeError as e:                             # same keys, other shapes
+        raise SystemExit(f"--recon_ckpt {ckpt_dir}: model.ckpt does not fit a {type(model).__name__}: "
+                         + " ".join(str(e).split())[:200])
+    for p in model.parameters():
+        p.requires_grad = False
+    return model.eval()
+
+
+def load_recon_normalizer(ckpt_dir):
+    """the anonymiser's own global InputNormalization (normalizer.ckpt of its checkpoint), frozen"""
+    fn = os.path.join(ckpt_dir, "normalizer.ckpt")
+    if not os.path.isfile(fn):
+        raise SystemExit(f"recon_normalizer checkpoint: no normalizer.ckpt in {ckpt_dir}")
+    norm = features.InputNormalization(norm_type="global", update_until_epoch=0)
+    norm.load_state_dict(torch.load(fn, map_location="cpu", weights_only=True))
+    return norm.eval()                                     # eval mode and not among Brain.modules: never updated
+
+
+class GenderReconBrain(GenderBrain):
+    """gender_classifier_train_recon.py:58-93: the x-vector classifier trained on what a frozen anonymiser
+    makes of the features.  ``modules.model`` is the anonymiser (anything with ``reconstruct``); Brain.fit puts
+    it in train mode with the other modules, as the reference's does, and reconstruct does not care.
+    hparams.recon_normalizer: "own" -- the recipe's mean_var_norm feeds the anonymiser (what the reference
+    runs); "checkpoint" -- the anonymiser's own frozen normaliser ``hparams.recon_norm`` does, while
+    mean_var_norm still follows every training batch (it is saved with the classifier) unapplied.
+    prepare_features is the recipe's only change; init_optimizers keeps the anonymiser's (frozen) parameters
+    out of the optimiser's list, and the checkpointer never had them."""
+
+    def prepare_features(self, wavs, lens, stage):
+        feats = self.modules.compute_features(wavs)
+        # no epoch is passed (reference :85): the global statistics follow every training batch
+        normed = self.modules.mean_var_norm(feats, lens)
+        if getattr(self.hparams, "recon_normalizer", "own") == "checkpoint":
+            normed = self.hparams.recon_norm(feats, lens, epoch=1)
+        return self.modules.model.reconstruct(normed)
+
+    def init_optimizers(self):
+        model = self.modules.pop("model")
+        try:
+            super().init_optimizers()
+        finally:
+            self.modules["model"] = model
