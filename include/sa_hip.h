@@ -192,6 +192,12 @@ int sa_convCto1(int dtype, const void* x, const float* w, const float* bias, flo
 int sa_wgrad1C(int dtype, const float* u, const void* v, float* slabs, int B, int L, int chunk,
                int flip, const float* s1, const float* t1, int swish, void* stream);
 int sa_wgrad1C_nchunk(int L, int chunk);
+/* decoder.8 backward in one launch and one read of v: g [B][L][32] and stats as sa_conv1toC(u, w, flip,
+ * ep_x = v, ep_s1 = s1, ...) writes them, slabs [B][sa_wgrad1C_nchunk(L, chunk)][32][15] as sa_wgrad1C(u, v,
+ * flip, s1, t1, swish = 1) writes them (same bits).  s1 / t1 / mean / rstd are required; chunk % 512 == 0 */
+int sa_bwd1C(int dtype, const float* u, const void* v, const float* w, void* g, float* stats, float* slabs,
+             int B, int L, int chunk, int flip, const float* s1, const float* t1, const float* mean,
+             const float* rstd, void* stream);
 int sa_sum_slabs(const float* slabs, float* dst, int nslab, int n, int accumulate, void* stream);
 
 /* ---- normalisation / activation backward + statistics finalisers (sa_elementwise.hip):
@@ -482,6 +488,14 @@ int sa_fbank_normalize(const float* feats, const float* tilemax, int B, int T, i
                        const float* lens, float top_db, int batch_max, int update, int epoch,
                        int update_until_epoch, float* state, float* scratch, float* out,
                        void* stream);
+/* two successive sa_fbank_normalize calls on the same features (the train step's input and target) from
+ * one read of them: out1 / out2 and the final state have the bits of the two calls.  snap: 160 floats of
+ * scratch.  out2 may be NULL when neither update moves mean / std (update == 0, or epoch >=
+ * update_until_epoch with count > 0): both results are then out1 */
+int sa_fbank_normalize_pair(const float* feats, const float* tilemax, int B, int T, int Tp,
+                            const float* lens, float top_db, int batch_max, int update, int epoch,
+                            int update_until_epoch, float* state, float* scratch, float* snap,
+                            float* out1, float* out2, void* stream);
 
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).

@@ -129,6 +129,10 @@ class Brain:
         # buckets when every gradient lives there (check_gradients / _grad_flats); same arithmetic up to the
         # order of the sum of squares
         self.fused_clip = bool(run_opts.get("fused_clip", os.environ.get("SA_FUSED_CLIP", "1") == "1"))
+        # front_end_once (default on; SA_FRONT_END_ONCE=0): a train step computes Fbank once and normalises
+        # input and target in one pass (InputNormalization.forward_pair: the bits and the state of the two
+        # features() calls of the reference's step); see SexAnonymizationTraining.features
+        self.front_end_once = bool(run_opts.get("front_end_once", os.environ.get("SA_FRONT_END_ONCE", "1") == "1"))
         self.distributed_launch = bool(run_opts.get("distributed_launch", sdist.is_distributed()))
         self.modules = torch.nn.ModuleDict(modules or {})
         # dp_batch_sizes (default "equal"): how the data-parallel ranks' batches relate.  The data
@@ -358,7 +362,17 @@ class SexAnonymizationTraining(Brain):
     switches the frozen-ASR utility loss on (SURVEY.md 8f-2: throughput-only, parity unpinned);
     without it the term is 0, whatever utility_loss_weight says."""
 
+    @staticmethod
+    def _sig_key(wavs, wav_lens):
+        """identity of a (waveform, lengths) pair: same storage, same shape, not written since"""
+        return tuple((t.data_ptr(), tuple(t.shape), t.dtype, t._version) for t in (wavs, wav_lens))
+
     def features(self, wavs, wav_lens):
+        # the target of a train step whose forward already normalised this very batch (front_end_once):
+        # handed out once, to compute_objectives' call with the same waveform and lengths storage
+        stash, self._target_stash = self.__dict__.get("_target_stash"), None
+        if stash is not None and stash[0] == self._sig_key(wavs, wav_lens):
+            return stash[1]
         feats = self.hparams.compute_features(wavs)
         current_epoch = self.hparams.epoch_counter.current
         # normalisation, top-dB clamp and the pad-to-36 (speechbrain_convae_train.py:62-63) are
@@ -366,10 +380,24 @@ class SexAnonymizationTraining(Brain):
         pad = 36 if self.hparams.model_type != "fcae" else None
         return self.modules.normalize(feats, wav_lens, epoch=current_epoch, pad_multiple=pad)
 
+    def _features_pair(self, wavs, wav_lens):
+        """inside a TRAIN fit_batch: Fbank once, input and target from one normalisation pass; the target
+        waits in _target_stash for compute_objectives' features() call"""
+        feats = self.hparams.compute_features(wavs)
+        pad = 36 if self.hparams.model_type != "fcae" else None
+        inp, target = self.modules.normalize.forward_pair(feats, wav_lens, epoch=self.hparams.epoch_counter.current,
+                                                          pad_multiple=pad)
+        self._target_stash = (self._sig_key(wavs, wav_lens), target)
+        return inp
+
     def compute_forward(self, batch, stage):
         batch = batch.to(self.device)
         wavs, wav_lens = batch.sig
-        feats = self.features(wavs, wav_lens)
+        if (stage == Stage.TRAIN and self.__dict__.get("_in_fit_batch") and self.front_end_once
+                and hasattr(self.modules.normalize, "forward_pair")):
+            feats = self._features_pair(wavs, wav_lens)
+        else:
+            feats = self.features(wavs, wav_lens)
         return self.modules.ConvAE(feats)
 
     def compute_objectives(self, predictions, batch, stage):
@@ -494,7 +522,9 @@ class SexAnonymizationTraining(Brain):
                 float(getattr(hp, "confusion_loss_weight", 0.0)), bool(upd),
                 tuple(p.requires_grad for p in params),
                 tuple(bool(st.get(p)) for p in params if not p.requires_grad),
-                tuple(tok.shape), getattr(self, "asr_brain", None) is not None)
+                tuple(tok.shape), getattr(self, "asr_brain", None) is not None,
+                # front_end_once: whether the captured normalisation writes one tensor or two
+                self.front_end_once, bool(not upd and getattr(nrm, "_count_positive", False)))
 
     def _step_core(self, batch):
         predictions = self.compute_forward(batch, Stage.TRAIN)
@@ -559,10 +589,21 @@ class SexAnonymizationTraining(Brain):
         return ent["loss"]
 
     def fit_batch(self, batch):
+        # front_end_once: compute_forward normalises input and target together while this flag is up; a
+        # target left over from an earlier step is never served
+        self._target_stash, self._in_fit_batch = None, True
+        try:
+            return self._fit_batch(batch)
+        finally:
+            self._target_stash, self._in_fit_batch = None, False
+
+    def _fit_batch(self, batch):
         self.apply_epoch_schedule()
         if (self.hip_graph and self.hparams.gradient_accumulation == 1 and sdist.capturable()
                 and self.optimizer is not None):
             return self._fit_batch_graph(batch)
+        if self.front_end_once:
+            batch = batch.to(self.device)       # once: both hooks then see the same device tensors
         predictions = self.compute_forward(batch, Stage.TRAIN)
         loss = self.compute_objectives(predictions, batch, Stage.TRAIN)
         (loss / self.hparams.gradient_accumulation).backward()

@@ -134,6 +134,9 @@ class ConvAutoencoder(nn.Module):
         # instead of sa_sum_partials + sa_fin_bias per layer
         self.batch_bias = os.environ.get("SA_BATCH_BIAS", "1") == "1"
         self.batch_wred = os.environ.get("SA_BATCH_WRED", "1") == "1"
+        # decoder.8's data gradient and weight gradient from one read of y8 (sa_bwd1C; same bits);
+        # SA_FUSED_BWD1C=0: the two launches (conv1toC + wgrad1C)
+        self.fused_bwd1c = os.environ.get("SA_FUSED_BWD1C", "1") == "1"
         # data-parallel FC head: None = every BatchNorm1d of the head exchanges its sums (any batch
         # split); "equal" = every rank holds a batch as large as this one (what data.shard_indices
         # deals); [b0, b1, ...] = the ranks' batch sizes.  With the sizes known the pooled rows are
@@ -870,11 +873,15 @@ class _ConvAEFn(torch.autograd.Function):
             g_rec = d_rec.reshape(B, Ltot).contiguous().float()
             if need["decoder.8.bias"]:
                 setg("decoder.8.bias", ops.sum_partials(g_rec.view(4 * B, Ltot // 4), 1, n=Ltot // 4).sum())
-            if need["decoder.8.weight"]:
-                G["decoder.8.weight"] = ops.wgrad1C(g_rec, y8, newg("decoder.8.weight"), flip=True,
-                                                    s1=n8[2], t1=n8[3], swish=True)
-            g, st = ops.conv1toC(g_rec, P["decoder.8.weight"], None, dt, flip=True, want_stats=True,
-                                 ep=dict(x=y8, s1=n8[2], t1=n8[3], mean=n8[0], rstd=n8[1]))     # d z8
+            if need["decoder.8.weight"] and model.fused_bwd1c:
+                g, st, G["decoder.8.weight"] = ops.bwd1C(g_rec, y8, P["decoder.8.weight"], newg("decoder.8.weight"),
+                                                         n8[2], n8[3], n8[0], n8[1])             # d z8
+            else:
+                if need["decoder.8.weight"]:
+                    G["decoder.8.weight"] = ops.wgrad1C(g_rec, y8, newg("decoder.8.weight"), flip=True,
+                                                        s1=n8[2], t1=n8[3], swish=True)
+                g, st = ops.conv1toC(g_rec, P["decoder.8.weight"], None, dt, flip=True, want_stats=True,
+                                     ep=dict(x=y8, s1=n8[2], t1=n8[3], mean=n8[0], rstd=n8[1]))  # d z8
             if model.store_bf16_probe >= 2:
                 _round_first(g)
             in_decoder[0] = True

@@ -341,3 +341,122 @@ extern "C" int sa_fbank_normalize(const float* feats, const float* tilemax, int 
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
+
+// ---- the train step's pair: features(wavs) for the model input and again for the target -------------
+// speechbrain_convae_train.py:58-63 and :82-87 normalise the same waveform twice per step; only the
+// running state differs between the two calls.  sa_fbank_normalize_pair reads the raw features once and
+// returns what two successive sa_fbank_normalize calls return (same bits, same final state).
+
+// (1 - w) * old + w * cur as sa_norm_update_kernel evaluates it: the first product rounded, the second
+// fused into the sum
+__device__ static inline float sa_running_avg(float w, float old, float cur) {
+#pragma clang fp contract(off)
+  const float t = (1.0f - w) * old;
+  return fmaf(w, cur, t);
+}
+
+// sa_norm_update_kernel's update, twice in sequence with the same batch statistics (computed once);
+// snap [mean[80], std[80]] = the statistics after the first update (what the first apply pass used)
+__global__ __launch_bounds__(640) void sa_norm_update2_kernel(const double* __restrict__ part,
+                                                              const float* __restrict__ lens, int B, int T,
+                                                              int update, int epoch, int update_until_epoch,
+                                                              float* state, float* __restrict__ snap) {
+  __shared__ float lm[8][SA_NMEL], ls[8][SA_NMEL];
+  const int f = threadIdx.x % SA_NMEL, q = threadIdx.x / SA_NMEL;
+  const float count = state[0];
+  float cm = 0.f, cs = 0.f;
+  for (int b = q; b < B; b += 8) {
+    int n = (int)rintf(lens[b] * (float)T);
+    if (n > T) n = T;
+    double s = 0.0, sq = 0.0;
+#pragma unroll
+    for (int c = 0; c < SA_UTT_CHUNKS; ++c) {
+      const double* d = part + (((size_t)b * SA_UTT_CHUNKS + c) * SA_NMEL + f) * 2;
+      s += d[0]; sq += d[1];
+    }
+    const double m = s / n;
+    double var = n > 1 ? (sq - s * m) / (n - 1) : 0.0;
+    if (var < 0.0) var = 0.0;
+    cm += (float)m;
+    cs += fmaxf((float)sqrt(var), 1e-10f);
+  }
+  lm[q][f] = cm; ls[q][f] = cs;
+  __syncthreads();
+  if (q == 0) {
+    cm = 0.f; cs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { cm += lm[r][f]; cs += ls[r][f]; }
+    cm /= B; cs /= B;
+    float gm = state[1 + f], gs = state[1 + SA_NMEL + f], cnt = count;
+#pragma unroll
+    for (int rep = 0; rep < 2; ++rep) {
+      if (update) {
+        if (cnt == 0.0f) { gm = cm; gs = cs; }
+        else if (epoch < update_until_epoch) {
+          const float w = 1.0f / (cnt + 1.0f);
+          gm = sa_running_avg(w, gm, cm);
+          gs = sa_running_avg(w, gs, cs);
+        }
+        cnt = cnt + 1.0f;
+      }
+      if (rep == 0) { snap[f] = gm; snap[SA_NMEL + f] = gs; }
+    }
+    if (update) { state[1 + f] = gm; state[1 + SA_NMEL + f] = gs; }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && update) state[0] = (count + 1.0f) + 1.0f;
+}
+
+// sa_norm_apply_kernel for two sets of statistics (st1, st2: [mean[80], std[80]]) from one read of feats
+__global__ void sa_norm_apply2_kernel(const float* __restrict__ feats, const float* __restrict__ floor_b,
+                                      const float* __restrict__ st1, const float* __restrict__ st2, int T,
+                                      int Tp, float* __restrict__ out1, float* __restrict__ out2) {
+  const int b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // float4 index in [Tp*80/4]
+  if (i >= (size_t)Tp * SA_NMEL / 4) return;
+  const size_t e = i * 4;
+  const int t = (int)(e / SA_NMEL), f = (int)(e % SA_NMEL);
+  float4 o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1;
+  if (t < T) {
+    const float4 x = *reinterpret_cast<const float4*>(feats + ((size_t)b * T) * SA_NMEL + e);
+    const float fl = floor_b[b];
+    const float c0 = fmaxf(x.x, fl), c1 = fmaxf(x.y, fl), c2 = fmaxf(x.z, fl), c3 = fmaxf(x.w, fl);
+    const float* gm = st1 + f;
+    const float* gs = st1 + SA_NMEL + f;
+    o1.x = (c0 - gm[0]) / gs[0]; o1.y = (c1 - gm[1]) / gs[1];
+    o1.z = (c2 - gm[2]) / gs[2]; o1.w = (c3 - gm[3]) / gs[3];
+    gm = st2 + f; gs = st2 + SA_NMEL + f;
+    o2.x = (c0 - gm[0]) / gs[0]; o2.y = (c1 - gm[1]) / gs[1];
+    o2.z = (c2 - gm[2]) / gs[2]; o2.w = (c3 - gm[3]) / gs[3];
+  }
+  *reinterpret_cast<float4*>(out1 + ((size_t)b * Tp) * SA_NMEL + e) = o1;
+  *reinterpret_cast<float4*>(out2 + ((size_t)b * Tp) * SA_NMEL + e) = o2;
+}
+
+// out1 / out2 [B][Tp][80]: what the first and the second of two successive sa_fbank_normalize calls write;
+// state ends where the second call leaves it.  snap: 160 floats of scratch.  out2 == NULL: the caller knows
+// that neither update moves mean / std (update == 0, or epoch >= update_until_epoch with count > 0), so
+// both results are out1 (count still advances by two when update != 0).
+extern "C" int sa_fbank_normalize_pair(const float* feats, const float* tilemax, int B, int T, int Tp,
+                                       const float* lens, float top_db, int batch_max, int update,
+                                       int epoch, int update_until_epoch, float* state, float* scratch,
+                                       float* snap, float* out1, float* out2, void* stream) {
+  if (!feats || !tilemax || !lens || !state || !scratch || !snap || !out1 || B <= 0 || T <= 0 || Tp < T)
+    return -22;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* fl = scratch;
+  double* part = reinterpret_cast<double*>(scratch + ((B + 1) & ~1));
+  hipLaunchKernelGGL(sa_fbank_utt_partial_kernel, dim3(SA_UTT_CHUNKS, B), dim3(256), 0, st, feats,
+                     tilemax, sa_div_up(T, SA_FB_FRAMES), B, T, lens, top_db, batch_max, fl, part);
+  hipLaunchKernelGGL(sa_norm_update2_kernel, dim3(1), dim3(640), 0, st, part, lens, B, T, update, epoch,
+                     update_until_epoch, state, snap);
+  const size_t n4 = (size_t)Tp * SA_NMEL / 4;
+  const dim3 grid((unsigned)((n4 + 255) / 256), B);
+  if (out2)
+    hipLaunchKernelGGL(sa_norm_apply2_kernel, grid, dim3(256), 0, st, feats, fl, snap, state + 1, T, Tp,
+                       out1, out2);
+  else
+    hipLaunchKernelGGL(sa_norm_apply_kernel, grid, dim3(256), 0, st, feats, fl, state, T, Tp, out1);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}

@@ -327,6 +327,189 @@ extern "C" int sa_wgrad1C(int dtype, const float* u, const void* v, float* slabs
   return e == hipSuccess ? 0 : -(int)e;
 }
 
+// decoder.8 backward in one launch: sa_conv1toC's flipped data gradient with the [InstanceNorm -> swish]
+// backward epilogue AND sa_wgrad1C's weight-gradient slabs, from one read of v (= y8) and one staged u row.
+//   g[b][l][c]  = (sum_k u[b][l+k-7] * w[c][flip ? 14-k : k]) * swish'(z),   z = v*s1[b][c] + t1[b][c]
+//   stats       = (sum g, sum g*(v - mean[b][c])*rstd[b][c]) per 512-position tile, [b][tile][c][2]
+//   slabs       = sum_l u[b][l+kk-7] * swish(z[b][l][c]),  [b][chunk][c][k]
+// The walk is sa_wgrad1C_kernel's (workgroup = chunk x utterance, 256-position tiles, the next tile's rows
+// in registers).  Both kernels map threads to (row, channel chunk) alike, so the thread that staged a row
+// forms its data gradient from the registers it staged it from; its (sum, sum*xhat) run over two
+// consecutive tiles = one statistics tile of sa_conv1toC_kernel and are reduced through red[] in that
+// kernel's order.  Every output has the thread, row and summation order of the two launches it replaces:
+// same bits.  chunk % 512 == 0 keeps a statistics tile inside one workgroup.
+template <typename T>
+__global__ __launch_bounds__(256, Tr<T>::VEC == 4 ? 3 : 2) void sa_bwd1C_kernel(const float* __restrict__ u,
+                                                       const T* __restrict__ v,
+                                                       const float* __restrict__ w,
+                                                       T* __restrict__ gout, float* __restrict__ stats,
+                                                       int ntiles, float* __restrict__ slabs, int L,
+                                                       int chunk, int flip,
+                                                       const float* __restrict__ s1,
+                                                       const float* __restrict__ t1,
+                                                       const float* __restrict__ mean,
+                                                       const float* __restrict__ rstd) {
+  constexpr int VEC = Tr<T>::VEC, CH = SA_C32 / VEC, RPP = 256 / CH, TILE = 256, PITCH = 33;
+  __shared__ float us[TILE + SA_K15 - 1 + 1];
+  __shared__ float vs[TILE * PITCH];
+  __shared__ __attribute__((aligned(16))) float ws[SA_K15][SA_C32];
+  __shared__ float red[RPP][SA_C32][2];
+  __shared__ __attribute__((aligned(16))) float pv[4][SA_C32];      // s1, t1, mean, rstd of this utterance
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+  const int lbeg = blockIdx.x * chunk;
+  int lend = lbeg + chunk; if (lend > L) lend = L;
+  const int c = tid % CH, r0 = tid / CH;
+  float ssum[VEC], ssq[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { ssum[j] = 0.f; ssq[j] = 0.f; }
+  if (tid < 4 * SA_C32) {
+    const float* src = tid < 32 ? s1 : tid < 64 ? t1 : tid < 96 ? mean : rstd;
+    pv[tid >> 5][tid & 31] = src[(size_t)b * SA_C32 + (tid & 31)];
+  }
+  for (int i = tid; i < SA_K15 * SA_C32; i += 256) {
+    const int k = i / SA_C32, cc = i % SA_C32;
+    ws[k][cc] = w[cc * SA_K15 + (flip ? SA_K15 - 1 - k : k)];
+  }
+  const int m = lane & 15, j4 = lane >> 4;                 // MFMA row (tap) / k-slot of this lane
+  const bool mval = m < SA_K15;
+  const int kk = mval ? (flip ? SA_K15 - 1 - m : m) : 0;
+  const int qa = wave * 64 + 16 * j4;                      // first position of this lane's k-slot
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  constexpr int NIT = TILE / RPP, NU = (TILE + SA_K15 - 1 + 255) / 256;
+  uint4 raw[NIT];
+  float rawu[NU];
+  auto issue_v = [&](int l0, int i) {
+    const int g = l0 + r0 + i * RPP;
+    raw[i] = make_uint4(0, 0, 0, 0);
+    if (g < lend) raw[i] = *reinterpret_cast<const uint4*>(v + ((size_t)b * L + g) * SA_C32 + c * VEC);
+  };
+  auto issue_u = [&](int l0) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int g = l0 + tid + i * 256 - 7;
+      rawu[i] = (l0 < lend && tid + i * 256 < TILE + SA_K15 - 1 && g >= 0 && g < L) ? u[(size_t)b * L + g] : 0.0f;
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) issue_v(lbeg, i);
+  issue_u(lbeg);
+  __syncthreads();                                         // pv (ws is first read behind the loop's barrier)
+  for (int l0 = lbeg; l0 < lend; l0 += TILE) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i)
+      if (tid + i * 256 < TILE + SA_K15 - 1) us[tid + i * 256] = rawu[i];
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int r = r0 + i * RPP, g = l0 + r;
+      float f[VEC];
+      Tr<T>::unpack(raw[i], f);
+      if (g < lend) {
+        // the per-channel vectors are re-read from LDS where they are used (an offset the compiler cannot
+        // see through keeps it from hoisting 16 registers' worth out of the tile loop: 3 waves per SIMD)
+        int z0 = c * VEC; asm volatile("" : "+v"(z0));
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[j] = sa_swish(fmaf(f[j], pv[0][z0 + j], pv[1][z0 + j]));
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) vs[r * PITCH + c * VEC + j] = f[j];
+    }
+    __syncthreads();
+    issue_u(l0 + TILE);
+    // data gradient of the rows this thread staged (sa_conv1toC_kernel's row body); a row's register is
+    // refilled with the next tile's row as soon as it has been unpacked
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int r = r0 + i * RPP, g = l0 + r;
+      float xv[VEC];
+      Tr<T>::unpack(raw[i], xv);
+      issue_v(l0 + TILE, i);
+      if (g < lend) {
+#pragma clang fp contract(off)           // as sa_conv1toC_kernel compiles: the stored product is rounded before it is summed
+        float acc[VEC], xn[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[j] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < SA_K15; ++k) {
+          const float uv = us[r + k];
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(uv, ws[k][c * VEC + j], acc[j]);
+        }
+        int z0 = c * VEC; asm volatile("" : "+v"(z0));
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          acc[j] *= sa_swish_grad(fmaf(xv[j], pv[0][z0 + j], pv[1][z0 + j]));
+          xn[j] = (xv[j] - pv[2][z0 + j]) * pv[3][z0 + j];
+        }
+        const uint4 o = Tr<T>::pack(acc);
+        *reinterpret_cast<uint4*>(gout + ((size_t)b * L + g) * SA_C32 + c * VEC) = o;
+        float f[VEC];
+        Tr<T>::unpack(o, f);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { ssum[j] += f[j]; ssq[j] = fmaf(f[j], xn[j], ssq[j]); }
+      }
+    }
+    // second half of a statistics tile, or the last tile of the chunk (workgroup-uniform)
+    const bool flush = (((l0 - lbeg) / TILE) & 1) || l0 + TILE >= lend;
+    if (flush) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        red[r0][c * VEC + j][0] = ssum[j]; red[r0][c * VEC + j][1] = ssq[j];
+        ssum[j] = 0.f; ssq[j] = 0.f;
+      }
+    }
+#pragma unroll 4
+    for (int t = 0; t < 16; ++t) {
+      const int q = qa + t;
+      const float av = mval ? us[q + kk] : 0.0f;
+      const float b0 = vs[q * PITCH + m], b1 = vs[q * PITCH + 16 + m];
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, acc1, 0, 0, 0);
+    }
+    __syncthreads();
+    if (flush && tid < SA_C32) {
+      float s = 0.f, q = 0.f;
+      for (int r = 0; r < RPP; ++r) { s += red[r][tid][0]; q += red[r][tid][1]; }
+      float* d = stats + (((size_t)b * ntiles + l0 / 512) * SA_C32 + tid) * 2;
+      d[0] = s; d[1] = q;
+    }
+  }
+  float* part = vs;                                        // [4][16][32], as in sa_wgrad1C_kernel
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    part[(wave * 16 + 4 * j4 + i) * 32 + m] = acc0[i];
+    part[(wave * 16 + 4 * j4 + i) * 32 + 16 + m] = acc1[i];
+  }
+  __syncthreads();
+  for (int o = tid; o < SA_K15 * SA_C32; o += 256) {
+    const int k = o / SA_C32, cc = o % SA_C32;
+    const float sum = ((part[(0 * 16 + k) * 32 + cc] + part[(1 * 16 + k) * 32 + cc]) +
+                       part[(2 * 16 + k) * 32 + cc]) + part[(3 * 16 + k) * 32 + cc];
+    slabs[((size_t)b * gridDim.x + blockIdx.x) * (SA_C32 * SA_K15) + cc * SA_K15 + k] = sum;
+  }
+}
+
+// g: [B][L][32] (dtype), stats: [B][sa_conv1toC_ntiles(L)][32][2], slabs: [B][sa_wgrad1C_nchunk(L, chunk)][32][15]
+// (sa_sum_slabs adds them).  The prologue vectors are required; chunk is a multiple of 512.
+extern "C" int sa_bwd1C(int dtype, const float* u, const void* v, const float* w, void* g, float* stats,
+                        float* slabs, int B, int L, int chunk, int flip, const float* s1,
+                        const float* t1, const float* mean, const float* rstd, void* stream) {
+  if (!u || !v || !w || !g || !stats || !slabs || B <= 0 || L <= 0 || chunk <= 0 || chunk % 512) return -22;
+  if (!s1 || !t1 || !mean || !rstd) return -22;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nt = sa_div_up(L, 512);
+  dim3 grid(sa_div_up(L, chunk), B);
+  if (dtype == SA_BF16)
+    hipLaunchKernelGGL(sa_bwd1C_kernel<bf16_t>, grid, dim3(256), 0, st, u,
+                       reinterpret_cast<const bf16_t*>(v), w, reinterpret_cast<bf16_t*>(g), stats, nt,
+                       slabs, L, chunk, flip, s1, t1, mean, rstd);
+  else
+    hipLaunchKernelGGL(sa_bwd1C_kernel<float>, grid, dim3(256), 0, st, u,
+                       reinterpret_cast<const float*>(v), w, reinterpret_cast<float*>(g), stats, nt,
+                       slabs, L, chunk, flip, s1, t1, mean, rstd);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
 // dst[i] (=|+=) sum_k slabs[k][i]   (fixed order, double accumulate; 16 outputs x 16 slab lanes)
 __global__ __launch_bounds__(256) void sa_sum_slabs_kernel(const float* __restrict__ slabs,
                                                            float* __restrict__ dst, int nslab, int n,

@@ -21,6 +21,7 @@ The reference constructs the classifier from absolute paths on its authors' mach
 (``ConvReconstruction(sex_classifier=...)``) or built with random weights.
 """
 import functools
+import os
 
 import torch
 import torch.nn as nn
@@ -39,6 +40,8 @@ class ConvReconstruction(nn.Module):
             raise SaHipError("ConvReconstruction runs in precision bf16x3 or f32")
         self.precision = precision
         self.act_dtype, self.kcode = ops.PRECISIONS[precision]
+        # encoder.12's data gradient and weight gradient in one launch (ConvAutoencoder.fused_bwd1c)
+        self.fused_bwd1c = os.environ.get("SA_FUSED_BWD1C", "1") == "1"
         self.encoder = nn.Sequential(
             nn.Conv1d(1, 32, 15, 1, 7), nn.InstanceNorm1d(32, affine=True), GLU(),
             nn.Conv1d(32, 64, 5, 2, 2), nn.InstanceNorm1d(64, affine=True), GLU(),
@@ -168,11 +171,15 @@ class _ConvRecFn(torch.autograd.Function):
         g_rec = d_recon.reshape(B, Ltot).contiguous().float()
         if need["encoder.12.bias"]:
             G["encoder.12.bias"] = ops.sum_partials(g_rec.view(4 * B, Ltot // 4), 1, n=Ltot // 4).sum().float().reshape(1)
-        if need["encoder.12.weight"]:
-            G["encoder.12.weight"] = ops.wgrad1C(g_rec, y3, newg("encoder.12.weight"), flip=True,
-                                                 s1=n3[2], t1=n3[3], swish=True)
-        g, st = ops.conv1toC(g_rec, P["encoder.12.weight"], None, dt, flip=True, want_stats=True,
-                             ep=dict(x=y3, s1=n3[2], t1=n3[3], mean=n3[0], rstd=n3[1]))          # d z3
+        if need["encoder.12.weight"] and model.fused_bwd1c:
+            g, st, G["encoder.12.weight"] = ops.bwd1C(g_rec, y3, P["encoder.12.weight"], newg("encoder.12.weight"),
+                                                      n3[2], n3[3], n3[0], n3[1])                 # d z3
+        else:
+            if need["encoder.12.weight"]:
+                G["encoder.12.weight"] = ops.wgrad1C(g_rec, y3, newg("encoder.12.weight"), flip=True,
+                                                     s1=n3[2], t1=n3[3], swish=True)
+            g, st = ops.conv1toC(g_rec, P["encoder.12.weight"], None, dt, flip=True, want_stats=True,
+                                 ep=dict(x=y3, s1=n3[2], t1=n3[3], mean=n3[0], rstd=n3[1]))      # d z3
         g = norm_bwd(g, st, y3, n3, 32, Ltot, "encoder.10", "encoder.9.bias")                    # d y3
         if need["encoder.9.weight"]:
             G["encoder.9.weight"] = wg(y2, g, 64, 32, 1, 2, CONVT_WG_TAPS, L2, newg("encoder.9.weight"),

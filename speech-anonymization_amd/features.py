@@ -140,6 +140,9 @@ class InputNormalization(torch.nn.Module):
         self.pad_multiple = pad_multiple
         # [count, glob_mean[80], glob_std[80]]
         self.register_buffer("state", torch.zeros(161), persistent=False)
+        # host knowledge that state[0] (count) > 0, without reading the device: set by a training pass
+        # and by load_state_dict (forward_pair)
+        self._count_positive = False
 
     @property
     def count(self):
@@ -153,11 +156,8 @@ class InputNormalization(torch.nn.Module):
     def glob_std(self):
         return self.state[81:161]
 
-    @torch.no_grad()
-    def forward(self, feats, lengths, epoch=0, pad_multiple=None):
-        """feats: FbankFeatures (fused clamp) or a plain [B,T,80] tensor.  Returns the normalised
-        features; with pad_multiple=m, T is zero-padded up to a multiple of m in the same pass
-        (speechbrain_convae_train.py:62-63)."""
+    def _prepare(self, feats, lengths, pad_multiple):
+        """-> (raw, tilemax, top_db, batch_max, B, T, Tp, lens, scratch) of one normalisation pass"""
         lib = L.load()
         if isinstance(feats, FbankFeatures):
             raw, tmax, top_db, bmax = feats.raw, feats.tilemax, feats.top_db, feats.batch_max
@@ -172,13 +172,48 @@ class InputNormalization(torch.nn.Module):
         m = pad_multiple if pad_multiple is not None else self.pad_multiple
         Tp = T if not m or T % m == 0 else T + (m - T % m)
         lens = lengths.to(device=raw.device, dtype=torch.float32).contiguous()
-        out = torch.empty(B, Tp, 80, dtype=torch.float32, device=raw.device)
         scratch = torch.empty(lib.sa_fbank_scratch_bytes(B) // 4, dtype=torch.float32, device=raw.device)
+        return raw, tmax, top_db, bmax, B, T, Tp, lens, scratch
+
+    @torch.no_grad()
+    def forward(self, feats, lengths, epoch=0, pad_multiple=None):
+        """feats: FbankFeatures (fused clamp) or a plain [B,T,80] tensor.  Returns the normalised
+        features; with pad_multiple=m, T is zero-padded up to a multiple of m in the same pass
+        (speechbrain_convae_train.py:62-63)."""
+        lib = L.load()
+        raw, tmax, top_db, bmax, B, T, Tp, lens, scratch = self._prepare(feats, lengths, pad_multiple)
+        out = torch.empty(B, Tp, 80, dtype=torch.float32, device=raw.device)
         L.check(lib.sa_fbank_normalize(L.ptr(raw), L.ptr(tmax), B, T, Tp, L.ptr(lens),
                                        C.c_float(top_db), int(bmax), int(self.training), int(epoch),
                                        int(self.update_until_epoch), L.ptr(self.state),
                                        L.ptr(scratch), L.ptr(out), L.stream()), "sa_fbank_normalize")
+        if self.training:
+            self._count_positive = True
         return out
+
+    @torch.no_grad()
+    def forward_pair(self, feats, lengths, epoch=0, pad_multiple=None):
+        """(out1, out2) = what two successive ``forward`` calls with these arguments return (the train
+        step's model input and its target, speechbrain_convae_train.py:58-63,82-87), and the state
+        they leave, from one read of the features (sa_fbank_normalize_pair; same bits).  Where
+        neither call moves mean / std -- eval mode, or epoch >= update_until_epoch once the host
+        knows count > 0 (an update has run, or a state with count > 0 was loaded) -- one tensor is
+        written and returned for BOTH outputs: out1 is out2."""
+        lib = L.load()
+        raw, tmax, top_db, bmax, B, T, Tp, lens, scratch = self._prepare(feats, lengths, pad_multiple)
+        same = (not self.training) or (int(epoch) >= int(self.update_until_epoch) and self._count_positive)
+        out1 = torch.empty(B, Tp, 80, dtype=torch.float32, device=raw.device)
+        out2 = out1 if same else torch.empty_like(out1)
+        snap = torch.empty(160, dtype=torch.float32, device=raw.device)
+        L.check(lib.sa_fbank_normalize_pair(L.ptr(raw), L.ptr(tmax), B, T, Tp, L.ptr(lens),
+                                            C.c_float(top_db), int(bmax), int(self.training), int(epoch),
+                                            int(self.update_until_epoch), L.ptr(self.state),
+                                            L.ptr(scratch), L.ptr(snap), L.ptr(out1),
+                                            None if same else L.ptr(out2), L.stream()),
+                "sa_fbank_normalize_pair")
+        if self.training:
+            self._count_positive = True
+        return out1, out2
 
     def state_dict(self, *a, **k):
         return {"count": self.count, "glob_mean": self.glob_mean.clone(),
@@ -188,5 +223,6 @@ class InputNormalization(torch.nn.Module):
     def load_state_dict(self, sd, strict=True):
         with torch.no_grad():
             self.state[0] = float(sd["count"])
+            self._count_positive = float(sd["count"]) > 0
             self.state[1:81] = sd["glob_mean"].to(self.state.device).float()
             self.state[81:161] = sd["glob_std"].to(self.state.device).float()

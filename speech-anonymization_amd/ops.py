@@ -356,6 +356,23 @@ def wgrad1C(u, v, dst, flip=False, s1=None, t1=None, swish=False, accumulate=Fal
     return dst
 
 
+def bwd1C(u, v, w, dst, s1, t1, mean, rstd, flip=True, accumulate=False, chunk=2048):
+    """backward of the 32 -> 1 layer in one launch and one read of v: (g, stats, dst) with the bits of
+    conv1toC(u, w, None, v.dtype, flip, want_stats=True, ep=dict(x=v, s1=, t1=, mean=, rstd=)) and of
+    wgrad1C(u, v, dst, flip, s1, t1, swish=True, accumulate=, chunk=)"""
+    lib = L.load()
+    B, Ln = u.shape
+    nch = lib.sa_wgrad1C_nchunk(Ln, chunk)
+    g = torch.empty(B, Ln, 32, dtype=v.dtype, device=u.device)
+    stats = torch.empty(B, lib.sa_conv1toC_ntiles(Ln), 32, 2, dtype=torch.float32, device=u.device)
+    slabs = torch.empty(B * nch, 32 * 15, dtype=torch.float32, device=u.device)
+    L.check(lib.sa_bwd1C(L.dt_code(v.dtype), _f(u), _f(v), _f(w), _f(g), _f(stats), _f(slabs), B, Ln, chunk,
+                         int(flip), _f(s1), _f(t1), _f(mean), _f(rstd), L.stream()), "sa_bwd1C")
+    L.check(lib.sa_sum_slabs(_f(slabs), _f(dst), B * nch, 32 * 15, int(accumulate), L.stream()),
+            "sa_sum_slabs")
+    return g, stats, dst
+
+
 def sum_partials(part, nbatch, n=None, rows=False):
     """part [nbatch][nslab][n] (contiguous) -> [nbatch, n] fixed-order sums.  n defaults to the
     product of the last two dims (the [.., C, 2] layout of the statistics slabs).  rows=True (with
