@@ -24,8 +24,7 @@ def main(argv):
     with open(hparams_file) as fin:
         settings = load_hyperpyyaml(fin, overrides)
     os.makedirs(settings["output_folder"], exist_ok=True)
-    print("gender_classifier_train: waveform augmentation (EnvCorrupt, TimeDomainSpecAugment) is not part of "
-          "this build; training without it")
+    print(gender.augment_notice("gender_classifier_train", settings))
     hparams = dict(settings, **gender.build(settings))
     run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
     brain = gender.GenderBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,

@@ -29,8 +29,7 @@ def main(argv):
         settings = load_hyperpyyaml(fin, overrides)
     gender.check_recon_options(settings, run_opts)
     os.makedirs(settings["output_folder"], exist_ok=True)
-    print("gender_classifier_train_recon: waveform augmentation (EnvCorrupt, TimeDomainSpecAugment) is not part of "
-          "this build; training without it")
+    print(gender.augment_notice("gender_classifier_train_recon", settings))
     ext = None
     if settings["model_type"] == "endtoend" and settings.get("external_classifier_ckpt"):
         ext = gender.load_external_classifier(settings["external_classifier_ckpt"])

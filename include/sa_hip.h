@@ -497,6 +497,29 @@ int sa_fbank_normalize_pair(const float* feats, const float* tilemax, int B, int
                             int update_until_epoch, float* state, float* scratch, float* snap,
                             float* out1, float* out2, void* stream);
 
+/* ---- waveform augmentation of the gender-classifier recipes (sa_augment.hip): additive noise
+ * rows, speed perturbation, frequency drop and chunk drop of speechbrain's env_corrupt / TimeDomainSpecAugment,
+ * restated.  wav, noise [B][L] fp32; every random draw but the noise is made by the host (augment.draw_plan).
+ *   sa_wav_abs_sums: sums [2][B] fp64 = per-row sum |x| of wav, then of noise (noise NULL: the first B only);
+ *     fp64 partials added in a fixed order, no atomics.
+ *   sa_noise_scales: scales [B][2] = (1 - f, f amp_c / (amp_n + 1e-14)), amp = sum / (lens L),
+ *     f = 1 / (10^(snr / 20) + 1); lens, snr [B] fp32 on the device; fp64 arithmetic, rounded once.
+ *   sa_wav_augment: out [R][Lp], R = B (rows as they are) or 2 B (row B + b = scales[b][0] wav[b] + scales[b][1]
+ *     noise[b], formed at staging) -> resampled by the S_out x W table (output q S_out + i = sum_j w[i][j]
+ *     x[q S_in + first[i] + j], zeros outside [0, L)) -> 101-tap filter y[n] = sum_j h[j] r[n + j - 50], zeros
+ *     outside [0, Lp) -> the row's intervals zeroed.  ONE launch, grid (tiles of sa_wav_augment_tile() samples, R).
+ *     plan: 32-bit words in device memory: first [S_out] int, w [S_out][W] float, h [101] float, chunks
+ *     [R][1 + 2 sa_wav_augment_max_chunks()] int (count, then start, end pairs; end exclusive).  first_min /
+ *     first_max: the extremes of first[].  -EINVAL: R not B or 2 B, R > 65535, S_out > 128, W > 32, S_out W > 2048,
+ *     a ratio S_in / S_out whose tile span exceeds the staging buffer (speeds under ~72 %). */
+int sa_wav_augment_tile(void);
+int sa_wav_augment_max_chunks(void);
+int sa_wav_abs_sums(const float* wav, const float* noise, int B, int L, double* sums, void* stream);
+int sa_noise_scales(const double* sums, const float* lens, const float* snr, int B, int L, float* scales,
+                    void* stream);
+int sa_wav_augment(const float* wav, const float* noise, const float* scales, const void* plan, int B, int L, int R,
+                   int Lp, int S_in, int S_out, int W, int first_min, int first_max, float* out, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

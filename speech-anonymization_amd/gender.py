@@ -13,8 +13,9 @@ Labels are data.SEX (M = 0, F = 1), the indices the ConvAE recipe compares ACC_e
 The reference's CategoricalEncoder numbers the classes in order of first appearance instead, which
 can swap them; the mapping used is written next to the weights (label_encoder.txt).
 
-Waveform augmentation (EnvCorrupt: an OpenRIR download; TimeDomainSpecAugment) is out of scope:
-the recipe trains without it.
+Waveform augmentation is opt-in (``augment: true``; augment.TrainAugment): white additive
+noise rows in place of EnvCorrupt's OpenRIR noise, and TimeDomainSpecAugment, at Stage.TRAIN only.  Off -- the
+default -- the recipe trains without it.
 
 The second half of the module is the same recipe on RECONSTRUCTED features (the reference's
 gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser)."""
@@ -110,9 +111,15 @@ def build(hp):
     norm = features.InputNormalization(norm_type="global")
     counter = EpochCounter(hp["number_of_epochs"])
     out = hp["output_folder"]
+    modules = {"compute_features": features.Fbank(fb["sample_rate"], fb["n_fft"], fb["n_mels"]),
+               "mean_var_norm": norm, "embedding_model": emb, "classifier": cl}
+    if hp.get("augment"):
+        from . import augment
+        cfg = augment.settings(hp.get("augment_options"), sample_rate=fb["sample_rate"])
+        augment.check_settings(cfg, hp["batch_size"])
+        modules["augmentation"] = augment.TrainAugment(seed=int(hp["seed"]), **vars(cfg))
     return {
-        "modules": {"compute_features": features.Fbank(fb["sample_rate"], fb["n_fft"], fb["n_mels"]),
-                    "mean_var_norm": norm, "embedding_model": emb, "classifier": cl},
+        "modules": modules,
         "epoch_counter": counter,
         "compute_cost": losses.NLLLoss(),
         "opt_class": functools.partial(torch.optim.Adam, lr=float(hp["adam_lr"])),
@@ -128,19 +135,35 @@ class GenderBrain(Brain):
     """gender_classifier_train.py:58-216 on the Brain base (fused Adam, clipping at max_grad_norm,
     the lazy finite check, checkpoint resume)."""
 
+    def augment(self, wavs, lens, stage):
+        """modules.augmentation (reference :79-86) at Stage.TRAIN: -> the augmented waveforms and their lengths.
+        ``_aug`` keeps (lengths, repeat) of the batch in flight for compute_forward and compute_objectives."""
+        self._aug = None
+        if stage == Stage.TRAIN and "augmentation" in self.modules:
+            wavs, lens, repeat = self.modules["augmentation"](wavs, lens, host_lens=self.__dict__.get("_host_lens"))
+            self._aug = (lens, repeat)
+        return wavs, lens
+
     def prepare_features(self, wavs, lens, stage):
+        wavs, lens = self.augment(wavs, lens, stage)
         feats = self.modules.compute_features(wavs)
         # no epoch is passed (reference :104): the global statistics follow every training batch
         return self.modules.mean_var_norm(feats, lens)
 
     def compute_forward(self, batch, stage):
+        # the loader's CPU lengths: the augmentation draws its chunk positions from them without a device read
+        self._host_lens = None if batch.sig[1].is_cuda else batch.sig[1]
         batch = batch.to(self.device)
         wavs, lens = batch.sig
         feats = self.prepare_features(wavs, lens, stage)
+        if self.__dict__.get("_aug"):
+            lens = self._aug[0]
         return xvector.train_log_probs(self.modules.embedding_model, self.modules.classifier, feats, lens)
 
     def compute_objectives(self, predictions, batch, stage):
         label = batch.gender.to(self.device)
+        if stage == Stage.TRAIN and self.__dict__.get("_aug") and self._aug[1] > 1:
+            label = label.repeat(self._aug[1])              # clean rows, then their noisy copies
         logp = predictions.squeeze(1)
         loss = self.hparams.compute_cost(logp, label)
         if stage != Stage.TRAIN:
@@ -150,6 +173,8 @@ class GenderBrain(Brain):
 
     def on_stage_start(self, stage, epoch=None):
         self.n_err, self.n_utt = 0, 0
+        if stage == Stage.TRAIN and "augmentation" in self.modules:
+            self.modules["augmentation"].reseed(epoch)       # (seed, epoch): the same draws after a resume
 
     def on_stage_end(self, stage, stage_loss, epoch=None):
         if stage == Stage.TRAIN:
@@ -182,6 +207,20 @@ class GenderBrain(Brain):
             fn = os.path.join(ckpts[0], ("normalizer" if name == "mean_var_norm" else name) + ".ckpt")
             sd = torch.load(fn, map_location="cpu", weights_only=True)
             self.modules[name].load_state_dict(sd)
+
+
+def augment_notice(script, settings):
+    """the one line either script prints about waveform augmentation"""
+    if not settings.get("augment"):
+        return (f"{script}: waveform augmentation (EnvCorrupt, TimeDomainSpecAugment) is not part of "
+                "this build; training without it")
+    from . import augment
+    c = augment.settings(settings.get("augment_options"))
+    noise = (f"additive white noise at {c.snr_low:g}-{c.snr_high:g} dB SNR doubling the batch (OpenRIR noise and "
+             "reverberation are not built)") if c.noise else "no noise rows"
+    return (f"{script}: waveform augmentation on: speeds {list(c.speeds)}, frequency drop "
+            f"{c.drop_freq_count_low}-{c.drop_freq_count_high} notches, chunk drop {c.drop_chunk_count_low}-"
+            f"{c.drop_chunk_count_high} x {c.drop_chunk_length_low}-{c.drop_chunk_length_high} samples, {noise}")
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -277,6 +316,7 @@ class GenderReconBrain(GenderBrain):
     out of the optimiser's list, and the checkpointer never had them."""
 
     def prepare_features(self, wavs, lens, stage):
+        wavs, lens = self.augment(wavs, lens, stage)
         feats = self.modules.compute_features(wavs)
         # no epoch is passed (reference :85): the global statistics follow every training batch
         normed = self.modules.mean_var_norm(feats, lens)

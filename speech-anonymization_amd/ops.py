@@ -808,3 +808,64 @@ def clip_flats(flats, max_norm, eps=1e-6):
     L.check(L.load().sa_clip_grads(C.byref(f), C.c_float(max_norm), C.c_float(eps), _f(partials), _f(total), L.stream()),
             "sa_clip_grads")
     return total
+
+
+# ---- waveform augmentation (csrc/sa_augment.hip; augment.py) ----
+def _aug_in(t, what, dtype=torch.float32, shape=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.SaHipError(f"{what}: the augmentation kernels take GPU tensors (no CPU fallback)")
+    if t.dtype != dtype:
+        raise L.SaHipError(f"{what}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise L.SaHipError(f"{what}: expected a contiguous tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.SaHipError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def wav_abs_sums(wav, noise=None):
+    """per-row sum |x| of wav [B, L] and, if given, of noise [B, L]: fp64 [2, B] (row 1 unwritten without noise)"""
+    if _aug_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, L] with B, L >= 1, got {tuple(wav.shape)}")
+    B, Lw = wav.shape
+    if noise is not None:
+        _aug_in(noise, "noise", shape=(B, Lw))
+    sums = torch.empty(2, B, dtype=torch.float64, device=wav.device)
+    L.check(L.load().sa_wav_abs_sums(_f(wav), _f(noise), B, Lw, _f(sums), L.stream()), "sa_wav_abs_sums")
+    return sums
+
+
+def noise_scales(sums, lens, snr, Lw):
+    """scales [B, 2] = (1 - f, f amp_clean / (amp_noise + 1e-14)) from wav_abs_sums' sums, the relative lengths
+    and the SNRs in dB (both fp32 [B] on the device); fp64 on the device, rounded once"""
+    B = _aug_in(lens, "lens").numel()
+    _aug_in(sums, "sums", torch.float64, (2, B))
+    _aug_in(snr, "snr", shape=(B,))
+    scales = torch.empty(B, 2, dtype=torch.float32, device=sums.device)
+    L.check(L.load().sa_noise_scales(_f(sums), _f(lens), _f(snr), B, int(Lw), _f(scales), L.stream()),
+            "sa_noise_scales")
+    return scales
+
+
+def wav_augment(wav, noise, scales, plan_words, R, Lp, S_in, S_out, W, first_min, first_max):
+    """the fused pass (one launch): wav [B, L] -> [R, Lp]; R = 2 B takes noise [B, L] and scales [B, 2].
+    plan_words: the device copy of augment.Plan.words()."""
+    if _aug_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, L] with B, L >= 1, got {tuple(wav.shape)}")
+    B, Lw = wav.shape
+    if R not in (B, 2 * B):
+        raise L.SaHipError(f"R = {R}: the output has B = {B} rows, or 2 B with noise rows")
+    if R == 2 * B:
+        _aug_in(noise, "noise", shape=(B, Lw))
+        _aug_in(scales, "scales", shape=(B, 2))
+    else:
+        noise = scales = None
+    from . import augment
+    need = S_out + S_out * W + 101 + R * (1 + 2 * augment.max_chunks())
+    if _aug_in(plan_words, "plan", torch.int32).numel() < need:
+        raise L.SaHipError(f"plan: {plan_words.numel()} words, the geometry needs {need}")
+    out = torch.empty(R, Lp, dtype=torch.float32, device=wav.device)
+    L.check(L.load().sa_wav_augment(_f(wav), _f(noise), _f(scales), _f(plan_words), B, Lw, R, int(Lp), int(S_in),
+                                    int(S_out), int(W), int(first_min), int(first_max), _f(out), L.stream()),
+            "sa_wav_augment")
+    return out
