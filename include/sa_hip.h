@@ -520,6 +520,23 @@ int sa_noise_scales(const double* sums, const float* lens, const float* snr, int
 int sa_wav_augment(const float* wav, const float* noise, const float* scales, const void* plan, int B, int L, int R,
                    int Lp, int S_in, int S_out, int W, int first_min, int first_max, float* out, void* stream);
 
+/* ---- SpecAugment of the ConvAE train step's input features (sa_specaug.hip): bicubic time warp,
+ * frequency masks and time masks of speechbrain's lobes.augment.SpecAugment, restated.  x, out [B][T][F] fp32, 16-byte
+ * aligned, x != out; every random draw is made by the host (specaug.draw_plan).
+ *   plan: 32-bit words in device memory: header [8] (flags: bit 0 = fill with zero; B; T; F; 0 ...), rows [T][8]
+ *     (base, lo, hi, 0 as int, then four float weights: out row o = sum_k w[k] x[clamp(base - 1 + k, lo, hi)]),
+ *     freq [B][8][2] and time [B][8][2] (pos, len; len 0 = unused), n_fm [B] (frequency-masked cells per utterance).
+ *   sa_specaug_warp_sums: out = the warped rows; part [ceil(T / 32) * B][2] fp64 = per workgroup the sum of its
+ *     values and of those in frequency-masked columns.  Grid (tiles of 32 frames, B); no atomics.
+ *   sa_specaug_finalize: vals [2] = (val_f, val_t): val_f = S / N, val_t = (S - S_fm + n_fm val_f) / N, N = B T F,
+ *     fp64 sums in a fixed order, each rounded once to fp32; both 0 with the zero flag.
+ *   sa_specaug_fill: out's time-masked rows = val_t, elsewhere its frequency-masked columns = val_f.
+ *   -EINVAL: B < 1 or > 65535, T < 1, F no multiple of 4 or > 128, a NULL or misaligned pointer, x == out. */
+int sa_specaug_warp_sums(const float* x, const void* plan, int B, int T, int F, float* out, double* part,
+                         void* stream);
+int sa_specaug_finalize(const double* part, const void* plan, int B, int T, int F, float* vals, void* stream);
+int sa_specaug_fill(const void* plan, const float* vals, int B, int T, int F, float* out, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

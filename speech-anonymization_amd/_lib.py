@@ -129,6 +129,7 @@ SYMBOLS = [
     "sa_fc_mid_fwd", "sa_fc_head_fwd", "sa_fc_head_bwd", "sa_fc_mid_bwd", "sa_fc_bn_bwd_fin", "sa_fc_enc_bwd",
     "sa_fc_wreduce", "sa_fc_recon_fwd",
     "sa_wav_augment_tile", "sa_wav_augment_max_chunks", "sa_wav_abs_sums", "sa_noise_scales", "sa_wav_augment",
+    "sa_specaug_warp_sums", "sa_specaug_finalize", "sa_specaug_fill",
 ]
 
 _lib = None

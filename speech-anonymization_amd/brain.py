@@ -398,7 +398,21 @@ class SexAnonymizationTraining(Brain):
             feats = self._features_pair(wavs, wav_lens)
         else:
             feats = self.features(wavs, wav_lens)
+        aug = self.__dict__.get("_specaug")
+        if aug is not None and stage == Stage.TRAIN:
+            # reference :65-67: the model's input is augmented, the target (the stash, or compute_objectives'
+            # own features) is not.  A captured step only launches on the plan _fit_batch_graph has sent
+            self._specaug_shapes[tuple(wavs.shape)] = tuple(feats.shape)
+            feats = aug.apply(feats) if self.__dict__.get("_specaug_drawn") else aug(feats)
         return self.modules.ConvAE(feats)
+
+    def spec_augment(self):
+        """the SpecAugment of the input features if hparams switch it on, else None"""
+        if not getattr(self.hparams, "spec_augment", False):
+            return None
+        from . import specaug
+        aug = getattr(self.hparams, "augmentation", None)
+        return aug if isinstance(aug, specaug.SpecAugment) else None
 
     def compute_objectives(self, predictions, batch, stage):
         reconstructed_speech, sex_logits = predictions
@@ -524,7 +538,9 @@ class SexAnonymizationTraining(Brain):
                 tuple(bool(st.get(p)) for p in params if not p.requires_grad),
                 tuple(tok.shape), getattr(self, "asr_brain", None) is not None,
                 # front_end_once: whether the captured normalisation writes one tensor or two
-                self.front_end_once, bool(not upd and getattr(nrm, "_count_positive", False)))
+                self.front_end_once, bool(not upd and getattr(nrm, "_count_positive", False)),
+                # SpecAugment of the input: three more launches in the captured step
+                self.__dict__.get("_specaug") is not None)
 
     def _step_core(self, batch):
         predictions = self.compute_forward(batch, Stage.TRAIN)
@@ -564,10 +580,22 @@ class SexAnonymizationTraining(Brain):
             self.nonfinite_count += self._poll_nonfinite(wait=True)      # nothing pending across the capture
             g = torch.cuda.CUDAGraph()
             self.optimizer.zero_grad(set_to_none=True)
-            with torch.cuda.graph(g):
-                ent["loss"] = self._step_core(ent["batch"])
+            aug = self.__dict__.get("_specaug")
+            if aug is not None:
+                # this step's plan goes into the module's persistent buffer (allocated here, outside the
+                # capture); the captured step launches on that buffer, every replay after a draw of its own
+                ent["specaug"] = self._specaug_shapes[tuple(wavs.shape)]
+                aug.draw(*ent["specaug"], device=self.device)
+                self._specaug_drawn = True
+            try:
+                with torch.cuda.graph(g):
+                    ent["loss"] = self._step_core(ent["batch"])
+            finally:
+                self._specaug_drawn = False
             ent["graph"] = g
             # the capture itself does not execute the step: replay it for this batch below
+        elif "specaug" in ent:
+            self._specaug.draw(*ent["specaug"], device=self.device)
         wavs, lens = batch.sig
         ent["wav"].copy_(wavs, non_blocking=True)
         ent["lens"].copy_(lens, non_blocking=True)
@@ -635,6 +663,13 @@ class SexAnonymizationTraining(Brain):
     def on_stage_start(self, stage, epoch=None):
         from .metrics import AccuracyStats, SimilarityMetricsStats
         self.external_classifier = self.load_external_classifier()
+        if stage == Stage.TRAIN:
+            # SpecAugment of the input: looked up once per epoch (a step without it runs nothing of it) and
+            # reseeded from (seed, epoch, rank), so that a run resumed here draws what an uninterrupted one draws
+            self._specaug = self.spec_augment()
+            if self._specaug is not None:
+                self.__dict__.setdefault("_specaug_shapes", {})
+                self._specaug.reseed(epoch, sdist.rank())
         if stage != Stage.TRAIN:
             self.sex_classification_acc = AccuracyStats()
             self.sex_classification_acc_extern = AccuracyStats()

@@ -869,3 +869,57 @@ def wav_augment(wav, noise, scales, plan_words, R, Lp, S_in, S_out, W, first_min
                                     int(S_out), int(W), int(first_min), int(first_max), _f(out), L.stream()),
             "sa_wav_augment")
     return out
+
+
+# ---- SpecAugment of the input features (csrc/sa_specaug.hip; specaug.py) ----
+SPECAUG_TILE = 32          # output frames per workgroup of sa_specaug_warp_sums / sa_specaug_fill
+
+
+def _specaug_shape(x, what):
+    if _aug_in(x, what).dim() != 3:
+        raise L.SaHipError(f"{what}: expected [B, T, F], got {tuple(x.shape)}")
+    B, T, F = x.shape
+    if B < 1 or B > 65535 or T < 1 or F < 4 or F % 4 or F > 128:
+        raise L.SaHipError(f"{what}: [B, T, F] = {tuple(x.shape)} -- B in 1..65535, T >= 1, F a multiple of 4 up to 128")
+    if x.data_ptr() % 16:
+        raise L.SaHipError(f"{what}: expected 16-byte aligned storage")
+    return B, T, F
+
+
+def _specaug_plan(words, B, T):
+    from . import specaug
+    need = specaug.plan_words(B, T)
+    if _aug_in(words, "plan", torch.int32).numel() < need:
+        raise L.SaHipError(f"plan: {words.numel()} words, the geometry needs {need}")
+
+
+def specaug_warp_sums(x, plan_words):
+    """x [B, T, F] -> (the warped features, a new tensor; part [tiles * B, 2] fp64: per workgroup the sum of its
+    values and of those in frequency-masked columns).  plan_words: the device copy of specaug.Plan.words()."""
+    B, T, F = _specaug_shape(x, "x")
+    _specaug_plan(plan_words, B, T)
+    out = torch.empty_like(x)
+    part = torch.empty(-(-T // SPECAUG_TILE) * B, 2, dtype=torch.float64, device=x.device)
+    L.check(L.load().sa_specaug_warp_sums(_f(x), _f(plan_words), B, T, F, _f(out), _f(part), L.stream()),
+            "sa_specaug_warp_sums")
+    return out, part
+
+
+def specaug_finalize(part, plan_words, B, T, F):
+    """vals [2] fp32 = (val_f, val_t), the fill values of the frequency and of the time masks, from the partial sums"""
+    B, T, F = int(B), int(T), int(F)
+    _aug_in(part, "part", torch.float64, (-(-T // SPECAUG_TILE) * B, 2))
+    _specaug_plan(plan_words, B, T)
+    vals = torch.empty(2, dtype=torch.float32, device=part.device)
+    L.check(L.load().sa_specaug_finalize(_f(part), _f(plan_words), B, T, F, _f(vals), L.stream()),
+            "sa_specaug_finalize")
+    return vals
+
+
+def specaug_fill(out, plan_words, vals):
+    """stores vals on the masked cells of out [B, T, F] (in place; out is what specaug_warp_sums returned) -> out"""
+    B, T, F = _specaug_shape(out, "out")
+    _specaug_plan(plan_words, B, T)
+    _aug_in(vals, "vals", shape=(2,))
+    L.check(L.load().sa_specaug_fill(_f(plan_words), _f(vals), B, T, F, _f(out), L.stream()), "sa_specaug_fill")
+    return out

@@ -7,8 +7,10 @@ speechbrain_convae_train.py:516-518).
 
 Class paths of the speechbrain / reference objects on the hot path resolve to this package's HIP
 implementations (CLASS_MAP); objects of subsystems that are out of scope (ASR transformer, beam
-search, SpecAugment, pretrainer ...) become ``Unavailable`` placeholders that raise on use, so a
-reference YAML loads unmodified and the ConvAE path runs.
+search, SpeedPerturb, pretrainer ...) become ``Unavailable`` placeholders that raise on use, so a
+reference YAML loads unmodified and the ConvAE path runs.  The reference's ``augmentation`` object
+(speechbrain.lobes.augment.SpecAugment) loads as ``specaug.SpecAugment``; it is applied only when
+``spec_augment`` is true.
 """
 import ast
 import functools
@@ -26,6 +28,7 @@ CLASS_MAP = {
     "speechbrain.lobes.models.Xvector.Classifier": "speech_anonymization_amd.xvector.Classifier",
     "speechbrain.lobes.augment.TimeDomainSpecAugment": "speech_anonymization_amd.augment.TimeDomainSpecAugment",
     "speechbrain.processing.speech_augmentation.AddNoise": "speech_anonymization_amd.augment.AddNoise",
+    "speechbrain.lobes.augment.SpecAugment": "speech_anonymization_amd.specaug.SpecAugment",
     "speechbrain.utils.epoch_loop.EpochCounter": "speech_anonymization_amd.brain.EpochCounter",
     "speechbrain.utils.train_logger.FileTrainLogger": "speech_anonymization_amd.brain.FileTrainLogger",
     "speechbrain.utils.checkpoints.Checkpointer": "speech_anonymization_amd.checkpoint.Checkpointer",

@@ -10,7 +10,9 @@
 
 Extra options of this build: ``--synthetic N`` trains on N synthetic utterances per epoch instead
 of CSV manifests (there is no dataset on the GPU box).  ``--external_classifier_ckpt DIR`` (a
-checkpoint of gender_classifier_train.py) adds the ACC_external / ACC_external_orig columns.  The
+checkpoint of gender_classifier_train.py) adds the ACC_external / ACC_external_orig columns.
+``--spec_augment true`` augments the model's input features at Stage.TRAIN (time warp, frequency and
+time masks: the reference's ``augmentation``, settings under ``spec_augment_options``).  The
 frozen-ASR utility loss and WER are not part of this path."""
 import os
 import sys
@@ -35,6 +37,21 @@ def check_model_type(model_type, run_opts, environ=None):
             raise SystemExit("model_type fcae runs on one GPU: data parallelism is not implemented for it")
         if run_opts.get("hip_graph"):
             raise SystemExit("model_type fcae does not support --hip_graph (its step is nine launches)")
+
+
+def setup_spec_augment(hparams):
+    """--spec_augment true: SpecAugment of the input features at Stage.TRAIN (the reference's hparams.augmentation,
+    :65-67), for every model type.  A specaug.SpecAugment the YAML built itself is kept; otherwise one is built
+    from spec_augment_options.  Prints one line when it is on."""
+    if not hparams.get("spec_augment"):
+        return None
+    from speech_anonymization_amd import specaug
+    aug = hparams.get("augmentation")
+    if not isinstance(aug, specaug.SpecAugment):
+        aug = hparams["augmentation"] = specaug.SpecAugment(**dict(hparams.get("spec_augment_options") or {}))
+    if sdist.if_main_process():
+        print(f"speechbrain_convae_train: SpecAugment of the input features on: {aug.describe()}")
+    return aug
 
 
 def main(argv):
@@ -66,6 +83,7 @@ def main(argv):
         from speech_anonymization_amd import fcae          # fp32 whatever `precision` says
         model = fcae.FullyConnectedAutoencoder(80, hparams["batch_size"])
 
+    setup_spec_augment(hparams)
     sa_brain = B.SexAnonymizationTraining(modules=hparams["modules"], opt_class=hparams["Adam"],
                                           hparams=hparams, run_opts=run_opts,
                                           checkpointer=hparams.get("checkpointer"))

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""Times the SpecAugment of the input features (csrc/sa_specaug.hip) at B = 32, T = 1008, F = 80, a torch-operator
+restatement of the same plan on the GPU in the same run, and the ConvAE train step with the feature off and on.
+
+Device events around each call after a warm-up; the median of --steps calls.  Prints one JSON line (and writes it
+to --out):
+  launches_ms            sa_specaug_warp_sums + sa_specaug_finalize + sa_specaug_fill on an uploaded plan
+  launches_gbps          8 B T F bytes (one read, one write of the features) over that time
+  torch_ms, speedup      the same plan in torch operators: two interpolate calls, cat, two mean + masked_fill; its
+                         result is compared with the kernels' before it is timed
+  module_ms              one SpecAugment call: plan draw on the host, upload, the three launches
+  step_off_ms, step_on_ms, step_delta_ms
+                         SexAnonymizationTraining.fit_batch of the benchmark's brain and batch (bench.py's own
+                         builders) without and with the feature, in this run; eager and, with --graph, replayed"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+REFERENCE = dict(freq_mask_width=30, time_mask_width=40, replace_with_zero=False)
+
+
+def time_calls(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts)
+
+
+def torch_restatement(x, plan, fm, tm):
+    if plan.c is not None:
+        it = lambda seg, n: F.interpolate(seg.unsqueeze(1), (n, x.shape[2]), mode="bicubic",
+                                          align_corners=True).squeeze(1)
+        x = torch.cat([it(x[:, :plan.c], plan.w), it(x[:, plan.c:], plan.T - plan.w)], 1)
+    x = x.masked_fill(fm, 0.0 if plan.zero else x.mean())
+    return x.masked_fill(tm, 0.0 if plan.zero else x.mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--T", type=int, default=1008)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-step", action="store_true", help="skip the train-step timings")
+    ap.add_argument("--graph", action="store_true", help="also time the train step replayed from a hipGraph")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "specaug_bench.json"))
+    a = ap.parse_args()
+    assert a.steps >= 20, "the median of at least 20 calls"
+    dev = torch.device("cuda:0")
+    from speech_anonymization_amd import specaug
+    B, T, Fq = a.B, a.T, 80
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(B, T, Fq, generator=g) * 1.5 + 0.3).to(dev)
+    plan = specaug.draw_plan(g, B, T, Fq, REFERENCE)
+    words = plan.words().to(dev)
+    fm, tm = (m.to(dev) for m in plan.masks())
+    fm, tm = fm[:, None, :], tm[:, :, None]
+    fused = lambda: specaug.apply_words(x, words)
+    restated = lambda: torch_restatement(x, plan, fm, tm)
+    got, want = fused(), restated()
+    diff, scale = float((got - want).abs().max()), float(want.abs().max())
+    assert diff <= 1e-5 * scale, (diff, scale)
+    ms = time_calls(fused, a.warmup, a.steps)
+    torch_ms = time_calls(restated, a.warmup, a.steps)
+    nbytes = 8 * B * T * Fq
+    out = {"B": B, "T": T, "F": Fq, "c": plan.c, "w": plan.w, "steps": a.steps, "launches_ms": round(ms, 4),
+           "bytes": nbytes, "launches_gbps": round(nbytes / ms / 1e6, 1), "torch_ms": round(torch_ms, 4),
+           "speedup_vs_torch": round(torch_ms / ms, 2), "max_abs_diff_vs_torch": diff}
+    aug = specaug.SpecAugment(seed=1, **REFERENCE)
+    out["module_ms"] = round(time_calls(lambda: aug(x), a.warmup, a.steps), 4)
+
+    if not a.no_step:
+        import bench
+        from speech_anonymization_amd.brain import Stage
+        batch = bench.synthetic_batch(B, 0, dev, 160 * (T - 1))
+        for mode in (("eager", "graph") if a.graph else ("eager",)):
+            for name, on in (("off", False), ("on", True)):
+                br = bench.build_brain(dev, "bf16x3", B, hip_graph=mode == "graph")
+                br.hparams.spec_augment = on
+                br.hparams.augmentation = specaug.SpecAugment(seed=1, **REFERENCE) if on else None
+                br.on_stage_start(Stage.TRAIN, 1)
+
+                def step():
+                    br.step += 1
+                    br.fit_batch(batch)
+                key = f"step_{name}_ms" if mode == "eager" else f"graph_step_{name}_ms"
+                out[key] = round(time_calls(step, max(a.warmup, 6), a.steps), 4)
+                del br
+                torch.cuda.empty_cache()
+            pre = "" if mode == "eager" else "graph_"
+            out[pre + "step_delta_ms"] = round(out[pre + "step_on_ms"] - out[pre + "step_off_ms"], 4)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
