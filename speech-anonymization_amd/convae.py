@@ -95,45 +95,24 @@ class ConvAutoencoder(nn.Module):
         )
         self.sex_classifier = TDNNSexClassifier(2)
         self.act_dtype, self.kcode = ops.PRECISIONS[precision]
-        # kernel precision of the decoder convolutions (experiment knob, default = same as the rest)
-        self.dec_kcode = self.kcode
+        # kernel precision of the data-gradient convolutions (tools/precision_probe.py overrides it)
         self.dgrad_kcode = ops.DGRAD_CODE[precision]
         # forward convs also store their transformed input in bf16 for the weight gradient
-        # (bf16x3 / bf16x1f models; +1/2 of the saved activations in memory, identical results)
+        # (bf16x3 / bf16x1f models; +1/2 of the saved activations in memory, identical results).
+        # With the cache and a bf16x3 / bf16 data gradient the norm-backward apply passes run in the
+        # prologue of the data-gradient convolutions; otherwise as separate sa_ew_apply launches.
         self.cache_wgrad_operand = cache_wgrad_operand
-        # with the cache: the norm-backward apply passes run in the prologue of the data-gradient
-        # convolutions (False: separate sa_ew_apply launches)
-        self.fuse_apply = True
-        # option: weight-gradient GEMMs on a second stream beside the data-gradient convolutions of
-        # the following layers.  Measured: the kernels do overlap, the step time does not change
-        # (13.34 vs 13.35 ms at B=32), so it is off unless SA_OVERLAP_WGRAD=1.
-        self.overlap_wgrad = os.environ.get("SA_OVERLAP_WGRAD", "0") == "1"
         # speechbrain's StatisticsPooling adds eps*U[1,9] to the pooled mean on every call
         # (train and eval); True reproduces that, a tensor [B,128] in [0,1] fixes the draw
         # (tests), False/None gives the deterministic form the oracle uses.
         self.pooling_noise = pooling_noise
         self.sync_bn = sync_bn
-        # True: slab reductions and their finalisers in one launch each (sa_reduce_finalize: 46 fewer
-        # launches per step).  Measured neutral to slightly slower (B = 32: 10.08 vs 10.04 ms; B = 10:
-        # within the run-to-run spread), so the separate sa_sum_partials / sa_fin_* launches stay
-        # the default (they are also what runs wherever the sums are all-reduced first).
-        self.fused_finalize = os.environ.get("SA_FUSED_FINALIZE", "0") == "1"
-        # the InstanceNorm FORWARD pairs alone (per utterance: no hand-off between workgroups in that mode)
-        self.fused_in_fwd = os.environ.get("SA_FUSED_IN_FWD", "0") == "1"
-        # The FC head of the classifier is ~12 (forward) / ~25 (backward) launches of 5-10 us each
-        # that nothing else waits for until the branches merge: True runs them on a side stream
-        # beside the decoder's convolutions (forward: after the pooling; backward: the decoder's
-        # backward is issued first).  Measured neutral (B = 32: 9.75-9.78 vs 9.77-9.88 ms; B = 10:
-        # 4.02-4.08 vs 4.02 ms), so off by default; never under SyncBatchNorm (the head then
-        # contains collectives).
-        self.overlap_head = os.environ.get("SA_OVERLAP_HEAD", "0") == "1"
+        # The kernels of a step are issued on one stream, reductions and finalisers as separate launches,
+        # the bias gradients and split-K reducers of a backward stage batched at its end: DESIGN.md has
+        # the measurements behind each.  The two switches below both have a live off path.
         # the FC head as one forward and one backward launch (sa_head_fused.hip) where its BatchNorm
         # statistics are local and B fits one workgroup; SA_FUSED_HEAD=0: the separate launches
         self.fused_head = os.environ.get("SA_FUSED_HEAD", "1") == "1"
-        # bias gradients of a backward stage as two launches at the end of the stage (sa_bias_multi)
-        # instead of sa_sum_partials + sa_fin_bias per layer
-        self.batch_bias = os.environ.get("SA_BATCH_BIAS", "1") == "1"
-        self.batch_wred = os.environ.get("SA_BATCH_WRED", "1") == "1"
         # decoder.8's data gradient and weight gradient from one read of y8 (sa_bwd1C; same bits);
         # SA_FUSED_BWD1C=0: the two launches (conv1toC + wgrad1C)
         self.fused_bwd1c = os.environ.get("SA_FUSED_BWD1C", "1") == "1"
@@ -142,14 +121,6 @@ class ConvAutoencoder(nn.Module):
         # deals); [b0, b1, ...] = the ranks' batch sizes.  With the sizes known the pooled rows are
         # exchanged ONCE and the head runs on the global batch on every rank (_head_plan).
         self.dp_batch_sizes = None
-        # parity probe only (see _ConvAEFn.backward): the backward re-reads bf16-rounded stored tensors
-        self.bwd_reload_bf16 = os.environ.get("SA_BWD_RELOAD_BF16", "0") == "1"
-        # PARITY PROBE, not a mode (tools/bf16_reload_probe.py): what storing the convolution outputs in
-        # bf16 would do -- 1: every stored forward tensor is rounded to bf16 right after the launch that
-        # produced it (its statistics still come from the fp32 accumulators, operands stay split);
-        # 2: the data gradients between the backward launches as well; 3: those gradients only;
-        # 4: the decoder's stored outputs and the gradients of the decoder's backward only
-        self.store_bf16_probe = int(os.environ.get("SA_STORE_BF16_PROBE", "0"))
 
     def forward(self, feats):
         # walking the module tree costs ~0.15 ms a call: the (names, parameters) lists are cached
@@ -187,16 +158,6 @@ class ConvAutoencoder(nn.Module):
         cg, inorm = _launchers(self, P, B)
         y, _, _ = _encoder_launches(self, P, pw, cg, inorm, x0, Ltot, False)
         return _decoder_launches(P, pw, cg, inorm, y[5], Ltot)[-1].view(B, T, 80)
-
-    def _wgrad_stream(self, device):
-        if getattr(self, "_wgs", None) is None and device.type == "cuda":
-            self._wgs = torch.cuda.Stream(device=device)
-        return getattr(self, "_wgs", None)
-
-    def _head_stream(self, device):
-        if getattr(self, "_hs", None) is None and device.type == "cuda":
-            self._hs = torch.cuda.Stream(device=device)
-        return getattr(self, "_hs", None)
 
     def _side_stream(self, device):
         if getattr(self, "_side", None) is None and device.type == "cuda":
@@ -295,9 +256,7 @@ PACK_PLAN = (
 
 
 def _kcode(model, key, kind):
-    if kind.endswith("dgrad"):
-        return model.dgrad_kcode
-    return model.dec_kcode if key.startswith("decoder") else model.kcode
+    return model.dgrad_kcode if kind.endswith("dgrad") else model.kcode
 
 
 def _packed(model, P):
@@ -317,14 +276,6 @@ def _packed(model, P):
 
 def _conv(x, w, *args, **kw):
     return ops.conv_gemm(x, w.img, *args, code=w.code, **kw)
-
-
-def _round_first(out):
-    """store_bf16_probe: the launch's main output as a bf16-stored tensor would hold it"""
-    y = out[0] if isinstance(out, tuple) else out
-    if torch.is_tensor(y) and y.dtype == torch.float32:
-        y.copy_(y.bfloat16())
-    return out
 
 
 class _PendingApply:
@@ -365,17 +316,9 @@ def _launchers(model, P, B, A=None):
     def cg(x, w, key, *args, **kw):
         if A is not None and key is not None and P[key].requires_grad:
             A[key] = kw["a_out"] = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        out = _conv(x, w, *args, **kw)
-        if model.store_bf16_probe in (1, 2) or (model.store_bf16_probe == 4 and str(key).startswith("decoder")):
-            y_ = out[0] if isinstance(out, tuple) else out
-            if y_.dtype == torch.float32:
-                y_.copy_(y_.bfloat16())
-        return out
+        return _conv(x, w, *args, **kw)
 
     def inorm(stats, n, prefix, C):
-        if model.fused_finalize or model.fused_in_fwd:
-            return ops.reduce_finalize(L.FIN_IN_FWD, stats, B, C, count=n, gamma=P[prefix + ".weight"],
-                                       beta=P[prefix + ".bias"])
         sums = ops.sum_partials(stats, B)
         return ops.fin_in_fwd(sums, B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
     return cg, inorm
@@ -387,8 +330,6 @@ def _encoder_launches(model, P, pw, cg, inorm, x0, Ltot, want_pro_stats):
     needs as a by-product of its prologue (want_pro_stats)."""
     L2, L4 = Ltot // 2, Ltot // 4
     y0 = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], model.act_dtype)
-    if model.store_bf16_probe in (1, 2) and y0.dtype == torch.float32:
-        y0.copy_(y0.bfloat16())
     y1, st = cg(y0, pw("encoder.2.weight", "conv_fwd"), "encoder.2.weight", P["encoder.2.bias"], 32, 64, 2, 1,
                 ops.taps_conv(K5, 1, 2), L2, swish=True, want_stats=True)
     n1 = inorm(st, L2, "encoder.3", 64)
@@ -431,7 +372,6 @@ class _ConvAEFn(torch.autograd.Function):
         # parameters that only feed it then get no gradient at all, like in the reference's graph
         ctx.set_materialize_grads(False)
         P = dict(zip(names, params))
-        dt = model.act_dtype
         train = model.training
         x0, B, T, Ltot = _input_rows(feats)
         L2, L4 = Ltot // 2, Ltot // 4
@@ -445,16 +385,9 @@ class _ConvAEFn(torch.autograd.Function):
                    and ops.WGRAD_CODE[model.precision] in (L.BF16X1F, L.BF16) and model.kcode != L.FP8)
 
         cg, inorm = _launchers(model, P, B, A if cache_a else None)
-        ff = model.fused_finalize
 
         def bn_stats(stats, count, mod, prefix, C, ci):
             """train-mode BatchNorm from the per-tile partial statistics of the producing launch"""
-            if train and ff and not model._bn_syncs():
-                out = ops.reduce_finalize(L.FIN_BN_FWD, stats, B, C, count=count, gamma=P[prefix + ".weight"],
-                                          beta=P[prefix + ".bias"], run_mean=mod.running_mean,
-                                          run_var=mod.running_var)
-                tracked.append(mod.num_batches_tracked)
-                return out
             sums = ops.sum_partials(stats, 1, rows=model._bn_rows()) if train else None
             return bnorm(sums, count, mod, prefix, C, ci)
 
@@ -517,27 +450,16 @@ class _ConvAEFn(torch.autograd.Function):
         fused_head = (train and model.fused_head and (plan is not None or not model._bn_syncs())
                       and Bh <= ops.head_max_rows())
         clsP = {k[len("sex_classifier.classify."):]: v for k, v in P.items() if k.startswith("sex_classifier.classify.")}
-        hs = (model._head_stream(feats.device) if (model.overlap_head and not model._bn_syncs() and not fused_head)
-              else None)
         if fused_head:
             H1, f1, H2, f2, logp = ops.head_fwd(head_in, clsP, cls.classify[2], cls.classify[5])
             tracked += [cls.classify[2].num_batches_tracked, cls.classify[5].num_batches_tracked]
-        elif hs is None:
+        else:
             H1, f1, H2, f2, logp = head_fwd(head_in, Bh, plan is not None)
-        else:                                  # beside the decoder's convolutions
-            main = torch.cuda.current_stream()
-            hs.wait_stream(main)
-            with torch.cuda.stream(hs):
-                H1, f1, H2, f2, logp = head_fwd(head_in, Bh)
         logp_all = logp
         if plan:                               # this rank's rows of the global log-probabilities
             logp = logp_all[plan[0]:plan[0] + B]
         # ---------------- decoder ----------------
         y6, n6, y7, y8, n8, recon = _decoder_launches(P, pw, cg, inorm, y5, Ltot)
-        if hs is not None:
-            main.wait_stream(hs)
-            for tns in (H1, H2, logp_all, f1[0], f2[0]):      # allocated on the side stream, consumed on this one
-                tns.record_stream(main)
 
         if tracked:
             torch._foreach_add_(tracked, 1)
@@ -561,14 +483,6 @@ class _ConvAEFn(torch.autograd.Function):
             raise SaHipError("backward through eval-mode BatchNorm is not implemented")
         y0, y1, y2, y3, y4, y5, y6, y7, y8 = S["y"]
         r0, r1, r2 = S["r"]
-        if model.bwd_reload_bf16:
-            # PARITY PROBE, not a mode: what bf16 side copies of the stored forward
-            # tensors would do to the gradients -- the tensors the backward only RE-READS (the
-            # normalisation-backward prologues' y, the epilogues' x) are rounded to bf16 here, the
-            # kernels and every other operand are unchanged (tools/bf16_reload_probe.py reports the result)
-            rb = lambda t_: t_.bfloat16().float() if t_ is not None and t_.dtype == torch.float32 else t_
-            y0, y1, y2, y3, y4, y5, y6, y7, y8 = (rb(t_) for t_ in (y0, y1, y2, y3, y4, y5, y6, y7, y8))
-            r0, r1, r2 = (rb(t_) for t_ in (r0, r1, r2))
         n1, n2, n3, n4, n6, n8 = S["n"][1], S["n"][2], S["n"][3], S["n"][4], S["n"][6], S["n"][8]
         bn_n, bn0, bn1, bn2 = S["bn"]
         f1, f2 = S["f"]
@@ -597,24 +511,15 @@ class _ConvAEFn(torch.autograd.Function):
         # the split-K reducers of a stage's weight gradients wait for the end of the stage like the bias
         # gradients (nobody reads them earlier) and run as one launch (sa_wgrad_reduce_multi)
         pending_wred = []
-        wg = functools.partial(ops.wgrad, code=ops.WGRAD_CODE[model.precision],
-                               defer=pending_wred if model.batch_wred else None)
-        ff = model.fused_finalize
+        wg = functools.partial(ops.wgrad, code=ops.WGRAD_CODE[model.precision], defer=pending_wred)
         # with the bf16 operand caches in place the apply pass of every normalised layer whose
         # gradient feeds a convolution moves into that convolution's prologue
-        fuse = bool(A) and model.fuse_apply and model.dgrad_kcode in (L.BF16X3, L.BF16)
+        fuse = bool(A) and model.dgrad_kcode in (L.BF16X3, L.BF16)
 
         def cg(gin, w, *args, **kw):
             """data-gradient / forward-type launch; a _PendingApply input selects the
             normalisation-backward prologue, which also emits the bf16 d y for the deferred weight
             gradients and the column sums for the bias gradient."""
-            if model.store_bf16_probe in (2, 3) or (model.store_bf16_probe == 4 and in_decoder[0]):
-                return _round_first(cg_(gin, w, *args, **kw))
-            return cg_(gin, w, *args, **kw)
-
-        in_decoder = [False]
-
-        def cg_(gin, w, *args, **kw):
             if not isinstance(gin, _PendingApply):
                 return _conv(gin, w, *args, **kw)
             p = gin
@@ -626,15 +531,9 @@ class _ConvAEFn(torch.autograd.Function):
             if want_cs:
                 cs = out[-1]
                 out = out[:-1] if len(out) > 2 else out[0]
-                nb_, nt_, cc_ = cs.shape
-                if ff:
-                    G[p.bias_key] = ops.reduce_finalize(L.FIN_BIAS, cs, nb_, cc_, ncomp=1, db=newg(p.bias_key))
-                elif model.batch_bias:
-                    G[p.bias_key] = newg(p.bias_key)
-                    pending_bias.append((cs, nb_, cc_, 1, G[p.bias_key]))
-                else:
-                    G[p.bias_key] = ops.fin_bias(ops.sum_partials(cs.view(nb_, nt_, cc_, 1), nb_), nb_, cc_,
-                                                 newg(p.bias_key), ncomp=1)
+                nb_, _, cc_ = cs.shape
+                G[p.bias_key] = newg(p.bias_key)
+                pending_bias.append((cs, nb_, cc_, 1, G[p.bias_key]))
             for f in p.wgrads:
                 f(dyc)
             p.wgrads = []
@@ -642,19 +541,15 @@ class _ConvAEFn(torch.autograd.Function):
 
         def bias_from(stats, key, C):
             if need[key]:
-                if ff:
-                    G[key] = ops.reduce_finalize(L.FIN_BIAS, stats, B, C, db=newg(key))
-                elif model.batch_bias:
-                    G[key] = newg(key)
-                    pending_bias.append((stats, B, C, 2, G[key]))
-                else:
-                    G[key] = ops.fin_bias(ops.sum_partials(stats, B), B, C, newg(key))
+                G[key] = newg(key)
+                pending_bias.append((stats, B, C, 2, G[key]))
 
         # bias gradients wait for the end of their stage: nothing reads them before the stage's
         # bucket is reduced, so all of a stage's slab sums run as two launches (sa_bias_multi)
         pending_bias = []
 
-        def flush_bias():
+        def flush_pending():
+            """the stage's queued bias sums, then its queued split-K reducers"""
             if pending_bias:
                 ops.bias_multi(pending_bias)
                 pending_bias.clear()
@@ -674,13 +569,9 @@ class _ConvAEFn(torch.autograd.Function):
             """g = d z (already multiplied by swish'), st = partial (sum dz, sum dz*yhat)."""
             mean, rstd = nrm[0], nrm[1]
             dg, db = newg(prefix + ".weight"), newg(prefix + ".bias")
-            if ff:
-                c1, c2, c3 = ops.reduce_finalize(L.FIN_IN_BWD, st, B, C, count=Ln, gamma=P[prefix + ".weight"],
-                                                 mean=mean, rstd=rstd, dgamma=dg, dbeta=db)
-            else:
-                sums = ops.sum_partials(st, B)
-                c1, c2, c3 = ops.fin_norm_bwd(sums, sums, B * C, C, Ln, P[prefix + ".weight"], mean, rstd,
-                                              dgamma=dg, dbeta=db)
+            sums = ops.sum_partials(st, B)
+            c1, c2, c3 = ops.fin_norm_bwd(sums, sums, B * C, C, Ln, P[prefix + ".weight"], mean, rstd,
+                                          dgamma=dg, dbeta=db)
             G[prefix + ".weight"], G[prefix + ".bias"] = dg, db
             if fuse:
                 return _PendingApply(g, y, (c1, c2, c3), False, False, bias_key)
@@ -701,16 +592,11 @@ class _ConvAEFn(torch.autograd.Function):
             mean, rstd = bn[0], bn[1]
             kw = dict(s1=xp[0], t1=xp[1], xp_is_act=True) if xp else {}
             dg, db = newg(prefix + ".weight"), newg(prefix + ".bias")
-            if ff and not model._bn_syncs():
-                c1, c2, c3 = ops.reduce_finalize(L.FIN_BN_BWD, st, B, 128, count=float(B * Ln),
-                                                 gamma=P[prefix + ".weight"], mean=mean, rstd=rstd,
-                                                 sign=-1.0 if xp else 1.0, dgamma=dg, dbeta=db)
-            else:
-                lsums = ops.sum_partials(st, 1, rows=model._bn_rows())
-                gsums, _ = model._bn_global(lsums)
-                c1, c2, c3 = ops.fin_norm_bwd(gsums, lsums, 128, 128, float(B * Ln), P[prefix + ".weight"],
-                                              mean, rstd, sign=-1.0 if xp else 1.0, dgamma=dg, dbeta=db,
-                                              n_dev=cdev(ci))
+            lsums = ops.sum_partials(st, 1, rows=model._bn_rows())
+            gsums, _ = model._bn_global(lsums)
+            c1, c2, c3 = ops.fin_norm_bwd(gsums, lsums, 128, 128, float(B * Ln), P[prefix + ".weight"],
+                                          mean, rstd, sign=-1.0 if xp else 1.0, dgamma=dg, dbeta=db,
+                                          n_dev=cdev(ci))
             G[prefix + ".weight"], G[prefix + ".bias"] = dg, db
             if fuse:
                 return _PendingApply(g, r, (c1, c2, c3), True, not xp, bias_key)
@@ -720,52 +606,27 @@ class _ConvAEFn(torch.autograd.Function):
                 bias_from(st2, bias_key, 128)
             return g
 
-        ws = model._wgrad_stream(dev) if model.overlap_wgrad else None
-
-        def on_side(fn, *tensors):
-            """run fn on the weight-gradient stream, ordered after everything enqueued so far"""
-            if ws is None:
-                return fn()
-            ws.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(ws):
-                out = fn()
-            for t in tensors:
-                t.record_stream(ws)                  # the allocator must not recycle them early
-            return out
-
-        def side_join():
-            if ws is not None:
-                torch.cuda.current_stream().wait_stream(ws)
-
-        def run_conv_wgrad(key, x, dy, cin, cout, sa, Mrows, K, dil, pad, pro):
-            if key in A:
-                x, pro = A[key], dict(x_pre=True, dy_pre=bool(pro.get("dy_pre")))
-            G[key] = on_side(lambda: wg(x, dy, cin, cout, sa, 1, [(k * dil - pad, 0) for k in range(K)],
-                                        Mrows, newg(key), (K, cin * K, 1), **pro), x, dy)
-
         def conv_wgrad(key, x, dy, cin, cout, sa, Mrows, K, dil, pad, **pro):
             if not need[key]:
                 return
             if isinstance(dy, _PendingApply):                # runs once the bf16 d y exists
-                dy.wgrads.append(lambda dyc: run_conv_wgrad(key, x, dyc, cin, cout, sa, Mrows, K, dil, pad,
-                                                            dict(dy_pre=True)))
-            else:
-                run_conv_wgrad(key, x, dy, cin, cout, sa, Mrows, K, dil, pad, pro)
-
-        def run_convT_wgrad(key, x, dy, cin, cout, Mrows, dy_pre):
-            pro = {}
+                dy.wgrads.append(lambda dyc: conv_wgrad(key, x, dyc, cin, cout, sa, Mrows, K, dil, pad, dy_pre=True))
+                return
             if key in A:
-                x, pro = A[key], dict(x_pre=True, dy_pre=dy_pre)
-            G[key] = on_side(lambda: wg(x, dy, cin, cout, 1, 2, CONVT_WG_TAPS, Mrows, newg(key),
-                                        (cout * K5, K5, 1), **pro), x, dy)
+                x, pro = A[key], dict(x_pre=True, dy_pre=bool(pro.get("dy_pre")))
+            G[key] = wg(x, dy, cin, cout, sa, 1, [(k * dil - pad, 0) for k in range(K)], Mrows, newg(key),
+                        (K, cin * K, 1), **pro)
 
-        def convT_wgrad(key, x, dy, cin, cout, Mrows):
+        def convT_wgrad(key, x, dy, cin, cout, Mrows, dy_pre=False):
             if not need[key]:
                 return
             if isinstance(dy, _PendingApply):
-                dy.wgrads.append(lambda dyc: run_convT_wgrad(key, x, dyc, cin, cout, Mrows, True))
-            else:
-                run_convT_wgrad(key, x, dy, cin, cout, Mrows, False)
+                dy.wgrads.append(lambda dyc: convT_wgrad(key, x, dyc, cin, cout, Mrows, True))
+                return
+            pro = {}
+            if key in A:
+                x, pro = A[key], dict(x_pre=True, dy_pre=dy_pre)
+            G[key] = wg(x, dy, cin, cout, 1, 2, CONVT_WG_TAPS, Mrows, newg(key), (cout * K5, K5, 1), **pro)
 
         # an output the loss does not use (the endtoend "sex only" branch,
         # speechbrain_convae_train.py:112-113, leaves recon out of the graph): like autograd in the
@@ -781,7 +642,7 @@ class _ConvAEFn(torch.autograd.Function):
             d_logp = torch.zeros(B, 2, device=dev)
 
         def finish(d_feats=None):
-            flush_bias()
+            flush_pending()
             buckets.join()
             ctx.S = None
             # (Brain.check_gradients clips the buckets directly when every .grad is still a view of one of them):
@@ -844,8 +705,6 @@ class _ConvAEFn(torch.autograd.Function):
         def tdnn_bwd(dP):
             t = "sex_classifier.tdnn."
             g, st = ops.pool_bwd(r2, bn2[2], bn2[3], dP, S["pmean"], S["psd"], bn=(bn2[0], bn2[1]))
-            if model.store_bf16_probe in (2, 3):
-                _round_first(g)
             g = bn_finish(g, st, r2, bn2, Lc, t + "8", t + "6.bias", 3)
             conv_wgrad(t + "6.weight", r1, g, 128, 128, 1, Lc, 3, 3, 0, s2=bn1[2], t2=bn1[3])
             g, st = cg(g, pw(t + "6.weight", "conv_dgrad"), None, 128, 128, 1, 1,
@@ -861,8 +720,7 @@ class _ConvAEFn(torch.autograd.Function):
             g, st = cg(g, pw(t + "0.weight", "conv_dgrad"), None, 128, 128, 1, 1,
                        ops.taps_conv_dgrad_s1(5, 1, 0), L4, want_stats=True, ep=bn_ep(y4, bn_n, xp4))
             da = bn_finish(g, st, y4, bn_n, L4, "sex_classifier.norm", None, 0, xp=xp4)      # includes GRL
-            side_join()
-            flush_bias()
+            flush_pending()
             if need_stage["sex_classifier"]:
                 buckets.reduce_stage("sex_classifier")
             return da
@@ -882,9 +740,6 @@ class _ConvAEFn(torch.autograd.Function):
                                                         s1=n8[2], t1=n8[3], swish=True)
                 g, st = ops.conv1toC(g_rec, P["decoder.8.weight"], None, dt, flip=True, want_stats=True,
                                      ep=dict(x=y8, s1=n8[2], t1=n8[3], mean=n8[0], rstd=n8[1]))  # d z8
-            if model.store_bf16_probe >= 2:
-                _round_first(g)
-            in_decoder[0] = True
             g = in_finish(g, st, y8, n8, 32, Ltot, "decoder.6", "decoder.5.bias")               # d y8
             convT_wgrad("decoder.5.weight", y7, g, 64, 32, L2)
             g, st = cg(g, pw("decoder.5.weight", "convT_dgrad"), None, 32, 64, 2, 1,
@@ -899,30 +754,15 @@ class _ConvAEFn(torch.autograd.Function):
                        ops.taps_convT_dgrad(), L4, want_stats=True)                              # d y5
             bias_from(st, "decoder.0.bias", 128)
             conv_wgrad("decoder.0.weight", y4, g, 128, 128, 1, L4, K5, 1, 2, s1=n4[2], t1=n4[3], swish=True)
-            side_join()
-            flush_bias()
+            flush_pending()
             if need_stage["decoder"]:
                 buckets.reduce_stage("decoder")
-            in_decoder[0] = False
             return g
 
-        hs = (model._head_stream(dev) if (model.overlap_head and run_decoder and not model._bn_syncs()
-                                         and dev.type == "cuda") else None)
-        if hs is None:
-            da4_cls = tdnn_bwd(head_bwd())
-            if not run_decoder:                   # classifier-only step: nothing below needs a gradient
-                return finish()
-            g = decoder_bwd()
-        else:
-            # the head's ~25 small launches on the side stream beside the decoder's backward
-            main = torch.cuda.current_stream()
-            hs.wait_stream(main)
-            with torch.cuda.stream(hs):
-                dP = head_bwd()
-            g = decoder_bwd()
-            main.wait_stream(hs)
-            dP.record_stream(main)
-            da4_cls = tdnn_bwd(dP)
+        da4_cls = tdnn_bwd(head_bwd())
+        if not run_decoder:                       # classifier-only step: nothing below needs a gradient
+            return finish()
+        g = decoder_bwd()
         if not run_encoder:
             return finish()
 
@@ -952,8 +792,7 @@ class _ConvAEFn(torch.autograd.Function):
         d_feats = None
         if ctx.need_input_grad:
             d_feats = ops.convCto1(g, P["encoder.0.weight"], None, flip=True).view(B, T, 80)
-        side_join()
-        flush_bias()
+        flush_pending()
         if need_stage["encoder"]:
             buckets.reduce_stage("encoder")
         # autograd's AccumulateGrad adopts a gradient only when nothing else references it (it

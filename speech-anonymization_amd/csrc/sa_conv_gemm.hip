@@ -640,10 +640,9 @@ extern "C" int sa_abi_sizeof(int which) {
     case 2: return (int)sizeof(SaEwArgs);
     case 3: return (int)sizeof(SaPackDesc);
     case 4: return (int)sizeof(SaTaps);
-    case 5: return (int)sizeof(SaFinArgs);
-    case 6: return (int)sizeof(SaBiasMulti);
-    case 7: return (int)sizeof(SaWredMulti);
-    case 8: return (int)sizeof(SaFlats);
+    case 5: return (int)sizeof(SaBiasMulti);
+    case 6: return (int)sizeof(SaWredMulti);
+    case 7: return (int)sizeof(SaFlats);
     default: return -22;
   }
 }

@@ -259,9 +259,6 @@ def conv_gemm(x, wp, bias, cin, cout, sa, u, phases, Lout, s1=None, t1=None, s2=
 
 
 WGRAD_TARGET_WGS = {True: 256, False: 512}
-if __import__("os").environ.get("SA_WG_TARGETS"):                    # tuning override "big,small"
-    _b, _s = __import__("os").environ["SA_WG_TARGETS"].split(",")
-    WGRAD_TARGET_WGS = {True: int(_b), False: int(_s)}
 
 
 def wgrad(x, dy, cin, cout, sa, u, taps, Mrows, dst, dst_strides, s1=None, t1=None, s2=None,
@@ -398,48 +395,6 @@ def sum_partials(part, nbatch, n=None, rows=False):
     return out
 
 
-_tickets = {}
-
-
-def reduce_finalize(mode, part, nbatch, Cc, ncomp=2, count=1.0, gamma=None, beta=None, mean=None, rstd=None,
-                    sign=1.0, dgamma=None, dbeta=None, db=None, run_mean=None, run_var=None, eps=1e-5,
-                    momentum=0.1):
-    """sa_reduce_finalize: the slab sums of `part` ([nbatch][nslab][Cc*ncomp], any trailing layout)
-    and the finaliser that consumes them in ONE launch (SaFinArgs in include/sa_hip.h).  Returns
-    (mean, rstd, scale, shift) for the FWD modes, (c1, c2, c3) for the BWD modes, db for FIN_BIAS.
-    Single-process statistics only (under SyncBatchNorm the sums are all-reduced between the two
-    halves: sum_partials + fin_* stay separate there)."""
-    n = Cc * ncomp
-    dev = part.device
-    nslab = part.numel() // (nbatch * n)
-    a = L.SaFinArgs()
-    a.part, a.nbatch, a.nslab, a.n, a.C, a.ncomp, a.mode = _f(part), nbatch, nslab, n, Cc, ncomp, mode
-    a.count, a.eps, a.momentum, a.sign = float(count), eps, momentum, sign
-    a.gamma, a.beta, a.mean, a.rstd = _f(gamma), _f(beta), _f(mean), _f(rstd)
-    a.dgamma, a.dbeta, a.db, a.run_mean, a.run_var = _f(dgamma), _f(dbeta), _f(db), _f(run_mean), _f(run_var)
-    out = None
-    if mode != L.FIN_IN_FWD:
-        rows = torch.empty(nbatch, n, dtype=torch.float64, device=dev)
-        # one ticket per 32-output chunk (sa_reduce_finalize indexes tickets[blockIdx.x]); the buffer is
-        # per (device, stream): launches on one stream are ordered, two streams must not share tickets
-        nchunk = -(-n // 32)
-        key = (dev, L.stream().value if hasattr(L.stream(), "value") else int(L.stream() or 0))
-        tk = _tickets.get(key)
-        if tk is None or tk.numel() < nchunk:   # zero-initialised once; the kernel resets what it used
-            tk = _tickets[key] = torch.zeros(max(256, nchunk), dtype=torch.int32, device=dev)
-        a.rows, a.tickets = _f(rows), _f(tk)
-    if mode in (L.FIN_IN_FWD, L.FIN_BN_FWD):
-        out = torch.empty(4, nbatch * Cc if mode == L.FIN_IN_FWD else Cc, dtype=torch.float32, device=dev)
-        a.o0, a.o1, a.o2, a.o3 = _f(out[0]), _f(out[1]), _f(out[2]), _f(out[3])
-    elif mode in (L.FIN_IN_BWD, L.FIN_BN_BWD):
-        out = torch.empty(3, nbatch * Cc if mode == L.FIN_IN_BWD else Cc, dtype=torch.float32, device=dev)
-        a.o0, a.o1, a.o2 = _f(out[0]), _f(out[1]), _f(out[2])
-    L.check(L.load().sa_reduce_finalize(C.byref(a), L.stream()), "sa_reduce_finalize")
-    if out is None:
-        return db
-    return tuple(out[i] for i in range(out.shape[0]))
-
-
 def fin_in_fwd(sums, B, Cc, n, gamma, beta, eps=1e-5):
     lib = L.load()
     o = torch.empty(4, B, Cc, dtype=torch.float32, device=sums.device)
@@ -519,16 +474,6 @@ def ew(kind, g, x, Cc, out=None, g2=None, s1=None, t1=None, mean=None, rstd=None
     a.stats, a.B, a.L = _f(stats), B, Ln
     fn = lib.sa_ew_stats if kind == "stats" else lib.sa_ew_apply
     L.check(fn(L.dt_code(x.dtype), Cc, C.byref(a), L.stream()), f"sa_ew_{kind}")
-    return stats
-
-
-def act_stats(x, s1, t1, swish=True):
-    lib = L.load()
-    B, Ln, Cc = x.shape
-    nt = lib.sa_ew_ntiles(Ln)
-    stats = torch.empty(B, nt, Cc, 2, dtype=torch.float32, device=x.device)
-    L.check(lib.sa_act_stats(L.dt_code(x.dtype), Cc, _f(x), _f(s1), _f(t1), int(swish), _f(stats), B,
-                             Ln, L.stream()), "sa_act_stats")
     return stats
 
 

@@ -49,7 +49,7 @@ def test_record_sizes_match_the_library():
     (SaFlats: sa_clip_grads); an unknown record is -EINVAL"""
     from speech_anonymization_amd import _lib
     lib = _lib.load()
-    recs = (_lib.SaConvArgs, _lib.SaWgradArgs, _lib.SaEwArgs, _lib.SaPackDesc, _lib.SaTaps, _lib.SaFinArgs,
+    recs = (_lib.SaConvArgs, _lib.SaWgradArgs, _lib.SaEwArgs, _lib.SaPackDesc, _lib.SaTaps,
             _lib.SaBiasMulti, _lib.SaWredMulti, _lib.SaFlats)
     for i, rec in enumerate(recs):
         assert lib.sa_abi_sizeof(i) == ctypes.sizeof(rec), rec.__name__

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one environment knob (0 / 1) as hipGraph replays (no host effects), B = 10 and B = 32, two rounds.
-#   usage: OUT=gpurun_out/x bash tools/env_ab.sh SA_OVERLAP_WGRAD
+#   usage: [OUT=dir] bash tools/env_ab.sh SA_FUSED_BWD1C
 VAR=$1; OUT=${OUT:-gpurun_out/env_ab}; mkdir -p $OUT
 for f in 0 1 0 1; do
   for b in 10 32; do
