@@ -107,25 +107,21 @@ int sa_conv_gemm(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* 
 /* sizeof(SaConvArgs | SaWgradArgs | SaEwArgs | SaPackDesc | SaTaps | SaBiasMulti | SaWredMulti | SaFlats) for which = 0..7: lets a binding
  * verify its mirror of these records (the library reads every field) */
 int sa_abi_sizeof(int which);
+/* ntiles: slabs per utterance of `stats`, nb_colsum and pro_stats -- one per tile, whichever kernel serves
+ * the launch; the reducers sum slabs in index order */
 int sa_conv_gemm_ntiles(int cin, int cout, int u, int Lout);
 int sa_conv_gemm_ntiles_tm(int tile_rows, int u, int Lout);       /* tiles per utterance at an explicit tile height */
 int sa_conv_gemm_set_tile_rows(int rows);   /* tuning knob: 0 (default policy), 64 or 128 */
-/* Geometry of a launch with this dtype code and shape: *ntiles = slabs per utterance of nb_colsum /
- * pro_stats ([B][*ntiles][cin] / [B][*ntiles][cin][2]), *nslabs = statistics slabs per utterance
- * (`stats` is [B][*nslabs][cout][2]); the reducers sum slabs in index order.  It depends on the
- * kernel choice below (the ping-pong kernel writes one slab per wave that shares a column block). */
-int sa_conv_gemm_geometry(int dtype, int cin, int cout, int u, int Lout, int* ntiles, int* nslabs);
 /* Kernel choice of sa_conv_gemm, process-wide.  2 (default): the weight-stationary kernel
  * (sa_conv_ws.hip) serves the bf16x3 128->128, 64->64 stride-1, 64->128 stride-2 and 128->64 / 64->32 transposed launches with >= 1536 tiles that it
  * covers (5 taps at unit spacing, 128 channels also 3 taps over 4 / 6 rows; no fused backward
- * epilogue, no normalisation-backward prologue), the one-tile-per-workgroup kernel everything else -- same geometry and, given the same
- * inputs, the same output bits.  0: one-tile kernel only.  1: the ping-pong kernel (sa_conv_pp.hip)
- * for the f32 / bf16x3 policies (opt-in, A/B timing).  sa_conv_pp_set_tile_rows: 0 (policy), 64, 128. */
+ * epilogue, no normalisation-backward prologue), sa_conv_wsd.hip the fused 128->128 data gradients under the
+ * same condition, the one-tile-per-workgroup kernel everything else -- same geometry and, given the same
+ * inputs, the same output bits.  0: one-tile kernel only.  Any other value: -22. */
 int sa_conv_gemm_set_impl(int impl);
-/* which kernel serves this launch under the current choice: 0 one-tile, 1 ping-pong, 2 weight-stationary
- * (profiling tools name the kernel they time with it) */
+/* which kernel serves this launch under the current choice: 0 one-tile, 2 weight-stationary, 3 weight-stationary
+ * fused data gradient (profiling tools name the kernel they time with it; 1 named a kernel that was removed) */
 int sa_conv_gemm_route(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a);
-int sa_conv_pp_set_tile_rows(int rows);
 
 /* fp32 master weights -> fragment-major MFMA operand image (K = GEMM reduction channels,
  * N = produced channels; element W(t,k,n) = src[k*sk + n*sn + t*st]).

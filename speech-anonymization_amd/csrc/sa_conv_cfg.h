@@ -1,5 +1,6 @@
-// Tile configuration shared by the two implicit-GEMM convolution kernels (sa_conv_gemm.hip: one
-// tile per 4-wave workgroup; sa_conv_pp.hip: two 4-wave groups per workgroup in anti-phase).
+// Tile configuration shared by the implicit-GEMM convolution kernels: the one-tile kernel
+// (sa_conv_gemm.hip, one tile per 4-wave workgroup) and the weight-stationary kernels
+// (sa_conv_ws.hip, sa_conv_wsd.hip).
 #pragma once
 #include "sa_common.h"
 

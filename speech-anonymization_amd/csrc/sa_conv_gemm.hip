@@ -26,23 +26,6 @@
 #include <type_traits>
 #include "sa_common.h"
 
-// -DSA_CONV_STAMPS: diagnostic build (tools/conv_stamps.py) that stamps s_memtime at the phase
-// boundaries of a few workgroups; no stamp exists in the normal build.
-#ifdef SA_CONV_STAMPS
-__device__ unsigned long long sa_conv_dbg[8 * 64];
-#define SA_STAMP_(i, op) do { if (tid == 0 && (blockIdx.x % 97) == 5 && blockIdx.y == 0) { \
-  unsigned long long t_; asm volatile(op " %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-  sa_conv_dbg[(blockIdx.x / 97 % 64) * 8 + (i)] = t_; } } while (0)
-#define SA_STAMP(i) SA_STAMP_(i, "s_memtime")
-#define SA_STAMP_RT(i) SA_STAMP_(i, "s_memrealtime")
-extern "C" int sa_conv_dbg_read(unsigned long long* out) {
-  return -(int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sa_conv_dbg), sizeof(sa_conv_dbg));
-}
-#else
-#define SA_STAMP(i)
-#define SA_STAMP_RT(i)
-#endif      // max (largest - smallest) tap row offset the prologue is sized for
-
 #include "sa_conv_cfg.h"
 
 template <typename T, int CIN, int COUT, int SA, int U, int TM, bool PRO2>
@@ -67,7 +50,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
   const int tile = blockIdx.x, b = blockIdx.y;
   const int m0 = tile * C::BMB;
 
-  SA_STAMP(0);
   // ---------------- prologue: stage + transform the input rows --------------------
   {
     const int c = tid % C::CHI, r0 = tid / C::CHI;
@@ -115,10 +97,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
         k1[j] = a.nb_c1[q]; k2[j] = a.nb_c2[q]; k3[j] = a.nb_c3[q]; csum[j] = 0.0f;
       }
     }
-#ifdef SA_CONV_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SA_STAMP(1);                                      // all row loads have landed
-#endif
     // The transform is selected by kernel arguments, i.e. uniformly: one specialised copy of the
     // staging loop per case (none: data gradients and ConvT forwards, 13 of 22 launches per step;
     // affine + x*sigmoid(x): the encoder / decoder forwards; generic) instead of per-element
@@ -221,7 +199,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
     }
   }
   __syncthreads();
-  SA_STAMP(2);
   // activation cache for sa_wgrad (x_pre): the bf16 (hi) plane of the rows this tile owns -- its
   // base rows, the last tile also the trailing halo -- goes out in 16-byte pieces; the stores
   // drain while the MFMA loop runs
@@ -330,11 +307,9 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
       }
     }
   }
-  SA_STAMP(3);
   constexpr int NOT = TM / C::RPPO;
   const int ec = tid % C::CHO, er0 = tid / C::CHO;
   __syncthreads();                                   // every wave is done reading As
-  SA_STAMP(4);
 
   // ---------------- epilogue: bias/ReLU -> LDS transpose -> coalesced store ------
 #pragma unroll
@@ -357,7 +332,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
     }
   }
   __syncthreads();
-  SA_STAMP(5);
   {
     const int c = ec, r0 = er0;
     float ssum[OVEC], ssq[OVEC], es1[OVEC], et1[OVEC], emu[OVEC], ers[OVEC];
@@ -468,8 +442,6 @@ __global__ __launch_bounds__(256, 2) void sa_conv_gemm_kernel(SaConvArgs a, int 
       }
     }
   }
-  SA_STAMP(6);
-  SA_STAMP_RT(7);
   if (a.stats) {
     __syncthreads();
     if (tid < COUT) {
@@ -549,57 +521,34 @@ static int tile_rows(int cin, int cout, int u) {
   return 64;
 }
 
-// number of (sum, sumsq) partial tiles per utterance the epilogue writes (one-tile-per-workgroup kernel)
+// slabs per utterance of `stats` ([B][ntiles][cout][2]), nb_colsum and pro_stats ([B][ntiles][cin](x2)):
+// one per tile, the same for every kernel sa_conv_gemm routes to
 extern "C" int sa_conv_gemm_ntiles(int cin, int cout, int u, int Lout) {
   const int tm = tile_rows(cin, cout, u);
   return sa_div_up(sa_div_up(Lout, u), tm / u);
 }
 
-// ---- implementation choice: sa_conv_gemm_set_impl(1) routes the f32 and bf16x3 policies to the
-// two-groups-in-anti-phase kernel (sa_conv_pp.hip).  Default 0: on the round-2 measurements
-// (profiles/r02_conv_structure_experiments.md) it ties the one-tile kernel on the forward launches
-// (370 vs 370 us, 128->128, B = 32) and loses on the fused data gradients (614 vs 450 us).
-int sa_conv_pp_dispatch(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a, hipStream_t st);
-int sa_pp_tile_rows(int cin, int cout, int u);
-int sa_pp_share(int cout);
-// Kernel choice.  Default (2): the 128->128 and 64->64 bf16x3 launches the weight-stationary kernel covers
-// (sa_conv_ws.hip: persistent, one wave per SIMD, weights in registers, rows by LDS-DMA, epilogue and
-// transform in the MFMA loop's issue gaps) go there when the launch has at least six tiles per CU (below that the un-overlapped first tiles of
-// every workgroup cost more than the rest gains: B = 4 at the training length loses, B = 6 wins) --
-// 266 / 289 us against 330 / 367 us (plain / forward with cache + statistics), 190 against 265 us for
-// the 3-tap layers, 190 against 255 us for 64->64 (B = 32, profiles/r02_conv_structure_experiments.md);
-// same slab geometry as this file's 64-row tiles, so nothing else changes for the caller.
-// sa_conv_gemm_set_impl(0): this file's kernel only; (1): the ping-pong kernel for f32 / bf16x3.
+// ---- implementation choice: sa_conv_gemm_set_impl(0) or (2).
+// 0: this file's one-tile kernel serves every launch.
+// 2 (default): the 128->128 and 64->64 bf16x3 launches the weight-stationary kernel covers (sa_conv_ws.hip:
+// persistent, one wave per SIMD, weights in registers, rows by LDS-DMA, epilogue and transform in the MFMA
+// loop's issue gaps) go there when the launch has at least six tiles per CU (below that the un-overlapped
+// first tiles of every workgroup cost more than the rest gains: B = 4 at the training length loses, B = 6
+// wins) -- 266 / 289 us against 330 / 367 us (plain / forward with cache + statistics), 190 against 265 us
+// for the 3-tap layers, 190 against 255 us for 64->64 (B = 32, profiles/r02_conv_structure_experiments.md);
+// same slab geometry as this file's tiles, so nothing else changes for the caller.
 bool sa_conv_ws_covers(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a);
 int sa_conv_ws_dispatch(int cin, int cout, const SaConvArgs* a, hipStream_t st);
 int sa_conv_ws_tile_rows(int cout);
 int sa_conv_ws_rows_per_tile(int cout);
-// (3): the fused data gradients 128 -> 128 that sa_conv_wsd.hip covers (normalisation-backward prologue
-// and / or fused backward epilogue) go to that kernel under the same conditions.
+// Under 2 the fused data gradients 128 -> 128 that sa_conv_wsd.hip covers (normalisation-backward prologue
+// and / or fused backward epilogue) go to that kernel under the same conditions (route 3).
 bool sa_conv_wsd_covers(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a);
 int sa_conv_wsd_dispatch(int cin, int cout, const SaConvArgs* a, hipStream_t st);
-static int g_use_pp = 0, g_use_ws = 1;
+static int g_use_ws = 1;
 extern "C" int sa_conv_gemm_set_impl(int impl) {
-  if (impl < 0 || impl > 2) return -22;
-  g_use_pp = impl == 1;
+  if (impl != 0 && impl != 2) return -22;
   g_use_ws = impl == 2;
-  return 0;
-}
-static bool uses_pp(int dtype) { return g_use_pp && (dtype == SA_F32 || dtype == SA_BF16X3); }
-
-// slabs per utterance of nb_colsum / pro_stats ([B][*ntiles][cin](x2)) and of `stats`
-// ([B][*nslabs][cout][2]) of a launch with this dtype code and shape
-extern "C" int sa_conv_gemm_geometry(int dtype, int cin, int cout, int u, int Lout, int* ntiles, int* nslabs) {
-  if (!ntiles || !nslabs || cin <= 0 || cout <= 0 || u <= 0 || Lout <= 0) return -22;
-  if (uses_pp(dtype)) {
-    const int tm = sa_pp_tile_rows(cin, cout, u);
-    const int nt = sa_div_up(sa_div_up(Lout, u), tm / u);
-    *ntiles = nt * 4;                      // nb_colsum / pro_stats: one slab per wave of the tile's group
-    *nslabs = nt * sa_pp_share(cout);
-  } else {
-    *ntiles = sa_conv_gemm_ntiles(cin, cout, u, Lout);
-    *nslabs = *ntiles;
-  }
   return 0;
 }
 
@@ -647,9 +596,9 @@ extern "C" int sa_abi_sizeof(int which) {
   }
 }
 
-// which kernel sa_conv_gemm routes this launch to: 0 one-tile, 1 ping-pong, 2 weight-stationary, 3 weight-stationary fused data gradient
+// which kernel sa_conv_gemm routes this launch to: 0 one-tile, 2 weight-stationary, 3 weight-stationary fused data gradient
+// (1 was a kernel that has been removed; the numbers are kept for stored profiles)
 static int conv_route(int dtype, int cin, int cout, int sa, int u, const SaConvArgs* a) {
-  if (uses_pp(dtype)) return 1;
   if (g_use_ws && sa_conv_ws_covers(dtype, cin, cout, sa, u, a) &&
       tile_rows(cin, cout, u) == sa_conv_ws_tile_rows(cout) &&
       (long)a->B * sa_div_up(a->Lout, sa_conv_ws_rows_per_tile(cout)) >= 1536)
@@ -671,7 +620,6 @@ extern "C" int sa_conv_gemm(int dtype, int cin, int cout, int sa, int u, const S
   if (!a || !a->x || !a->wp || !a->y || a->B <= 0 || a->Lin <= 0 || a->Lout <= 0) return -22;
   if (a->ep_mode < 0 || a->ep_mode > 2 || (a->ep_mode && !a->ep_x)) return -22;
   const int route = conv_route(dtype, cin, cout, sa, u, a);
-  if (route == 1) return sa_conv_pp_dispatch(dtype, cin, cout, sa, u, a, st);
   if (route == 2) return sa_conv_ws_dispatch(cin, cout, a, st);
   if (route == 3) return sa_conv_wsd_dispatch(cin, cout, a, st);
   SA_CONV_CASE(32, 64, 2, 1)

@@ -157,24 +157,23 @@ class PackedWeights:
 
 
 @functools.lru_cache(maxsize=None)
-def _conv_geometry(code, cin, cout, u, Lout):
-    """(row tiles, statistics slabs) per utterance of a launch (cached: kernel choice and tile
-    policy are fixed per process; conv_impl() clears the cache when it switches them)"""
-    nt, ns = C.c_int(0), C.c_int(0)
-    L.check(L.load().sa_conv_gemm_geometry(code, cin, cout, u, Lout, C.byref(nt), C.byref(ns)),
-            "sa_conv_gemm_geometry")
-    return nt.value, ns.value
+def _conv_geometry(cin, cout, u, Lout):
+    """tiles per utterance of a launch = slabs of its stats / pro_stats / colsum outputs (cached: the
+    tile policy is fixed per process; conv_impl() clears the cache when its tile-row knob changes it)"""
+    return L.load().sa_conv_gemm_ntiles(cin, cout, u, Lout)
 
 
-def conv_impl(pingpong=False, tile_rows=0, pp_rows=0, ws=True):
-    """kernel choice for the f32 / bf16x3 policies (A/B timing, kernel tests).  Default: the
-    weight-stationary kernel (sa_conv_ws.hip) for the large 128->128 / 64->64 bf16x3 launches it covers, the
-    one-tile-per-workgroup kernel for everything else; ws=False: one-tile kernel only; pingpong=True:
-    the two-groups-in-anti-phase kernel (sa_conv_pp.hip).  Tile-row knobs of the latter two (0 = policy)."""
+def conv_impl(pingpong=False, tile_rows=0, ws=True):
+    """kernel choice (A/B timing, kernel tests).  Default: the weight-stationary kernels (sa_conv_ws.hip,
+    sa_conv_wsd.hip) for the large bf16x3 launches they cover, the one-tile-per-workgroup kernel for
+    everything else; ws=False: one-tile kernel only.  tile_rows: tile height of the one-tile kernel
+    (0 = policy).  pingpong is accepted only so that a caller asking for the removed kernel is told so."""
+    if pingpong:
+        raise L.SaHipError("the ping-pong conv kernel was removed (it tied the one-tile kernel forward and lost "
+                           "on the fused data gradients: DESIGN.md section 4); use ws=True or ws=False")
     lib = L.load()
-    L.check(lib.sa_conv_gemm_set_impl(1 if pingpong else (2 if ws else 0)), "sa_conv_gemm_set_impl")
+    L.check(lib.sa_conv_gemm_set_impl(2 if ws else 0), "sa_conv_gemm_set_impl")
     L.check(lib.sa_conv_gemm_set_tile_rows(int(tile_rows)), "sa_conv_gemm_set_tile_rows")
-    L.check(lib.sa_conv_pp_set_tile_rows(int(pp_rows)), "sa_conv_pp_set_tile_rows")
     _conv_geometry.cache_clear()
 
 
@@ -193,8 +192,8 @@ def conv_gemm(x, wp, bias, cin, cout, sa, u, phases, Lout, s1=None, t1=None, s2=
     assert x.shape[2] == cin
     y = out if out is not None else torch.empty(B, Lout, cout, dtype=x.dtype, device=x.device)
     kc = L.dt_code(x.dtype) if code is None else code
-    nt, nslab = _conv_geometry(kc, cin, cout, u, Lout)
-    stats = torch.empty(B, nslab, cout, 2, dtype=torch.float32, device=x.device) if want_stats else None
+    nt = _conv_geometry(cin, cout, u, Lout)
+    stats = torch.empty(B, nt, cout, 2, dtype=torch.float32, device=x.device) if want_stats else None
     a = L.SaConvArgs()
     a.x, a.wp, a.bias, a.y = _f(x), _f(wp), _f(bias), _f(y)
     a.s1, a.t1, a.s2, a.t2 = _f(s1), _f(t1), _f(s2), _f(t2)
@@ -245,7 +244,6 @@ def conv_gemm(x, wp, bias, cin, cout, sa, u, phases, Lout, s1=None, t1=None, s2=
         # kernel for the roofline record: same source, same structure, 1 launch per step each)
         kind = (f"sa_conv_wsd_kernel ({tname}, {cin}->{cout}; 5 instances)" if route == 3 else
                 f"sa_conv_ws_kernel<{ws_mode},{ntap}> ({tname}, {cin}->{cout})" if route == 2 else
-                f"sa_conv_pp_kernel<{tname},{cin},{cout},{sa},{u}>" if route == 1 else
                 f"sa_conv_gemm_kernel<{tname},{cin},{cout},{sa},{u}{',nb prologue' if nb else ''}>")
         PROFILE.stop(e0, io + ntap * cin * cout * esz + extra,
                      2 * B * (-(-Lout // u)) * ntap * cin * cout,

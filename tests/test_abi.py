@@ -57,6 +57,30 @@ def test_record_sizes_match_the_library():
     assert lib.sa_abi_sizeof(len(recs)) == -22
 
 
+def test_conv_kernel_choice_and_slab_geometry():
+    """sa_conv_gemm_set_impl takes 0 (one-tile only) and 2 (default); 1 named the removed ping-pong kernel
+    and is -EINVAL, and ops.conv_impl(pingpong=True) says so before it touches the library.  Every launch
+    has one slab geometry: ops sizes stats / pro_stats / colsum with sa_conv_gemm_ntiles."""
+    from speech_anonymization_amd import _lib, ops
+    lib = _lib.load()
+    for bad in (1, -1, 3):
+        assert lib.sa_conv_gemm_set_impl(bad) == -22
+    assert lib.sa_conv_gemm_set_impl(0) == 0
+    a = _lib.SaConvArgs()                    # a large 128->128 bf16x3 forward launch: route 2 under the default
+    a.B, a.Lin, a.Lout, a.taps = 32, 20160, 20160, _lib.make_taps(ops.taps_conv(5, 1, 2))
+    route = lambda: lib.sa_conv_gemm_route(_lib.BF16X3, 128, 128, 1, 1, ctypes.byref(a))
+    assert route() == 0
+    assert lib.sa_conv_gemm_set_impl(2) == 0
+    assert route() == 2
+    with pytest.raises(_lib.SaHipError, match="removed"):
+        ops.conv_impl(pingpong=True, ws=False)
+    assert route() == 2                      # the refused call left the choice alone
+    for cin, cout, u, Lout in [(32, 64, 1, 517), (64, 64, 1, 20001), (128, 128, 1, 20160), (128, 128, 1, 1),
+                               (128, 64, 2, 20001), (64, 32, 2, 517), (64, 128, 1, 64), (64, 128, 1, 65)]:
+        nt = ops._conv_geometry(cin, cout, u, Lout)
+        assert nt == lib.sa_conv_gemm_ntiles(cin, cout, u, Lout) and nt >= 1, (cin, cout, u, Lout)
+
+
 def test_comm_entry_points_before_init():
     """the data-parallel exchange entry points (sa_comm_init / sa_comm_destroy) without a
     communicator: no RCCL, no HIP call is reached -- the codes include/sa_hip.h documents"""

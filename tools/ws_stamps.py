@@ -6,8 +6,14 @@ sys.path.insert(0, R)
 src = os.path.join(R, "speech-anonymization_amd", "csrc")
 so = os.path.join(R, "build", "abl", "libsa_ws_stamps.so")
 if not os.path.exists(so) or os.environ.get("WS_REBUILD"):
+    # the library's own objects, with sa_conv_ws.hip alone recompiled with the stamps (as tools/wsd_stamps.py)
     os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(f"cd {src} && /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -std=c++17 -DSA_WS_STAMPS -shared -o {so} sa_conv_gemm.hip sa_conv_pp.hip sa_conv_ws.hip sa_wgrad.hip sa_small.hip sa_elementwise.hip sa_head.hip sa_fbank.hip sa_mi.hip", shell=True)
+    subprocess.check_call(["make", "-C", src, "-j8"], stdout=subprocess.DEVNULL)
+    o = os.path.join(R, "build", "abl", "ws_stamps.o")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-DSA_WS_STAMPS",
+                           "-c", os.path.join(src, "sa_conv_ws.hip"), "-o", o])
+    objs = [os.path.join(src, x) for x in os.listdir(src) if x.endswith(".o") and x != "sa_conv_ws.o"]
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, o] + objs + ["-ldl"])
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
 import numpy as np
