@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Anonymised speech as audio: a trained anonymiser runs in inference on every utterance and its output features
+are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder).
+
+    python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
+        --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
+
+DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
+normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
+manifest of the recipes (ID, duration, wav, ...; ``$data_root`` in a path is ``--data_folder``).  The path is
+Fbank -> normalise -> reconstruct -> de-normalise -> Mel pseudo-inverse -> Griffin-Lim; OUT receives one 16-bit
+mono 16 kHz WAV per utterance, named by its ID.  ``--passthrough true`` skips the anonymiser and vocodes the
+original features (normalised by the batch's own statistics unless --recon_ckpt names a normaliser): the
+vocoder's own loss, the baseline to compare against.  model_type endtoend also takes
+``--external_classifier_ckpt DIR`` for its frozen in-graph classifier, which never runs here.
+
+The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
+of the waveform against the magnitudes it was made from, the sample count and the peak |wav| before write_audio
+clamps to [-1, 1]."""
+import json
+import os
+import sys
+
+import torch
+
+import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
+from speech_anonymization_amd import data, features, gender, vocoder
+from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
+
+
+def _batches(settings, bs, seed):
+    """(ids, Batch) pairs from the manifest or the synthetic set"""
+    if settings.get("synthetic"):
+        k = 0
+        for batch in data.synthetic_gender_dataset(int(settings["synthetic"]), bs, seed=seed):
+            n = batch.sig[0].shape[0]
+            yield [f"synthetic_{k + i:04d}" for i in range(n)], batch
+            k += n
+    else:
+        ds = data.CsvDataset(settings["csv"], {"data_root": str(settings.get("data_folder", "."))}, "ascending")
+        for batch in data.batches(ds, bs):
+            yield list(batch.id), batch
+
+
+def main(argv):
+    hparams_file, run_opts, overrides = parse_arguments(argv)
+    with open(hparams_file) as fin:
+        settings = load_plain(fin, overrides)
+    vocoder.check_anonymize_options(settings, run_opts)
+    device = torch.device(run_opts.get("device", "cuda:0"))
+    passthrough = bool(settings.get("passthrough"))
+    bs, seed = int(settings.get("batch_size", 3)), int(settings.get("seed", 1986))
+    mt = settings["model_type"]
+    model = norm = None
+    if not passthrough:
+        ext = None
+        if mt == "endtoend" and settings.get("external_classifier_ckpt"):
+            ext = gender.load_external_classifier(settings["external_classifier_ckpt"])
+        model = gender.load_anonymiser(
+            gender.build_anonymiser(mt, settings.get("precision", "bf16x3"), ext, bs), settings["recon_ckpt"])
+        model = model.to(device)
+    if settings.get("recon_ckpt"):
+        norm = gender.load_recon_normalizer(settings["recon_ckpt"])
+    torch.cuda.set_device(device)
+    fbank = features.Fbank(int(settings.get("sample_rate", 16000)), int(settings.get("n_fft", 400)),
+                           int(settings.get("n_mels", 80))).to(device)
+    gl = vocoder.GriffinLim(n_iter=int(settings.get("n_iter", 32)), momentum=float(settings.get("momentum", 0.99)),
+                            seed=seed)
+    pad = 36 if (mt != "fcae" and not passthrough) else None
+    os.makedirs(settings["out_dir"], exist_ok=True)
+    utts = []
+    for ids, batch in _batches(settings, bs, seed):
+        wavs, lens = batch.sig
+        wavs = wavs.to(device)
+        feats = fbank(wavs)
+        T = feats.shape[1]
+        if T < 2:
+            raise SystemExit(f"utterance {ids[0]}: {wavs.shape[1]} samples give {T} frame; the inversion needs 2")
+        nz = norm
+        if nz is None:                                      # passthrough without a checkpoint: the batch's own
+            nz = features.InputNormalization(norm_type="global").to(device).train()
+            normed = nz(feats, lens, epoch=0)
+            nz.eval()
+        else:
+            normed = nz(feats, lens, epoch=1, pad_multiple=pad)
+        recon = normed if passthrough else model.reconstruct(normed)
+        wav, _, S = vocoder.invert_features(recon, nz, lens, frames=T, return_magnitude=True, gl=gl)
+        sc = vocoder.spectral_convergence(wav, S).cpu()
+        wav = wav.cpu()
+        N = wav.shape[1]
+        for i, uid in enumerate(ids):
+            n = int(float(lens[i]) * N)
+            sig = wav[i, :n]
+            utts.append({"id": uid, "spectral_convergence": float(sc[i]), "samples": n,
+                         "peak": float(sig.abs().max()) if n else 0.0})
+            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
+    print(json.dumps({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
+                      "recon_ckpt": settings.get("recon_ckpt"), "n_iter": gl.n_iter, "seed": seed,
+                      "utterances": utts}))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -504,6 +504,26 @@ int sa_specaug_warp_sums(const float* x, const void* plan, int B, int T, int F, 
 int sa_specaug_finalize(const double* part, const void* plan, int B, int T, int F, float* vals, void* stream);
 int sa_specaug_fill(const void* plan, const float* vals, int B, int T, int F, float* out, void* stream);
 
+/* ---- Griffin-Lim inversion of the features (sa_vocoder.hip): normalised log-Mel frames back to
+ * a waveform.  n_fft 400, hop 160, 201 bins, the front end's periodic Hamming window, center=True with zero padding:
+ * T frames <-> N = (T - 1) 160 samples.  Complex spectra are [B][T][201] interleaved (re, im) fp32.  window [400];
+ * twiddle [800] = cos then sin(2 pi i / 400), i = 0..399 (fp64 rounded once; read at (k j) mod 400).
+ *   sa_mel_to_mag: S [B][T][201] = sqrt(max(0, sum_m p_m M[m][k])), p_m = 10^((x[b][t][m] std[m] + mean[m]) / 10);
+ *     x [B][Tf][80], frames t >= T of it are not read; M [80][201] the filterbank's pseudo-inverse.
+ *   sa_gl_istft: y [B][N] = torch.istft(C, center=True, length=N): windowed inverse real DFTs (the imaginary parts of
+ *     bins 0 and 200 do not enter), overlap-added by gathering and divided by the envelope sum_t w^2.
+ *   sa_gl_project: R = STFT(y) (zero padding, center=True); A = R - m Tprev; C_new = S A / (|A| + 1e-16), the update
+ *     in fp64 from the fp32 values, rounded once; R is stored too (the next call's Tprev; C_new, R != Tprev).
+ *   sa_gl_tile: hop blocks of output (sa_gl_istft) and frames (sa_gl_project) per workgroup.
+ *   Grids are (tiles, B).  -EINVAL: a NULL pointer, B < 1 or > 65535 (grid.y), T < 2 (sa_mel_to_mag: T < 1) or
+ *     T > 2^23 (160 T + 400 stays an int), T > Tf. */
+int sa_gl_tile(void);
+int sa_mel_to_mag(const float* x, const float* mean, const float* stdv, const float* M, int B, int T, int Tf,
+                  float* S, void* stream);
+int sa_gl_istft(const void* C, const float* window, const float* twiddle, int B, int T, float* y, void* stream);
+int sa_gl_project(const float* y, const float* S, const void* Tprev, float momentum_ratio, const float* window,
+                  const float* twiddle, int B, int T, void* C_new, void* R, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

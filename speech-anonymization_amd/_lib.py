@@ -119,6 +119,7 @@ SYMBOLS = [
     "sa_fc_wreduce", "sa_fc_recon_fwd",
     "sa_wav_augment_tile", "sa_wav_augment_max_chunks", "sa_wav_abs_sums", "sa_noise_scales", "sa_wav_augment",
     "sa_specaug_warp_sums", "sa_specaug_finalize", "sa_specaug_fill",
+    "sa_gl_tile", "sa_mel_to_mag", "sa_gl_istft", "sa_gl_project",
 ]
 
 _lib = None

@@ -754,9 +754,9 @@ def clip_flats(flats, max_norm, eps=1e-6):
 
 
 # ---- waveform augmentation (csrc/sa_augment.hip; augment.py) ----
-def _aug_in(t, what, dtype=torch.float32, shape=None):
+def _aug_in(t, what, dtype=torch.float32, shape=None, family="augmentation"):
     if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.SaHipError(f"{what}: the augmentation kernels take GPU tensors (no CPU fallback)")
+        raise L.SaHipError(f"{what}: the {family} kernels take GPU tensors (no CPU fallback)")
     if t.dtype != dtype:
         raise L.SaHipError(f"{what}: expected {dtype}, got {t.dtype}")
     if not t.is_contiguous():
@@ -866,3 +866,66 @@ def specaug_fill(out, plan_words, vals):
     _aug_in(vals, "vals", shape=(2,))
     L.check(L.load().sa_specaug_fill(_f(plan_words), _f(vals), B, T, F, _f(out), L.stream()), "sa_specaug_fill")
     return out
+
+
+# ---- Griffin-Lim inversion (csrc/sa_vocoder.hip; vocoder.py) ----
+GL_MAX_B, GL_MAX_T = 65535, 1 << 23        # grid.y; 160 T + 400 stays an int
+
+
+_gl_in = functools.partial(_aug_in, family="vocoder")
+
+
+def _gl_spec(t, what, dtype):
+    if _gl_in(t, what, dtype).dim() != 3 or t.shape[2] != 201:
+        raise L.SaHipError(f"{what}: expected [B, T, 201], got {tuple(t.shape)}")
+    B, T, _ = t.shape
+    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T:
+        raise L.SaHipError(f"{what}: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 2..{GL_MAX_T}")
+    return B, T
+
+
+def _gl_tables(window, twiddle):
+    _gl_in(window, "window", shape=(400,))
+    _gl_in(twiddle, "twiddle", shape=(800,))
+
+
+def mel_to_mag(x, mean, std, M, frames=None):
+    """normalised log-Mel features x [B, Tf, 80] -> linear magnitudes S [B, frames, 201] = sqrt(max(0, p M)),
+    p = 10^((x std + mean) / 10); mean, std [80]; M [80, 201] (vocoder.mel_pinv(), fp32).  frames <= Tf drops
+    padding frames, which are not read."""
+    if _gl_in(x, "x").dim() != 3 or x.shape[2] != 80:
+        raise L.SaHipError(f"x: expected [B, Tf, 80], got {tuple(x.shape)}")
+    B, Tf, _ = x.shape
+    T = Tf if frames is None else int(frames)
+    if B < 1 or B > GL_MAX_B or T < 1 or T > Tf or T > GL_MAX_T:
+        raise L.SaHipError(f"x: [B, Tf] = [{B}, {Tf}], frames = {T} -- B in 1..{GL_MAX_B}, frames in 1..Tf")
+    _gl_in(mean, "mean", shape=(80,))
+    _gl_in(std, "std", shape=(80,))
+    _gl_in(M, "M", shape=(80, 201))
+    S = torch.empty(B, T, 201, dtype=torch.float32, device=x.device)
+    L.check(L.load().sa_mel_to_mag(_f(x), _f(mean), _f(std), _f(M), B, T, Tf, _f(S), L.stream()), "sa_mel_to_mag")
+    return S
+
+
+def gl_istft(C, window, twiddle):
+    """C complex64 [B, T, 201] -> y [B, (T - 1) 160] with the semantics of torch.istft(center=True, length=N);
+    window [400], twiddle [800] (vocoder.tables)"""
+    B, T = _gl_spec(C, "C", torch.complex64)
+    _gl_tables(window, twiddle)
+    y = torch.empty(B, (T - 1) * 160, dtype=torch.float32, device=C.device)
+    L.check(L.load().sa_gl_istft(_f(C), _f(window), _f(twiddle), B, T, _f(y), L.stream()), "sa_gl_istft")
+    return y
+
+
+def gl_project(y, S, Tprev, m, window, twiddle):
+    """one projection and phase update: R = STFT(y), A = R - m Tprev, C_new = S A / (|A| + 1e-16) -> (C_new, R),
+    both complex64 [B, T, 201], new tensors.  y [B, (T - 1) 160]; S fp32 and Tprev complex64 [B, T, 201];
+    m = momentum / (1 + momentum), rounded to fp32."""
+    B, T = _gl_spec(S, "S", torch.float32)
+    _gl_in(Tprev, "Tprev", torch.complex64, (B, T, 201))
+    _gl_in(y, "y", shape=(B, (T - 1) * 160))
+    _gl_tables(window, twiddle)
+    Cn, R = torch.empty_like(Tprev), torch.empty_like(Tprev)
+    L.check(L.load().sa_gl_project(_f(y), _f(S), _f(Tprev), C.c_float(float(m)), _f(window), _f(twiddle), B, T,
+                                   _f(Cn), _f(R), L.stream()), "sa_gl_project")
+    return Cn, R

@@ -1,0 +1,180 @@
+"""Griffin-Lim inversion: normalised 80-bin log-Mel frames -- what the anonymisers'
+``reconstruct`` returns -- back to a 16 kHz waveform, so that anonymised speech can be heard and handed to any
+evaluator that takes audio.  The path: de-normalise -> Mel pseudo-inverse -> fast Griffin-Lim (Perraudin et al.,
+momentum 0.99) on the front end's own STFT (n_fft 400, hop 160, periodic Hamming window, center=True with zero
+padding).  Three kernels of csrc/sa_vocoder.hip, 2 n_iter + 1 launches for the loop and one for the Mel inverse.
+
+The starting phases are drawn on the host from a ``torch.Generator`` the module owns (the project's plan convention:
+no device RNG, nothing copied back).  Tables are made in fp64 and rounded once."""
+import functools
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .features import HOP, N_FFT, NBIN, _hamming, _mel_matrix
+
+N_MELS = 80
+PINV_RCOND = 1e-3
+
+
+def n_samples(T):
+    """samples of T frames (center=True: T = 1 + N // 160, and N is a multiple of the hop)"""
+    T = int(T)
+    if T < 2:
+        raise ValueError(f"the inversion needs at least 2 frames, got {T}")
+    return (T - 1) * HOP
+
+
+@functools.lru_cache(maxsize=None)
+def mel_pinv():
+    """M [80, 201] fp64: the pseudo-inverse of the project's own filterbank fb [201, 80] with singular values under
+    1e-3 of the largest cut (76 of 80 kept; max |M| = 1.37, against 4.5e6 uncut).  Linear power = Mel power @ M.
+    Bins 0 and 200, which no filter covers, are exactly zero.  Cached: do not write to it."""
+    fb = _mel_matrix(N_MELS, N_FFT, 16000)[:NBIN, :N_MELS].double().numpy()
+    M = np.linalg.pinv(fb, rcond=PINV_RCOND)
+    M[:, ~fb.any(axis=1)] = 0.0                      # (already below 1e-17 there)
+    M.setflags(write=False)
+    return M
+
+
+def envelope(T):
+    """E [N + 400] fp64 in padded coordinates: E[p] = sum_t w^2[p - 160 t] over the T frames (what sa_gl_istft
+    divides by; the output sample n sits at p = n + 200)"""
+    N = n_samples(T)
+    w2 = _hamming(N_FFT).astype(np.float64) ** 2
+    E = np.zeros(N + N_FFT)
+    for t in range(int(T)):
+        E[HOP * t:HOP * t + N_FFT] += w2
+    return E
+
+
+@functools.lru_cache(maxsize=None)
+def host_tables():
+    """(window [400], twiddle [800] = cos then sin(2 pi i / 400)) as fp32 CPU tensors, from fp64"""
+    ang = 2.0 * np.pi * np.arange(N_FFT, dtype=np.float64) / N_FFT
+    tw = np.concatenate([np.cos(ang), np.sin(ang)]).astype(np.float32)
+    return torch.from_numpy(_hamming(N_FFT).copy()), torch.from_numpy(tw)
+
+
+_dev = {}
+
+
+def tables(device):
+    """(window, twiddle, M fp32 [80, 201]) on ``device``, made once per device"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.SaHipError("the vocoder runs on the GPU only (no CPU fallback)")
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _dev:
+        w, tw = host_tables()
+        M = torch.from_numpy(mel_pinv().astype(np.float32))
+        _dev[key] = tuple(t.to(device) for t in (w, tw, M))
+    return _dev[key]
+
+
+class GriffinLim(torch.nn.Module):
+    """magnitude S [B, T, 201] (device, fp32) -> wav [B, (T - 1) 160]: C = S e^{i phi}, Tprev = 0, then n_iter
+    times {y = istft(C); R = stft(y); C = S A / (|A| + 1e-16), A = R - m Tprev; Tprev = R}, m = momentum /
+    (1 + momentum), and y = istft(C)."""
+
+    def __init__(self, n_iter=32, momentum=0.99, seed=1986):
+        super().__init__()
+        if int(n_iter) < 0 or not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"GriffinLim: n_iter {n_iter} >= 0 and momentum {momentum} in [0, 1) expected")
+        self.n_iter, self.momentum, self.seed = int(n_iter), float(momentum), int(seed)
+        self.gen = torch.Generator()
+        self.gen.manual_seed(self.seed)
+
+    @property
+    def m(self):
+        return self.momentum / (1.0 + self.momentum)
+
+    def draw_phase(self, shape):
+        """phi uniform on [0, 2 pi), fp32 on the host, from the module's generator"""
+        return torch.rand(tuple(shape), generator=self.gen, dtype=torch.float32) * (2.0 * np.pi)
+
+    @torch.no_grad()
+    def forward(self, S, phase=None):
+        from . import ops
+        if not torch.is_tensor(S) or not S.is_cuda:
+            raise L.SaHipError("GriffinLim runs on the GPU only (no CPU fallback)")
+        w, tw, _ = tables(S.device)
+        phi = self.draw_phase(S.shape) if phase is None else phase
+        Cx = torch.polar(S, phi.to(S.device, non_blocking=True))
+        Tprev = torch.zeros_like(Cx)
+        for _ in range(self.n_iter):
+            y = ops.gl_istft(Cx, w, tw)
+            Cx, Tprev = ops.gl_project(y, S, Tprev, self.m, w, tw)
+        return ops.gl_istft(Cx, w, tw)
+
+
+def stft(wav):
+    """R complex64 [B, T, 201] of wav [B, (T - 1) 160]: sa_gl_project's linear part"""
+    from . import ops
+    B, N = wav.shape
+    if N < HOP or N % HOP:
+        raise L.SaHipError(f"wav: expected [B, N] with N a positive multiple of {HOP}, got {tuple(wav.shape)}")
+    w, tw, _ = tables(wav.device)
+    T = 1 + N // HOP
+    one = torch.ones(B, T, NBIN, dtype=torch.float32, device=wav.device)
+    return ops.gl_project(wav, one, torch.zeros(B, T, NBIN, dtype=torch.complex64, device=wav.device), 0.0, w, tw)[1]
+
+
+@torch.no_grad()
+def spectral_convergence(wav, S):
+    """|| |STFT(wav)| - S ||_F / || S ||_F per utterance -> [B] on the device"""
+    mag = stft(wav).abs().double()
+    return (((mag - S.double()) ** 2).sum(dim=(1, 2)).sqrt() / (S.double() ** 2).sum(dim=(1, 2)).sqrt()).float()
+
+
+@torch.no_grad()
+def invert_features(feats, normalizer, lens=None, frames=None, return_magnitude=False, **gl):
+    """normalised features [B, Tf, 80] (device) -> (wav [B, N], lens): de-normalised with ``normalizer``'s state
+    (features.InputNormalization: x std + mean), the first ``frames`` frames kept (the ConvAE pads Tf to a multiple
+    of 36), N = (frames - 1) 160.  lens: relative lengths [B] (default ones), returned so that int(lens N) trims
+    each row.  gl: GriffinLim's arguments, or gl=<a GriffinLim> to keep one generator across calls."""
+    from . import ops
+    if not torch.is_tensor(feats) or not feats.is_cuda:
+        raise L.SaHipError("invert_features runs on the GPU only (no CPU fallback)")
+    if not getattr(normalizer, "_count_positive", False) and normalizer.count <= 0:
+        raise L.SaHipError("invert_features: the normaliser has seen no data (count == 0): its mean and std say "
+                           "nothing about the features")
+    if normalizer.state.device != feats.device:
+        normalizer.to(feats.device)
+    T = feats.shape[1] if frames is None else int(frames)
+    n_samples(T)
+    _, _, M = tables(feats.device)
+    S = ops.mel_to_mag(feats.float().contiguous(), normalizer.glob_mean.contiguous(),
+                       normalizer.glob_std.contiguous(), M, T)
+    vocoder = gl.pop("gl", None) or GriffinLim(**gl)
+    wav = vocoder(S)
+    lens = torch.ones(feats.shape[0]) if lens is None else lens
+    return (wav, lens, S) if return_magnitude else (wav, lens)
+
+
+ANON_MODEL_TYPES = ("convae", "fcae", "endtoend")
+
+
+def check_anonymize_options(settings, run_opts, environ=None):
+    """what anonymize.py refuses before anything touches a GPU, one line each"""
+    import os
+    environ = os.environ if environ is None else environ
+    mt = settings.get("model_type")
+    if mt not in ANON_MODEL_TYPES:
+        raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
+    if not settings.get("passthrough") and not settings.get("recon_ckpt"):
+        raise SystemExit("--recon_ckpt DIR is required without --passthrough true: a CKPT+* directory of "
+                         "speechbrain_convae_train.py (model.ckpt, normalizer.ckpt)")
+    if not settings.get("out_dir"):
+        raise SystemExit("--out_dir OUT is required: the folder the WAV files go to")
+    if settings.get("csv") and settings.get("synthetic"):
+        raise SystemExit("--csv FILE and --synthetic N exclude each other")
+    if not settings.get("csv") and not settings.get("synthetic"):
+        raise SystemExit("one of --csv FILE and --synthetic N is required")
+    if int(settings.get("n_iter", 32)) < 0:
+        raise SystemExit(f"--n_iter {settings.get('n_iter')}: a count of iterations, 0 or more")
+    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("anonymize runs on one GPU: data parallelism is not implemented for it")
+    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
+        raise SystemExit("anonymize does not support --hip_graph")

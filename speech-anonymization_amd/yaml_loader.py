@@ -183,6 +183,27 @@ def load_hyperpyyaml(stream, overrides=None):
     return {k: done[k] for k in raw}
 
 
+def load_plain(stream, overrides=None):
+    """the file's plain top-level values (numbers, strings, lists, mappings of them) overlaid with ``overrides``;
+    entries that construct or reference something are left out and nothing is constructed -- for scripts that
+    need the settings of a recipe's YAML but none of its objects (anonymize.py)"""
+    text = stream.read() if hasattr(stream, "read") else stream
+    raw = yaml.load(text, Loader=_Loader)
+
+    def plain(v):
+        if isinstance(v, (_Ref, _Tagged)):
+            return False
+        if isinstance(v, dict):
+            return all(plain(x) for x in v.values())
+        if isinstance(v, list):
+            return all(plain(x) for x in v)
+        return True
+
+    out = {k: _literal(v) for k, v in raw.items() if plain(v)}
+    out.update(overrides or {})
+    return out
+
+
 def parse_arguments(argv):
     """sb.parse_arguments: positional yaml file, run options, and arbitrary --key value overrides."""
     run_keys = {"device", "distributed_launch", "distributed_backend", "max_grad_norm",
