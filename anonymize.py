@@ -14,9 +14,14 @@ original features (normalised by the batch's own statistics unless --recon_ckpt 
 vocoder's own loss, the baseline to compare against.  model_type endtoend also takes
 ``--external_classifier_ckpt DIR`` for its frozen in-graph classifier, which never runs here.
 
+``--pitch_norm true [--pitch_target_hz 170]`` runs no model at all: OUT receives the pitch-normalised waveforms
+(speech_anonymization_amd.pitchnorm), the signal-processing baseline; it takes neither
+--recon_ckpt nor --passthrough.  ``--report_f0 true`` adds, in any mode, the mean voiced F0 (``f0_mean_hz``) and the
+share of voiced frames (``voiced_share``) of every waveform written.
+
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
-of the waveform against the magnitudes it was made from, the sample count and the peak |wav| before write_audio
-clamps to [-1, 1]."""
+of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
+sample count and the peak |wav| before write_audio clamps to [-1, 1]."""
 import json
 import os
 import sys
@@ -24,7 +29,7 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, features, gender, vocoder
+from speech_anonymization_amd import data, features, gender, pitchnorm, vocoder
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -42,6 +47,41 @@ def _batches(settings, bs, seed):
             yield list(batch.id), batch
 
 
+def _f0_report(wav, lens):
+    """(mean voiced F0 in Hz, voiced share) per row of wav [B, N] on the device, over the frames of round(lens N)
+    samples"""
+    from speech_anonymization_amd import ops
+    N = wav.shape[1]
+    lens = lens.to(wav.device, torch.float32).contiguous()
+    _, mean, voiced = ops.pitch_ratio(pitchnorm.f0_track(wav.contiguous()), lens, N)
+    frames = (torch.round(lens.double() * N).long() // features.HOP + 1).clamp(max=N // features.HOP + 1)
+    return mean.cpu().tolist(), (voiced.double() / frames.double()).cpu().tolist()
+
+
+def _pitch_norm(settings, device, bs, seed):
+    """--pitch_norm true: every utterance pitch-normalised and written, no model and no features"""
+    pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
+                                   n_iter=int(settings.get("n_iter", 32)),
+                                   momentum=float(settings.get("momentum", 0.99)), seed=seed)
+    utts = []
+    for ids, batch in _batches(settings, bs, seed):
+        wavs, lens = batch.sig
+        out = pn(wavs.to(device).contiguous(), lens)
+        rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        ratio = pn.last[0].cpu().tolist()
+        out = out.cpu()
+        N = out.shape[1]
+        for i, uid in enumerate(ids):
+            n = int(round(float(lens[i]) * N))
+            sig = out[i, :n]
+            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0, "ratio": ratio[i]})
+            if rep:
+                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
+    print(json.dumps({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
+                      "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}))
+
+
 def main(argv):
     hparams_file, run_opts, overrides = parse_arguments(argv)
     with open(hparams_file) as fin:
@@ -50,6 +90,10 @@ def main(argv):
     device = torch.device(run_opts.get("device", "cuda:0"))
     passthrough = bool(settings.get("passthrough"))
     bs, seed = int(settings.get("batch_size", 3)), int(settings.get("seed", 1986))
+    if settings.get("pitch_norm"):
+        torch.cuda.set_device(device)
+        os.makedirs(settings["out_dir"], exist_ok=True)
+        return _pitch_norm(settings, device, bs, seed)
     mt = settings["model_type"]
     model = norm = None
     if not passthrough:
@@ -86,6 +130,7 @@ def main(argv):
         recon = normed if passthrough else model.reconstruct(normed)
         wav, _, S = vocoder.invert_features(recon, nz, lens, frames=T, return_magnitude=True, gl=gl)
         sc = vocoder.spectral_convergence(wav, S).cpu()
+        rep = _f0_report(wav, lens) if settings.get("report_f0") else None
         wav = wav.cpu()
         N = wav.shape[1]
         for i, uid in enumerate(ids):
@@ -93,6 +138,8 @@ def main(argv):
             sig = wav[i, :n]
             utts.append({"id": uid, "spectral_convergence": float(sc[i]), "samples": n,
                          "peak": float(sig.abs().max()) if n else 0.0})
+            if rep:
+                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
                       "recon_ckpt": settings.get("recon_ckpt"), "n_iter": gl.n_iter, "seed": seed,

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Trains the x-vector gender classifier on PITCH-NORMALISED waveforms (the reference's
+gender_classifier_train_pitch_norm.py, its signal-processing baseline): every waveform, at train, valid and test
+alike, has its voiced F0 scaled to a mean of ``pitch_target_hz`` before the classifier's front end sees it
+(speech_anonymization_amd.pitchnorm).  Its test error answers "how much of sex does a classifier
+still recover once the mean pitch is gone?" -- the number the learned anonymisers are compared against.
+
+    python gender_classifier_train_pitch_norm.py speechbrain_configs/gender_classifier_pitch_norm.yaml \
+        --device cuda:0 [--pitch_target_hz 170] [--synthetic N] [--key value ...]
+
+Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
+summary as the last line (with pitch_target_hz added)."""
+import json
+import os
+import sys
+
+import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
+from speech_anonymization_amd import data, gender, pitchnorm
+from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
+
+
+def main(argv):
+    hparams_file, run_opts, overrides = parse_arguments(argv)
+    synthetic = overrides.pop("synthetic", None)
+    with open(hparams_file) as fin:
+        settings = load_hyperpyyaml(fin, overrides)
+    pn = pitchnorm.check_pitch_options(settings, run_opts)
+    os.makedirs(settings["output_folder"], exist_ok=True)
+    print(gender.augment_notice("gender_classifier_train_pitch_norm", settings))
+    hparams = dict(settings, **gender.build(settings))
+    hparams["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pn)
+    run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
+    brain = gender.GenderPitchNormBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,
+                                        run_opts=run_opts, checkpointer=hparams["checkpointer"])
+    bs, seed = int(hparams["batch_size"]), int(hparams["seed"])
+    counter = hparams["epoch_counter"]
+    if synthetic:
+        n = int(synthetic)
+        held = max(bs, n // 4)
+        make = lambda k, s, ep=0: data.synthetic_gender_dataset(k, bs, seed=s + ep)
+        train = lambda epoch: make(n, seed, 1000 * epoch)
+        valid = lambda epoch: make(held, seed + 1)
+        test = lambda: make(held, seed + 2)
+    else:
+        rep = {"data_root": hparams["data_folder"]}
+        csv = {k: os.path.join(hparams["data_folder"], v) for k, v in hparams["manifests"].items()}
+        tr = data.CsvDataset(csv["train"], rep)
+        va = data.CsvDataset(csv["valid"], rep, "ascending")
+        te = data.CsvDataset(csv["test"], rep, "ascending")
+        train = lambda epoch: data.batches(tr, bs, bool(hparams.get("shuffle", True)), seed, epoch=epoch)
+        valid = lambda epoch: data.batches(va, bs)
+        test = lambda: data.batches(te, bs)
+
+    class Loader:
+        def __init__(self, f):
+            self.f = f
+
+        def __iter__(self):
+            return iter(self.f(max(1, int(counter.current))))
+
+    brain.fit(counter, Loader(train), Loader(valid))
+    brain.evaluate(test(), min_key="error")
+    print(json.dumps({"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
+                      "best_checkpoint": getattr(brain, "best_checkpoint", None),
+                      "pitch_target_hz": pn["target_hz"]}))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

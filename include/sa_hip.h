@@ -524,6 +524,37 @@ int sa_gl_istft(const void* C, const float* window, const float* twiddle, int B,
 int sa_gl_project(const float* y, const float* S, const void* Tprev, float momentum_ratio, const float* window,
                   const float* twiddle, int B, int T, void* C_new, void* R, void* stream);
 
+/* ---- pitch normalisation (sa_pitch.hip): an F0 tracker and the passes that, around
+ * sa_gl_istft / sa_gl_project, scale a waveform's pitch by a per-utterance ratio.  16 kHz, hop 160.
+ *   sa_yin_dim(which): 0 sample rate 16000, 1 hop 160, 2 W 400, 3 tau_min 40, 4 tau_max 266, 5 L = W + tau_max
+ *     666, 6 frames per workgroup of sa_yin_f0, 7 outputs per workgroup of sa_pitch_resample; else -EINVAL.
+ *   sa_yin_f0: wav [B][N] -> f0 [B][T] in Hz (0: unvoiced), T = N / 160 + 1.  Frame t reads x[j] =
+ *     wav[160 t - 333 + j], j < L, zeros outside [0, N); d(tau) = sum_{j < W} (x[j] - x[j + tau])^2 summed as
+ *     written; d'(tau) = d(tau) tau / sum_{i <= tau} d(i) (1 where the sum is 0; d'(0) = 1); the pick is the
+ *     smallest tau in [tau_min, tau_max - 1] with d' < threshold, d'(tau) <= d'(tau - 1), d'(tau) < d'(tau + 1),
+ *     refined by the parabola through its neighbours (fp64 from the fp32 d', rounded once); no pick: 0.
+ *     dprime: NULL, or [B][T][tau_max + 1] to receive d' (tests).
+ *   sa_pitch_ratio: over the first round(lens_b N) / 160 + 1 (at most T) frames of row b: voiced_b = the count
+ *     of f0 > 0, mean_b their mean (fp64, fixed order; 0 without any), ratio_b = clamp(target / mean_b, r_min,
+ *     r_max) if voiced_b >= min_voiced, else 1.
+ *   sa_pitch_stretch_mag: R complex [B][T][201] -> S [B][Tout][201]: for t' < T'_b = ceil((T - 1) r_b) + 1,
+ *     (1 - a) |R[i]| + a |R[i + 1]| at pos = min(t' / r_b, T - 1) (fp64), i = min(floor(pos), T - 2), a = pos - i;
+ *     0 from T'_b on.  Tout is the caller's max_b T'_b (a smaller one truncates).
+ *   sa_pitch_resample: y [B][Nin] -> out [B][Nout]: out[n] = sum_i y[i] h(n r_b - i) for n < n_valid[b], else 0;
+ *     h(u) = c sinc(c u) (0.5 + 0.5 cos(pi u / H)) on |u| < H, c = min(1, 1 / r_b), H = 16 / c (at most 64 taps;
+ *     position and weights in fp64, weights rounded once, fp32 accumulation).  Row b's input ends at
+ *     min(Nin, 160 ceil(ceil(Nout / 160) r_b)) samples -- (T'_b - 1) 160 of a waveform of Nout samples.
+ *   The ratios are read on the device: a value outside [0.5, 2] is taken as the nearer bound, a NaN as 1.
+ *   -EINVAL: a NULL pointer (dprime may be NULL), B < 1 or > 65535 (grid.y), N, Nin < 1 or > 2^30, Nout < 1 or
+ *     > 2^29, T < 1 (stretch: < 2) or T, Tout > 2^23, target <= 0, r_min < 0.5, r_max > 2, r_min > r_max. */
+int sa_yin_dim(int which);
+int sa_yin_f0(const float* wav, int B, int N, float threshold, float* f0, float* dprime, void* stream);
+int sa_pitch_ratio(const float* f0, const float* lens, int B, int T, int N, float target, float r_min, float r_max,
+                   int min_voiced, float* ratio, float* mean, int* voiced, void* stream);
+int sa_pitch_stretch_mag(const void* R, const float* ratio, int B, int T, int Tout, float* S, void* stream);
+int sa_pitch_resample(const float* y, const float* ratio, const int* n_valid, int B, int Nin, int Nout, float* out,
+                      void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -18,7 +18,8 @@ noise rows in place of EnvCorrupt's OpenRIR noise, and TimeDomainSpecAugment, at
 default -- the recipe trains without it.
 
 The second half of the module is the same recipe on RECONSTRUCTED features (the reference's
-gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser)."""
+gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser), and at its end the
+recipe on PITCH-NORMALISED waveforms (gender_classifier_train_pitch_norm.py; GenderPitchNormBrain)."""
 import functools
 import os
 
@@ -330,3 +331,16 @@ class GenderReconBrain(GenderBrain):
             super().init_optimizers()
         finally:
             self.modules["model"] = model
+
+
+# ---------------------------------------------------------------------------------------------------
+# the same recipe on pitch-normalised waveforms (the reference's gender_classifier_train_pitch_norm.py)
+# ---------------------------------------------------------------------------------------------------
+class GenderPitchNormBrain(GenderBrain):
+    """gender_classifier_train_pitch_norm.py: the reference's ``audio_pipeline`` pitch-normalises every waveform
+    it loads, for train, valid and test alike, so ``hparams.pitch_normalizer`` (pitchnorm.PitchNormalizer; DESIGN
+    section 15) runs at every stage, before augmentation and features.  Shapes and lengths are kept, so the rest
+    of the recipe is GenderBrain's."""
+
+    def prepare_features(self, wavs, lens, stage):
+        return super().prepare_features(self.hparams.pitch_normalizer(wavs, lens), lens, stage)

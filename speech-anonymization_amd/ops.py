@@ -929,3 +929,77 @@ def gl_project(y, S, Tprev, m, window, twiddle):
     L.check(L.load().sa_gl_project(_f(y), _f(S), _f(Tprev), C.c_float(float(m)), _f(window), _f(twiddle), B, T,
                                    _f(Cn), _f(R), L.stream()), "sa_gl_project")
     return Cn, R
+
+
+# ---- pitch normalisation (csrc/sa_pitch.hip; pitchnorm.py) ----
+YIN_HOP, YIN_TMAX = 160, 266
+PN_MAX_N = 1 << 30
+
+_pn_in = functools.partial(_aug_in, family="pitch")
+
+
+def _pn_rows(t, what, dtype=torch.float32):
+    if _pn_in(t, what, dtype).dim() != 2 or t.numel() == 0:
+        raise L.SaHipError(f"{what}: expected [B, N] with B, N >= 1, got {tuple(t.shape)}")
+    B, N = t.shape
+    if B > GL_MAX_B or N > PN_MAX_N:
+        raise L.SaHipError(f"{what}: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
+    return B, N
+
+
+def yin_f0(wav, threshold=0.15, return_dprime=False):
+    """wav [B, N] -> f0 [B, N // 160 + 1] in Hz, 0 where unvoiced (sa_yin_f0).  return_dprime: also the cumulative
+    mean normalised difference d' [B, T, 267] the decision was made on (tests)."""
+    B, N = _pn_rows(wav, "wav")
+    T = N // YIN_HOP + 1
+    f0 = torch.empty(B, T, dtype=torch.float32, device=wav.device)
+    dp = torch.empty(B, T, YIN_TMAX + 1, dtype=torch.float32, device=wav.device) if return_dprime else None
+    L.check(L.load().sa_yin_f0(_f(wav), B, N, C.c_float(float(threshold)), _f(f0), _f(dp), L.stream()), "sa_yin_f0")
+    return (f0, dp) if return_dprime else f0
+
+
+def pitch_ratio(f0, lens, N, target_hz=170.0, r_min=0.5, r_max=2.0, min_voiced=5):
+    """f0 [B, T], relative lengths lens [B] (fp32, device), N samples per row -> (ratio fp32 [B], mean fp32 [B],
+    voiced int32 [B]): clamp(target / mean voiced f0) over the frames of round(lens N) samples, 1 under min_voiced"""
+    B, T = _pn_rows(f0, "f0")
+    _pn_in(lens, "lens", shape=(B,))
+    N = int(N)
+    if N < 1 or N > PN_MAX_N or T > GL_MAX_T:
+        raise L.SaHipError(f"pitch_ratio: N = {N} in 1..{PN_MAX_N} and T = {T} up to {GL_MAX_T} expected")
+    if not (float(target_hz) > 0.0 and 0.5 <= float(r_min) <= float(r_max) <= 2.0):
+        raise L.SaHipError(f"pitch_ratio: target {target_hz} > 0 and 0.5 <= r_min {r_min} <= r_max {r_max} <= 2 expected")
+    ratio = torch.empty(B, dtype=torch.float32, device=f0.device)
+    mean = torch.empty(B, dtype=torch.float32, device=f0.device)
+    voiced = torch.empty(B, dtype=torch.int32, device=f0.device)
+    L.check(L.load().sa_pitch_ratio(_f(f0), _f(lens), B, T, N, C.c_float(float(target_hz)), C.c_float(float(r_min)),
+                                    C.c_float(float(r_max)), int(min_voiced), _f(ratio), _f(mean), _f(voiced),
+                                    L.stream()), "sa_pitch_ratio")
+    return ratio, mean, voiced
+
+
+def pitch_stretch_mag(R, ratio, Tout):
+    """R complex64 [B, T, 201], ratio fp32 [B] -> S fp32 [B, Tout, 201]: |R| read at t' / r_b between its frames for
+    t' < ceil((T - 1) r_b) + 1, zero from there on"""
+    B, T = _gl_spec(R, "R", torch.complex64)
+    _pn_in(ratio, "ratio", shape=(B,))
+    Tout = int(Tout)
+    if Tout < 1 or Tout > GL_MAX_T:
+        raise L.SaHipError(f"pitch_stretch_mag: Tout = {Tout} in 1..{GL_MAX_T} expected")
+    S = torch.empty(B, Tout, 201, dtype=torch.float32, device=R.device)
+    L.check(L.load().sa_pitch_stretch_mag(_f(R), _f(ratio), B, T, Tout, _f(S), L.stream()), "sa_pitch_stretch_mag")
+    return S
+
+
+def pitch_resample(y, ratio, n_valid, Nout):
+    """y [B, Nin], ratio fp32 [B], n_valid int32 [B] -> out [B, Nout]: the windowed-sinc read of y at n r_b for
+    n < n_valid_b, zero from there on (sa_pitch_resample)"""
+    B, Nin = _pn_rows(y, "y")
+    _pn_in(ratio, "ratio", shape=(B,))
+    _pn_in(n_valid, "n_valid", torch.int32, (B,))
+    Nout = int(Nout)
+    if Nout < 1 or Nout > PN_MAX_N // 2:
+        raise L.SaHipError(f"pitch_resample: Nout = {Nout} in 1..{PN_MAX_N // 2} expected")
+    out = torch.empty(B, Nout, dtype=torch.float32, device=y.device)
+    L.check(L.load().sa_pitch_resample(_f(y), _f(ratio), _f(n_valid), B, Nin, Nout, _f(out), L.stream()),
+            "sa_pitch_resample")
+    return out

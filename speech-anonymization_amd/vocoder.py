@@ -161,9 +161,18 @@ def check_anonymize_options(settings, run_opts, environ=None):
     import os
     environ = os.environ if environ is None else environ
     mt = settings.get("model_type")
-    if mt not in ANON_MODEL_TYPES:
+    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm"):   # (pitch normalisation runs no model)
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
-    if not settings.get("passthrough") and not settings.get("recon_ckpt"):
+    if settings.get("pitch_norm"):
+        if settings.get("passthrough"):
+            raise SystemExit("--pitch_norm true and --passthrough true exclude each other: one writes the "
+                             "pitch-normalised waveforms, the other the vocoded originals")
+        if settings.get("recon_ckpt"):
+            raise SystemExit("--pitch_norm true takes no --recon_ckpt: no anonymiser runs, the waveforms are "
+                             "pitch-normalised")
+        from .pitchnorm import check_pitch_target
+        check_pitch_target(settings.get("pitch_target_hz", 170.0))
+    elif not settings.get("passthrough") and not settings.get("recon_ckpt"):
         raise SystemExit("--recon_ckpt DIR is required without --passthrough true: a CKPT+* directory of "
                          "speechbrain_convae_train.py (model.ckpt, normalizer.ckpt)")
     if not settings.get("out_dir"):
