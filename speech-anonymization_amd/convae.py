@@ -24,9 +24,6 @@ from . import ops
 from . import _lib as L
 from ._lib import SaHipError
 
-K5 = 5
-CONVT_WG_TAPS = [(1, 0), (1, 1), (0, 0), (0, 1), (-1, 0)]      # (input row offset, output phase) per tap
-
 
 class _ParamOnly(nn.Module):
     """activation placeholders keep the Sequential indices of the reference."""
@@ -94,6 +91,12 @@ class ConvAutoencoder(nn.Module):
             nn.Conv1d(32, 1, 15, 1, 7),
         )
         self.sex_classifier = TDNNSexClassifier(2)
+        # every conv_gemm layer's launch geometry, derived from the containers above
+        self.lay = ops.conv_layers(self, ("encoder", "sex_classifier.tdnn", "decoder"))
+        # every (weight, use) pair the fused forward / backward multiplies with: the forward images, Conv1d before
+        # ConvTranspose1d, then the data-gradient images in the same order
+        self.pack_plan = [(ly.key, ly.kinds[i]) for i in (0, 1)
+                          for ly in sorted(self.lay.values(), key=lambda ly: ly.transposed)]
         self.act_dtype, self.kcode = ops.PRECISIONS[precision]
         # kernel precision of the data-gradient convolutions (tools/precision_probe.py overrides it)
         self.dgrad_kcode = ops.DGRAD_CODE[precision]
@@ -153,11 +156,9 @@ class ConvAutoencoder(nn.Module):
             raise SaHipError("ConvAutoencoder expects feats [B, T, 80]")
         x0, B, T, Ltot = _input_rows(feats)
         P = dict(zip(*self._named_params()))
-        W = _packed(self, P)
-        pw = lambda k, kind: W[(k, kind)]
-        cg, inorm = _launchers(self, P, B)
-        y, _, _ = _encoder_launches(self, P, pw, cg, inorm, x0, Ltot, False)
-        return _decoder_launches(P, pw, cg, inorm, y[5], Ltot)[-1].view(B, T, 80)
+        cg, inorm = _launchers(self, P, _packed(self, P), B)
+        y, _, _ = _encoder_launches(self, P, cg, inorm, x0, Ltot, False)
+        return _decoder_launches(self, P, cg, inorm, y[5], Ltot)[-1].view(B, T, 80)
 
     def _side_stream(self, device):
         if getattr(self, "_side", None) is None and device.type == "cuda":
@@ -241,21 +242,7 @@ class _W:
         self.img, self.code = img, code
 
 
-# every (weight, use) pair the fused forward / backward multiplies with
-PACK_PLAN = (
-    [(k, "conv_fwd") for k in ("encoder.2.weight", "encoder.5.weight", "encoder.8.weight",
-                               "encoder.11.weight", "sex_classifier.tdnn.0.weight",
-                               "sex_classifier.tdnn.3.weight", "sex_classifier.tdnn.6.weight",
-                               "decoder.0.weight", "decoder.4.weight")]
-    + [(k, "convT_fwd") for k in ("decoder.1.weight", "decoder.5.weight")]
-    + [(k, "conv_dgrad") for k in ("encoder.2.weight", "encoder.5.weight", "encoder.8.weight",
-                                   "encoder.11.weight", "sex_classifier.tdnn.0.weight",
-                                   "sex_classifier.tdnn.3.weight", "sex_classifier.tdnn.6.weight",
-                                   "decoder.0.weight", "decoder.4.weight")]
-    + [(k, "convT_dgrad") for k in ("decoder.1.weight", "decoder.5.weight")])
-
-
-def _kcode(model, key, kind):
+def _kcode(model, kind):
     return model.dgrad_kcode if kind.endswith("dgrad") else model.kcode
 
 
@@ -264,7 +251,7 @@ def _packed(model, P):
     are persistent (keyed by the parameters' storage): a backward uses the images its forward
     packed, which is what autograd's saved-tensor semantics ask for as long as the weights are
     not modified between the two."""
-    items = [((k, kind), P[k], kind, _kcode(model, k, kind)) for k, kind in PACK_PLAN]
+    items = [((k, kind), P[k], kind, _kcode(model, kind)) for k, kind in model.pack_plan]
     key = tuple(w.data_ptr() for _, w, _, _ in items) + tuple(c for _, _, _, c in items)
     pk = getattr(model, "_pack_cache", None)
     if pk is None or pk[0] != key:
@@ -310,13 +297,23 @@ def _input_rows(feats):
     return feats.detach().reshape(B, Ltot).contiguous().float(), B, T, Ltot
 
 
-def _launchers(model, P, B, A=None):
-    """(cg, inorm): a convolution launch and an InstanceNorm finaliser as forward and reconstruct issue them.
-    A: dict that receives the bf16 operand cache of the weight gradients (None: no cache)."""
-    def cg(x, w, key, *args, **kw):
-        if A is not None and key is not None and P[key].requires_grad:
-            A[key] = kw["a_out"] = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        return _conv(x, w, *args, **kw)
+def _in_ep(y, nrm, g2=None):
+    """fused-epilogue description of an [InstanceNorm -> swish] backward (stats pass)."""
+    mean, rstd, scale, shift = nrm
+    d = dict(mode=1, x=y, g2=g2, s1=scale, t1=shift, mean=mean, rstd=rstd)
+    if isinstance(g2, _PendingApply):                     # apply of the `norm` BatchNorm rides along
+        d.update(g2=g2.g, g2k=g2.c)
+    return d
+
+
+def _launchers(model, P, W, B, A=None):
+    """(cg, inorm): a layer's forward launch and an InstanceNorm finaliser as forward and reconstruct issue them.
+    W: the packed images (_packed).  A: dict that receives the bf16 operand cache of the weight gradients (None:
+    no cache)."""
+    def cg(ly, x, **kw):
+        if A is not None and P[ly.key].requires_grad:
+            A[ly.key] = kw["a_out"] = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        return _conv(x, W[ly.key, ly.kinds[0]], P[ly.bias], *ly.fwd(x.shape[1]), **kw)
 
     def inorm(stats, n, prefix, C):
         sums = ops.sum_partials(stats, B)
@@ -324,42 +321,34 @@ def _launchers(model, P, B, A=None):
     return cg, inorm
 
 
-def _encoder_launches(model, P, pw, cg, inorm, x0, Ltot, want_pro_stats):
+def _encoder_launches(model, P, cg, inorm, x0, Ltot, want_pro_stats):
     """encoder + decoder.0 -> ([y0..y5], [n1..n4], a4_stats or None).  decoder.0 belongs here: it stages the
     transformed encoder output, and in train mode leaves the statistics the classifier's input BatchNorm
     needs as a by-product of its prologue (want_pro_stats)."""
-    L2, L4 = Ltot // 2, Ltot // 4
+    L2, L4, lay = Ltot // 2, Ltot // 4, model.lay
     y0 = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], model.act_dtype)
-    y1, st = cg(y0, pw("encoder.2.weight", "conv_fwd"), "encoder.2.weight", P["encoder.2.bias"], 32, 64, 2, 1,
-                ops.taps_conv(K5, 1, 2), L2, swish=True, want_stats=True)
+    y1, st = cg(lay["encoder.2"], y0, swish=True, want_stats=True)
     n1 = inorm(st, L2, "encoder.3", 64)
-    y2, st = cg(y1, pw("encoder.5.weight", "conv_fwd"), "encoder.5.weight", P["encoder.5.bias"], 64, 64, 1, 1,
-                ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True)
+    y2, st = cg(lay["encoder.5"], y1, s1=n1[2], t1=n1[3], swish=True, want_stats=True)
     n2 = inorm(st, L2, "encoder.6", 64)
-    y3, st = cg(y2, pw("encoder.8.weight", "conv_fwd"), "encoder.8.weight", P["encoder.8.bias"], 64, 128, 2, 1,
-                ops.taps_conv(K5, 1, 2), L4, s1=n2[2], t1=n2[3], swish=True, want_stats=True)
+    y3, st = cg(lay["encoder.8"], y2, s1=n2[2], t1=n2[3], swish=True, want_stats=True)
     n3 = inorm(st, L4, "encoder.9", 128)
-    y4, st = cg(y3, pw("encoder.11.weight", "conv_fwd"), "encoder.11.weight", P["encoder.11.bias"], 128, 128, 1, 1,
-                ops.taps_conv(K5, 1, 2), L4, s1=n3[2], t1=n3[3], swish=True, want_stats=True)
+    y4, st = cg(lay["encoder.11"], y3, s1=n3[2], t1=n3[3], swish=True, want_stats=True)
     n4 = inorm(st, L4, "encoder.12", 128)
-    y5 = cg(y4, pw("decoder.0.weight", "conv_fwd"), "decoder.0.weight", P["decoder.0.bias"], 128, 128, 1, 1,
-            ops.taps_conv(K5, 1, 2), L4, s1=n4[2], t1=n4[3], swish=True, want_pro_stats=want_pro_stats)
+    y5 = cg(lay["decoder.0"], y4, s1=n4[2], t1=n4[3], swish=True, want_pro_stats=want_pro_stats)
     a4_stats = None
     if want_pro_stats:
         y5, a4_stats = y5
     return [y0, y1, y2, y3, y4, y5], [n1, n2, n3, n4], a4_stats
 
 
-def _decoder_launches(P, pw, cg, inorm, y5, Ltot):
+def _decoder_launches(model, P, cg, inorm, y5, Ltot):
     """decoder.1 ... decoder.8 -> (y6, n6, y7, y8, n8, recon [B, Ltot])"""
-    L2 = Ltot // 2
-    y6, st = cg(y5, pw("decoder.1.weight", "convT_fwd"), "decoder.1.weight", P["decoder.1.bias"], 128, 64, 1, 2,
-                ops.UP2, L2, want_stats=True)
+    L2, lay = Ltot // 2, model.lay
+    y6, st = cg(lay["decoder.1"], y5, want_stats=True)
     n6 = inorm(st, L2, "decoder.2", 64)
-    y7 = cg(y6, pw("decoder.4.weight", "conv_fwd"), "decoder.4.weight", P["decoder.4.bias"], 64, 64, 1, 1,
-            ops.taps_conv(K5, 1, 2), L2, s1=n6[2], t1=n6[3], swish=True)
-    y8, st = cg(y7, pw("decoder.5.weight", "convT_fwd"), "decoder.5.weight", P["decoder.5.bias"], 64, 32, 1, 2,
-                ops.UP2, Ltot, want_stats=True)
+    y7 = cg(lay["decoder.4"], y6, s1=n6[2], t1=n6[3], swish=True)
+    y8, st = cg(lay["decoder.5"], y7, want_stats=True)
     n8 = inorm(st, Ltot, "decoder.6", 32)
     recon = ops.convCto1(y8, P["decoder.8.weight"], P["decoder.8.bias"], n8[2], n8[3], True)
     return y6, n6, y7, y8, n8, recon
@@ -376,15 +365,14 @@ class _ConvAEFn(torch.autograd.Function):
         x0, B, T, Ltot = _input_rows(feats)
         L2, L4 = Ltot // 2, Ltot // 4
         S = {}                                                  # saved for backward
-        W = _packed(model, P)
-        pw = lambda k, kind: W[(k, kind)]
+        W, lay = _packed(model, P), model.lay
         # activation cache: each conv also writes its transformed input rows in bf16, the operand
         # its weight gradient multiplies with (saves the recomputation and half of the bytes there)
         A = {}
         cache_a = (train and model.cache_wgrad_operand and any(ctx.needs_input_grad)
                    and ops.WGRAD_CODE[model.precision] in (L.BF16X1F, L.BF16) and model.kcode != L.FP8)
 
-        cg, inorm = _launchers(model, P, B, A if cache_a else None)
+        cg, inorm = _launchers(model, P, W, B, A if cache_a else None)
 
         def bn_stats(stats, count, mod, prefix, C, ci):
             """train-mode BatchNorm from the per-tile partial statistics of the producing launch"""
@@ -414,21 +402,15 @@ class _ConvAEFn(torch.autograd.Function):
         cdev = lambda i: None if gc is None else gc[i:i + 1]
         # ---------------- encoder (and decoder.0: it stages the same transformed encoder output the
         # classifier's input BatchNorm needs statistics of) ----------------
-        (y0, y1, y2, y3, y4, y5), (n1, n2, n3, n4), a4_stats = _encoder_launches(model, P, pw, cg, inorm, x0, Ltot, train)
+        (y0, y1, y2, y3, y4, y5), (n1, n2, n3, n4), a4_stats = _encoder_launches(model, P, cg, inorm, x0, Ltot, train)
         # ---------------- sex classifier (GradReverse = identity forward) ----------------
         bn_n = bn_stats(a4_stats if train else None, B * L4, cls.norm, "sex_classifier.norm", 128, 0)
-        r0, st = cg(y4, pw("sex_classifier.tdnn.0.weight", "conv_fwd"), "sex_classifier.tdnn.0.weight",
-                               P["sex_classifier.tdnn.0.bias"], 128, 128, 1, 1, ops.taps_conv(5, 1, 0), La,
-                               s1=n4[2], t1=n4[3], swish=True, s2=bn_n[2], t2=bn_n[3], relu=True,
-                               want_stats=True)
+        r0, st = cg(lay["sex_classifier.tdnn.0"], y4, s1=n4[2], t1=n4[3], swish=True, s2=bn_n[2], t2=bn_n[3],
+                    relu=True, want_stats=True)
         bn0 = bn_stats(st, B * La, cls.tdnn[2], "sex_classifier.tdnn.2", 128, 1)
-        r1, st = cg(r0, pw("sex_classifier.tdnn.3.weight", "conv_fwd"), "sex_classifier.tdnn.3.weight",
-                               P["sex_classifier.tdnn.3.bias"], 128, 128, 1, 1, ops.taps_conv(3, 2, 0), Lb,
-                               s2=bn0[2], t2=bn0[3], relu=True, want_stats=True)
+        r1, st = cg(lay["sex_classifier.tdnn.3"], r0, s2=bn0[2], t2=bn0[3], relu=True, want_stats=True)
         bn1 = bn_stats(st, B * Lb, cls.tdnn[5], "sex_classifier.tdnn.5", 128, 2)
-        r2, st = cg(r1, pw("sex_classifier.tdnn.6.weight", "conv_fwd"), "sex_classifier.tdnn.6.weight",
-                               P["sex_classifier.tdnn.6.bias"], 128, 128, 1, 1, ops.taps_conv(3, 3, 0), Lc,
-                               s2=bn1[2], t2=bn1[3], relu=True, want_stats=True)
+        r2, st = cg(lay["sex_classifier.tdnn.6"], r1, s2=bn1[2], t2=bn1[3], relu=True, want_stats=True)
         bn2 = bn_stats(st, B * Lc, cls.tdnn[8], "sex_classifier.tdnn.8", 128, 3)
         pooled, pmean, psd = ops.pool_fwd(r2, bn2[2], bn2[3], noise=_noise(model, B, feats.device))
         def head_fwd(X, n, local=False):
@@ -459,7 +441,7 @@ class _ConvAEFn(torch.autograd.Function):
         if plan:                               # this rank's rows of the global log-probabilities
             logp = logp_all[plan[0]:plan[0] + B]
         # ---------------- decoder ----------------
-        y6, n6, y7, y8, n8, recon = _decoder_launches(P, pw, cg, inorm, y5, Ltot)
+        y6, n6, y7, y8, n8, recon = _decoder_launches(model, P, cg, inorm, y5, Ltot)
 
         if tracked:
             torch._foreach_add_(tracked, 1)
@@ -504,10 +486,9 @@ class _ConvAEFn(torch.autograd.Function):
 
         def setg(key, val):
             G[key] = newg(key).copy_(val.reshape(P[key].shape))
-        W, A = S["W"], S["A"]
+        W, A, lay = S["W"], S["A"], model.lay
         gc = S["gc"]                                      # all-reduced BatchNorm counts (or None)
         cdev = lambda i: None if gc is None else gc[i:i + 1]
-        pw = lambda k, kind: W[(k, kind)]
         # the split-K reducers of a stage's weight gradients wait for the end of the stage like the bias
         # gradients (nobody reads them earlier) and run as one launch (sa_wgrad_reduce_multi)
         pending_wred = []
@@ -516,13 +497,14 @@ class _ConvAEFn(torch.autograd.Function):
         # gradient feeds a convolution moves into that convolution's prologue
         fuse = bool(A) and model.dgrad_kcode in (L.BF16X3, L.BF16)
 
-        def cg(gin, w, *args, **kw):
-            """data-gradient / forward-type launch; a _PendingApply input selects the
+        def cg(ly, gin, **kw):
+            """the layer's data-gradient launch; a _PendingApply input selects the
             normalisation-backward prologue, which also emits the bf16 d y for the deferred weight
             gradients and the column sums for the bias gradient."""
-            if not isinstance(gin, _PendingApply):
-                return _conv(gin, w, *args, **kw)
-            p = gin
+            p, dy = gin, gin.g if isinstance(gin, _PendingApply) else gin
+            w, args = W[ly.key, ly.kinds[1]], (None,) + ly.dgrad(ly.lin(dy.shape[1]))
+            if dy is gin:
+                return _conv(dy, w, *args, **kw)
             dyc = torch.empty(p.g.shape, dtype=torch.bfloat16, device=p.g.device) if p.wgrads else None
             want_cs = p.bias_key is not None and need[p.bias_key]
             out = _conv(p.g, w, *args, a_out=dyc, nb=dict(x=p.y, c1=p.c[0], c2=p.c[1], c3=p.c[2],
@@ -556,14 +538,6 @@ class _ConvAEFn(torch.autograd.Function):
             if pending_wred:
                 ops.wgrad_reduce_multi(pending_wred)
                 pending_wred.clear()
-
-        def in_ep(y, nrm, g2=None):
-            """fused-epilogue description of an [InstanceNorm -> swish] backward (stats pass)."""
-            mean, rstd, scale, shift = nrm
-            d = dict(mode=1, x=y, g2=g2, s1=scale, t1=shift, mean=mean, rstd=rstd)
-            if isinstance(g2, _PendingApply):                 # apply of the `norm` BatchNorm rides along
-                d.update(g2=g2.g, g2k=g2.c)
-            return d
 
         def in_finish(g, st, y, nrm, C, Ln, prefix, bias_key):
             """g = d z (already multiplied by swish'), st = partial (sum dz, sum dz*yhat)."""
@@ -606,27 +580,17 @@ class _ConvAEFn(torch.autograd.Function):
                 bias_from(st2, bias_key, 128)
             return g
 
-        def conv_wgrad(key, x, dy, cin, cout, sa, Mrows, K, dil, pad, **pro):
+        def conv_wgrad(ly, x, dy, **pro):
+            key = ly.key
             if not need[key]:
                 return
             if isinstance(dy, _PendingApply):                # runs once the bf16 d y exists
-                dy.wgrads.append(lambda dyc: conv_wgrad(key, x, dyc, cin, cout, sa, Mrows, K, dil, pad, dy_pre=True))
+                dy.wgrads.append(lambda dyc: conv_wgrad(ly, x, dyc, dy_pre=True))
                 return
             if key in A:
                 x, pro = A[key], dict(x_pre=True, dy_pre=bool(pro.get("dy_pre")))
-            G[key] = wg(x, dy, cin, cout, sa, 1, [(k * dil - pad, 0) for k in range(K)], Mrows, newg(key),
-                        (K, cin * K, 1), **pro)
-
-        def convT_wgrad(key, x, dy, cin, cout, Mrows, dy_pre=False):
-            if not need[key]:
-                return
-            if isinstance(dy, _PendingApply):
-                dy.wgrads.append(lambda dyc: convT_wgrad(key, x, dyc, cin, cout, Mrows, True))
-                return
-            pro = {}
-            if key in A:
-                x, pro = A[key], dict(x_pre=True, dy_pre=dy_pre)
-            G[key] = wg(x, dy, cin, cout, 1, 2, CONVT_WG_TAPS, Mrows, newg(key), (cout * K5, K5, 1), **pro)
+            *geo, strides = ly.wgrad(x.shape[1])
+            G[key] = wg(x, dy, *geo, newg(key), strides, **pro)
 
         # an output the loss does not use (the endtoend "sex only" branch,
         # speechbrain_convae_train.py:112-113, leaves recon out of the graph): like autograd in the
@@ -706,19 +670,15 @@ class _ConvAEFn(torch.autograd.Function):
             t = "sex_classifier.tdnn."
             g, st = ops.pool_bwd(r2, bn2[2], bn2[3], dP, S["pmean"], S["psd"], bn=(bn2[0], bn2[1]))
             g = bn_finish(g, st, r2, bn2, Lc, t + "8", t + "6.bias", 3)
-            conv_wgrad(t + "6.weight", r1, g, 128, 128, 1, Lc, 3, 3, 0, s2=bn1[2], t2=bn1[3])
-            g, st = cg(g, pw(t + "6.weight", "conv_dgrad"), None, 128, 128, 1, 1,
-                       ops.taps_conv_dgrad_s1(3, 3, 0), Lb, want_stats=True, ep=bn_ep(r1, bn1))
+            conv_wgrad(lay[t + "6"], r1, g, s2=bn1[2], t2=bn1[3])
+            g, st = cg(lay[t + "6"], g, want_stats=True, ep=bn_ep(r1, bn1))
             g = bn_finish(g, st, r1, bn1, Lb, t + "5", t + "3.bias", 2)
-            conv_wgrad(t + "3.weight", r0, g, 128, 128, 1, Lb, 3, 2, 0, s2=bn0[2], t2=bn0[3])
-            g, st = cg(g, pw(t + "3.weight", "conv_dgrad"), None, 128, 128, 1, 1,
-                       ops.taps_conv_dgrad_s1(3, 2, 0), La, want_stats=True, ep=bn_ep(r0, bn0))
+            conv_wgrad(lay[t + "3"], r0, g, s2=bn0[2], t2=bn0[3])
+            g, st = cg(lay[t + "3"], g, want_stats=True, ep=bn_ep(r0, bn0))
             g = bn_finish(g, st, r0, bn0, La, t + "2", t + "0.bias", 1)
-            conv_wgrad(t + "0.weight", y4, g, 128, 128, 1, La, 5, 1, 0, s1=n4[2], t1=n4[3], swish=True,
-                       s2=bn_n[2], t2=bn_n[3])
+            conv_wgrad(lay[t + "0"], y4, g, s1=n4[2], t1=n4[3], swish=True, s2=bn_n[2], t2=bn_n[3])
             xp4 = (n4[2], n4[3])
-            g, st = cg(g, pw(t + "0.weight", "conv_dgrad"), None, 128, 128, 1, 1,
-                       ops.taps_conv_dgrad_s1(5, 1, 0), L4, want_stats=True, ep=bn_ep(y4, bn_n, xp4))
+            g, st = cg(lay[t + "0"], g, want_stats=True, ep=bn_ep(y4, bn_n, xp4))
             da = bn_finish(g, st, y4, bn_n, L4, "sex_classifier.norm", None, 0, xp=xp4)      # includes GRL
             flush_pending()
             if need_stage["sex_classifier"]:
@@ -741,19 +701,16 @@ class _ConvAEFn(torch.autograd.Function):
                 g, st = ops.conv1toC(g_rec, P["decoder.8.weight"], None, dt, flip=True, want_stats=True,
                                      ep=dict(x=y8, s1=n8[2], t1=n8[3], mean=n8[0], rstd=n8[1]))  # d z8
             g = in_finish(g, st, y8, n8, 32, Ltot, "decoder.6", "decoder.5.bias")               # d y8
-            convT_wgrad("decoder.5.weight", y7, g, 64, 32, L2)
-            g, st = cg(g, pw("decoder.5.weight", "convT_dgrad"), None, 32, 64, 2, 1,
-                       ops.taps_convT_dgrad(), L2, want_stats=True)                              # d y7
+            conv_wgrad(lay["decoder.5"], y7, g)
+            g, st = cg(lay["decoder.5"], g, want_stats=True)                                    # d y7
             bias_from(st, "decoder.4.bias", 64)
-            conv_wgrad("decoder.4.weight", y6, g, 64, 64, 1, L2, K5, 1, 2, s1=n6[2], t1=n6[3], swish=True)
-            g, st = cg(g, pw("decoder.4.weight", "conv_dgrad"), None, 64, 64, 1, 1,
-                       ops.taps_conv_dgrad_s1(K5, 1, 2), L2, want_stats=True, ep=in_ep(y6, n6))  # d z6
+            conv_wgrad(lay["decoder.4"], y6, g, s1=n6[2], t1=n6[3], swish=True)
+            g, st = cg(lay["decoder.4"], g, want_stats=True, ep=_in_ep(y6, n6))                 # d z6
             g = in_finish(g, st, y6, n6, 64, L2, "decoder.2", "decoder.1.bias")                 # d y6
-            convT_wgrad("decoder.1.weight", y5, g, 128, 64, L4)
-            g, st = cg(g, pw("decoder.1.weight", "convT_dgrad"), None, 64, 128, 2, 1,
-                       ops.taps_convT_dgrad(), L4, want_stats=True)                              # d y5
+            conv_wgrad(lay["decoder.1"], y5, g)
+            g, st = cg(lay["decoder.1"], g, want_stats=True)                                    # d y5
             bias_from(st, "decoder.0.bias", 128)
-            conv_wgrad("decoder.0.weight", y4, g, 128, 128, 1, L4, K5, 1, 2, s1=n4[2], t1=n4[3], swish=True)
+            conv_wgrad(lay["decoder.0"], y4, g, s1=n4[2], t1=n4[3], swish=True)
             flush_pending()
             if need_stage["decoder"]:
                 buckets.reduce_stage("decoder")
@@ -768,24 +725,16 @@ class _ConvAEFn(torch.autograd.Function):
 
         # ======================= encoder =======================
         # d z4 = (decoder.0 dgrad + classifier branch) * swish'(z4), fused into the dgrad launch
-        g, st = cg(g, pw("decoder.0.weight", "conv_dgrad"), None, 128, 128, 1, 1,
-                   ops.taps_conv_dgrad_s1(K5, 1, 2), L4, want_stats=True, ep=in_ep(y4, n4, g2=da4_cls))
-        g = in_finish(g, st, y4, n4, 128, L4, "encoder.12", "encoder.11.bias")               # d y4
-        conv_wgrad("encoder.11.weight", y3, g, 128, 128, 1, L4, K5, 1, 2, s1=n3[2], t1=n3[3], swish=True)
-        g, st = cg(g, pw("encoder.11.weight", "conv_dgrad"), None, 128, 128, 1, 1,
-                   ops.taps_conv_dgrad_s1(K5, 1, 2), L4, want_stats=True, ep=in_ep(y3, n3))
-        g = in_finish(g, st, y3, n3, 128, L4, "encoder.9", "encoder.8.bias")                 # d y3
-        conv_wgrad("encoder.8.weight", y2, g, 64, 128, 2, L4, K5, 1, 2, s1=n2[2], t1=n2[3], swish=True)
-        g, st = cg(g, pw("encoder.8.weight", "conv_dgrad"), None, 128, 64, 1, 2, ops.UP2, L2,
-                   want_stats=True, ep=in_ep(y2, n2))
-        g = in_finish(g, st, y2, n2, 64, L2, "encoder.6", "encoder.5.bias")                  # d y2
-        conv_wgrad("encoder.5.weight", y1, g, 64, 64, 1, L2, K5, 1, 2, s1=n1[2], t1=n1[3], swish=True)
-        g, st = cg(g, pw("encoder.5.weight", "conv_dgrad"), None, 64, 64, 1, 1,
-                   ops.taps_conv_dgrad_s1(K5, 1, 2), L2, want_stats=True, ep=in_ep(y1, n1))
-        g = in_finish(g, st, y1, n1, 64, L2, "encoder.3", "encoder.2.bias")                  # d y1
-        conv_wgrad("encoder.2.weight", y0, g, 32, 64, 2, L2, K5, 1, 2, swish=True)
-        g, st = cg(g, pw("encoder.2.weight", "conv_dgrad"), None, 64, 32, 1, 2, ops.UP2, Ltot,
-                   want_stats=True, ep=dict(mode=1, x=y0))                                   # d y0
+        g, st = cg(lay["decoder.0"], g, want_stats=True, ep=_in_ep(y4, n4, g2=da4_cls))
+        # per layer: y = conv(swish(nx(x))) and nrm the InstanceNorm on y; encoder.2's input y0 carries no norm
+        for conv, norm, y, nrm, x, nx in (("encoder.11", "encoder.12", y4, n4, y3, n3),
+                                          ("encoder.8", "encoder.9", y3, n3, y2, n2),
+                                          ("encoder.5", "encoder.6", y2, n2, y1, n1),
+                                          ("encoder.2", "encoder.3", y1, n1, y0, None)):
+            ly = lay[conv]
+            g = in_finish(g, st, y, nrm, ly.cout, y.shape[1], norm, ly.bias)                    # d y
+            conv_wgrad(ly, x, g, swish=True, **(dict(s1=nx[2], t1=nx[3]) if nx else {}))
+            g, st = cg(ly, g, want_stats=True, ep=_in_ep(x, nx) if nx else dict(mode=1, x=x))   # d z below (d y0 last)
         bias_from(st, "encoder.0.bias", 32)
         if need["encoder.0.weight"]:
             G["encoder.0.weight"] = ops.wgrad1C(S["x0"], g, newg("encoder.0.weight"))

@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import SaHipError
-from .convae import GLU, CONVT_WG_TAPS, K5
+from .convae import GLU, _in_ep
 from .xvector import EncoderClassifier
 
 
@@ -49,6 +49,7 @@ class ConvReconstruction(nn.Module):
             nn.ConvTranspose1d(64, 32, 5, 2, 2, output_padding=1), nn.InstanceNorm1d(32, affine=True), GLU(),
             nn.Conv1d(32, 1, 15, 1, 7),
         )
+        self.lay = ops.conv_layers(self, ("encoder",))        # the conv_gemm layers' launch geometry, stated once
         self.sex_classifier = sex_classifier if sex_classifier is not None else EncoderClassifier()
         for p in self.sex_classifier.parameters():          # pretrained and frozen in the reference
             p.requires_grad = False
@@ -88,29 +89,27 @@ def _input_rows(feats):
     return feats.detach().reshape(B, Ltot).contiguous().float(), B, T, Ltot
 
 
+def _cg(model, P, ly, x, dgrad=False, **kw):
+    """the layer's forward launch, or its data-gradient launch on d y = x; the weights are packed per call"""
+    w = ops.pack_weights(P[ly.key].detach(), ly.kinds[dgrad], model.act_dtype, model.kcode)
+    args = (None,) + ly.dgrad(ly.lin(x.shape[1])) if dgrad else (P[ly.bias],) + ly.fwd(x.shape[1])
+    return ops.conv_gemm(x, w, *args, code=model.kcode, **kw)
+
+
 def _recon_launches(model, P, x0, B, Ltot):
     """the conv stack's launches -> ([y0..y3], [n0..n3], recon [B, Ltot]); what forward and reconstruct run"""
-    dt, code = model.act_dtype, model.kcode
-    L2 = Ltot // 2
-
-    def pack(key, kind):
-        return ops.pack_weights(P[key].detach(), kind, dt, code)
+    L2, lay = Ltot // 2, model.lay
 
     def inorm(stats, n, prefix, C):
         return ops.fin_in_fwd(ops.sum_partials(stats, B), B, C, n, P[prefix + ".weight"], P[prefix + ".bias"])
 
-    y0, st = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], dt, want_stats=True)
+    y0, st = ops.conv1toC(x0, P["encoder.0.weight"], P["encoder.0.bias"], model.act_dtype, want_stats=True)
     n0 = inorm(st, Ltot, "encoder.1", 32)
-    y1, st = ops.conv_gemm(y0, pack("encoder.3.weight", "conv_fwd"), P["encoder.3.bias"], 32, 64, 2, 1,
-                           ops.taps_conv(K5, 1, 2), L2, s1=n0[2], t1=n0[3], swish=True, want_stats=True,
-                           code=code)
+    y1, st = _cg(model, P, lay["encoder.3"], y0, s1=n0[2], t1=n0[3], swish=True, want_stats=True)
     n1 = inorm(st, L2, "encoder.4", 64)
-    y2, st = ops.conv_gemm(y1, pack("encoder.6.weight", "conv_fwd"), P["encoder.6.bias"], 64, 64, 1, 1,
-                           ops.taps_conv(K5, 1, 2), L2, s1=n1[2], t1=n1[3], swish=True, want_stats=True,
-                           code=code)
+    y2, st = _cg(model, P, lay["encoder.6"], y1, s1=n1[2], t1=n1[3], swish=True, want_stats=True)
     n2 = inorm(st, L2, "encoder.7", 64)
-    y3, st = ops.conv_gemm(y2, pack("encoder.9.weight", "convT_fwd"), P["encoder.9.bias"], 64, 32, 1, 2,
-                           ops.UP2, Ltot, s1=n2[2], t1=n2[3], swish=True, want_stats=True, code=code)
+    y3, st = _cg(model, P, lay["encoder.9"], y2, s1=n2[2], t1=n2[3], swish=True, want_stats=True)
     n3 = inorm(st, Ltot, "encoder.10", 32)
     recon = ops.convCto1(y3, P["encoder.12.weight"], P["encoder.12.bias"], n3[2], n3[3], True)
     return [y0, y1, y2, y3], [n0, n1, n2, n3], recon
@@ -133,7 +132,7 @@ class _ConvRecFn(torch.autograd.Function):
         if S is None:
             raise SaHipError("ConvReconstruction backward called twice (saved tensors were released)")
         P = dict(zip(names, ctx.params))
-        dt, code = model.act_dtype, model.kcode
+        dt, lay = model.act_dtype, model.lay
         B, T, Ltot, L2 = S["dims"]
         y0, y1, y2, y3 = S["y"]
         n0, n1, n2, n3 = S["n"]
@@ -148,8 +147,12 @@ class _ConvRecFn(torch.autograd.Function):
         def newg(key):
             return torch.empty_like(P[key])
 
-        def pack(key, kind):
-            return ops.pack_weights(P[key].detach(), kind, dt, code)
+        def layer_bwd(ly, x, nrm, dy):
+            """the layer's weight gradient (x, nrm: its stored input and that input's norm), then d z of its input"""
+            if need[ly.key]:
+                *geo, strides = ly.wgrad(x.shape[1])
+                G[ly.key] = wg(x, dy, *geo, newg(ly.key), strides, s1=nrm[2], t1=nrm[3], swish=True)
+            return _cg(model, P, ly, dy, dgrad=True, want_stats=True, ep=_in_ep(x, nrm))
 
         def norm_bwd(g, st, y, nrm, C, Ln, prefix, bias_key):
             """g = d z (already multiplied by the activation derivative), st = partial (sum dz,
@@ -165,9 +168,6 @@ class _ConvRecFn(torch.autograd.Function):
                 G[bias_key] = ops.fin_bias(ops.sum_partials(st2, B), B, C, newg(bias_key))
             return g
 
-        def in_ep(y, nrm):
-            return dict(mode=1, x=y, s1=nrm[2], t1=nrm[3], mean=nrm[0], rstd=nrm[1])
-
         g_rec = d_recon.reshape(B, Ltot).contiguous().float()
         if need["encoder.12.bias"]:
             G["encoder.12.bias"] = ops.sum_partials(g_rec.view(4 * B, Ltot // 4), 1, n=Ltot // 4).sum().float().reshape(1)
@@ -181,25 +181,11 @@ class _ConvRecFn(torch.autograd.Function):
             g, st = ops.conv1toC(g_rec, P["encoder.12.weight"], None, dt, flip=True, want_stats=True,
                                  ep=dict(x=y3, s1=n3[2], t1=n3[3], mean=n3[0], rstd=n3[1]))      # d z3
         g = norm_bwd(g, st, y3, n3, 32, Ltot, "encoder.10", "encoder.9.bias")                    # d y3
-        if need["encoder.9.weight"]:
-            G["encoder.9.weight"] = wg(y2, g, 64, 32, 1, 2, CONVT_WG_TAPS, L2, newg("encoder.9.weight"),
-                                       (32 * K5, K5, 1), s1=n2[2], t1=n2[3], swish=True)
-        g, st = ops.conv_gemm(g, pack("encoder.9.weight", "convT_dgrad"), None, 32, 64, 2, 1,
-                              ops.taps_convT_dgrad(), L2, want_stats=True, ep=in_ep(y2, n2), code=code)   # d z2
+        g, st = layer_bwd(lay["encoder.9"], y2, n2, g)                                           # d z2
         g = norm_bwd(g, st, y2, n2, 64, L2, "encoder.7", "encoder.6.bias")                       # d y2
-        taps5 = [(k - 2, 0) for k in range(K5)]
-        if need["encoder.6.weight"]:
-            G["encoder.6.weight"] = wg(y1, g, 64, 64, 1, 1, taps5, L2, newg("encoder.6.weight"),
-                                       (K5, 64 * K5, 1), s1=n1[2], t1=n1[3], swish=True)
-        g, st = ops.conv_gemm(g, pack("encoder.6.weight", "conv_dgrad"), None, 64, 64, 1, 1,
-                              ops.taps_conv_dgrad_s1(K5, 1, 2), L2, want_stats=True, ep=in_ep(y1, n1),
-                              code=code)                                                          # d z1
+        g, st = layer_bwd(lay["encoder.6"], y1, n1, g)                                           # d z1
         g = norm_bwd(g, st, y1, n1, 64, L2, "encoder.4", "encoder.3.bias")                       # d y1
-        if need["encoder.3.weight"]:
-            G["encoder.3.weight"] = wg(y0, g, 32, 64, 2, 1, taps5, L2, newg("encoder.3.weight"),
-                                       (K5, 32 * K5, 1), s1=n0[2], t1=n0[3], swish=True)
-        g, st = ops.conv_gemm(g, pack("encoder.3.weight", "conv_dgrad"), None, 64, 32, 1, 2, ops.UP2, Ltot,
-                              want_stats=True, ep=in_ep(y0, n0), code=code)                      # d z0
+        g, st = layer_bwd(lay["encoder.3"], y0, n0, g)                                           # d z0
         g = norm_bwd(g, st, y0, n0, 32, Ltot, "encoder.1", "encoder.0.bias")                     # d y0
         if need["encoder.0.weight"]:
             G["encoder.0.weight"] = ops.wgrad1C(S["x0"], g, newg("encoder.0.weight"))

@@ -3,6 +3,7 @@
 Tensors are device memory handles only; all arithmetic happens in libsa_hip.so on the
 current torch stream.  Activations are channels-last [B, L, C] (see include/sa_hip.h).
 """
+import collections
 import ctypes as C
 import functools
 
@@ -29,6 +30,69 @@ def taps_conv_dgrad_s1(K, dil, pad):
 def taps_convT_dgrad(K=5, pad=2):
     """ConvTranspose1d(stride 2) dgrad = stride-2 conv over dy (SA = 2)."""
     return [[(k - pad, k) for k in range(K)]]
+
+
+CONVT_WG_TAPS = [(1, 0), (1, 1), (0, 0), (0, 1), (-1, 0)]     # k5 s2 p2 (op1) convT wgrad: (input row offset, phase) per tap
+
+
+class ConvGeom(collections.namedtuple("ConvGeom", "key bias cin cout K stride dil pad transposed kinds")):
+    """One conv_gemm layer, read once from its nn.Conv1d / nn.ConvTranspose1d container (ConvGeom.of): the
+    arguments of its forward, data-gradient and weight-gradient launches for an input length Lin, its parameter
+    keys and its pack kinds (forward, dgrad).  Strided and transposed layers exist for k5 s2 p2 (op1) only.
+    The launch tuples are cached per length (bounded: utterance lengths vary from batch to batch)."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, prefix, mod):
+        T = isinstance(mod, torch.nn.ConvTranspose1d)
+        g = cls(prefix + ".weight", prefix + ".bias", mod.in_channels, mod.out_channels, mod.kernel_size[0],
+                mod.stride[0], mod.dilation[0], mod.padding[0], T,
+                ("convT_fwd", "convT_dgrad") if T else ("conv_fwd", "conv_dgrad"))
+        if (T or g.stride != 1) and (g[4:8] != (5, 2, 1, 2) or (T and mod.output_padding[0] != 1)):
+            raise L.SaHipError(f"{prefix}: strided / transposed conv layers are k5 s2 p2 (output_padding 1) only")
+        return g
+
+    def lout(self, Lin):
+        if self.transposed:
+            return 2 * Lin
+        return Lin // 2 if self.stride == 2 else Lin + 2 * self.pad - self.dil * (self.K - 1)
+
+    def lin(self, Lout):
+        """input length of the layer whose output (or output gradient) has Lout rows"""
+        if self.transposed:
+            return Lout // 2
+        return 2 * Lout if self.stride == 2 else Lout - 2 * self.pad + self.dil * (self.K - 1)
+
+    @functools.lru_cache(maxsize=256)
+    def fwd(self, Lin):
+        """(cin, cout, sa, u, phases, Lout) of conv_gemm"""
+        if self.transposed:
+            return self.cin, self.cout, 1, 2, UP2, 2 * Lin
+        return self.cin, self.cout, self.stride, 1, taps_conv(self.K, self.dil, self.pad), self.lout(Lin)
+
+    @functools.lru_cache(maxsize=256)
+    def dgrad(self, Lin):
+        """the same tuple for the data gradient: d y [B, lout(Lin), cout] -> d x [B, Lin, cin]"""
+        if self.transposed:
+            return self.cout, self.cin, 2, 1, taps_convT_dgrad(), Lin
+        if self.stride == 2:
+            return self.cout, self.cin, 1, 2, UP2, Lin
+        return self.cout, self.cin, 1, 1, taps_conv_dgrad_s1(self.K, self.dil, self.pad), Lin
+
+    @functools.lru_cache(maxsize=256)
+    def wgrad(self, Lin):
+        """(cin, cout, sa, u, taps, Mrows, dst_strides) of wgrad"""
+        if self.transposed:
+            return self.cin, self.cout, 1, 2, CONVT_WG_TAPS, Lin, (self.cout * self.K, self.K, 1)
+        return (self.cin, self.cout, self.stride, 1, [(k * self.dil - self.pad, 0) for k in range(self.K)],
+                self.lout(Lin), (self.K, self.cin * self.K, 1))
+
+
+def conv_layers(model, roots):
+    """{"encoder.8": ConvGeom, ...} of the conv_gemm layers under model.<root>, in module order (the
+    single-channel first and last layers have their own kernels: conv1toC / convCto1)"""
+    return {f"{r}.{n}": ConvGeom.of(f"{r}.{n}", m) for r in roots for n, m in model.get_submodule(r).named_children()
+            if isinstance(m, (torch.nn.Conv1d, torch.nn.ConvTranspose1d)) and min(m.in_channels, m.out_channels) > 1}
 
 
 def _f(t):
