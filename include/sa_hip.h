@@ -312,7 +312,7 @@ int sa_head_bwd(const float* dlogp, const float* logp, const float* pooled, cons
                 float* db2, float* dg2, float* dbe2, float* dw3, float* db3, float* dpooled, int M, void* stream);
 int sa_head_max_rows(void);
 
-/* x-vector gender classifier forward (models/external_gender_classifiers.py:71-115,144-183;
+/* x-vector gender classifier forward (sa_xvector.hip; models/external_gender_classifiers.py:71-115,144-183;
  * evaluator_inference.yaml:34-48): TDNN block = speechbrain Conv1d (reflect "same" padding) ->
  * LeakyReLU -> BatchNorm1d(eval); StatisticsPooling over time with relative lengths. */
 /* wp: sa_pack_weights(SA_BF16X3, ...) image of the Conv1d weight zero-padded to Npad output channels
@@ -341,7 +341,7 @@ int sa_time_pool_bwd(const float* x, const float* lens, const float* g, const fl
 int sa_leaky_affine_bwd(const float* dy, const float* x, const float* s, float slope, int M, int C,
                         float* dx, void* stream);
 
-/* ---- the x-vector classifier in TRAIN mode (sa_xvector_train.hip; gender_classifier_train.py):
+/* ---- the x-vector classifier in TRAIN mode (sa_xvector.hip; gender_classifier_train.py):
  * TDNN block z = LeakyReLU(conv_same_reflect(x) + bias), y = BatchNorm1d_train(z) = s*z + t with the
  * statistics over all B*T frames.  No float atomics: every reduction is fixed-order partials.
  * sa_xv_tdnn_fwd_train: x [B][T][Cin] (s_in / t_in: the previous block's BatchNorm affine applied at

@@ -276,14 +276,7 @@ class _PendingApply:
 
 
 def _noise(model, B, device):
-    n = model.pooling_noise
-    if n is None or n is False:
-        return None
-    if torch.is_tensor(n):
-        return n.to(device=device, dtype=torch.float32).contiguous()
-    g = torch.randn(B, 128, device=device)                      # speechbrain _get_gauss_noise
-    g = g - g.min()
-    return (g / g.max()).contiguous()
+    return ops.pooling_noise(model.pooling_noise, B, 128, device)
 
 
 def _input_rows(feats):

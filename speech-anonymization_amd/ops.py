@@ -539,6 +539,18 @@ def ew(kind, g, x, Cc, out=None, g2=None, s1=None, t1=None, mean=None, rstd=None
     return stats
 
 
+def pooling_noise(setting, B, Cc, device):
+    """speechbrain's StatisticsPooling adds eps*U[1,9] to the pooled mean on every call: the [B, Cc] draw
+    in [0, 1] behind it (_get_gauss_noise).  None / False: no noise; a tensor fixes the draw; True draws."""
+    if setting is None or setting is False:
+        return None
+    if torch.is_tensor(setting):
+        return setting.to(device=device, dtype=torch.float32).contiguous()
+    g = torch.randn(B, Cc, device=device)
+    g = g - g.min()
+    return (g / g.max()).contiguous()
+
+
 def pool_fwd(r, scale, shift, noise=None, eps=1e-5):
     lib = L.load()
     B, Ln, _ = r.shape

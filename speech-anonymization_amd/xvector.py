@@ -12,6 +12,9 @@ reference's fork adds (speechbrain_convae_train.py:139,146): returns (log_probs,
 classifier pretrained and frozen): differentiable with respect to the features only
 (sa_tdnn_bwd_input / sa_tdnn_fold / sa_time_pool_bwd / sa_leaky_affine_bwd); its parameters never
 receive gradients.
+
+``train_log_probs`` is the TRAIN mode of gender_classifier_train.py (_XvTrainFn).  All kernels are in
+csrc/sa_xvector.hip; the dense layers, softmax and finalisers in sa_head.hip / sa_elementwise.hip.
 """
 import ctypes as C
 
@@ -80,23 +83,75 @@ def _packed_dgrad(conv):
     return conv._dimg, conv._dgeom
 
 
-def _tdnn_bwd(dy, mask, conv, bn, slope=0.01):
-    """d loss / d x of one frozen TDNN block from d loss / d y and the forward's LeakyReLU mask."""
+def _linear(v, lin):
+    return ops.dense(v, lin.weight, lin.bias, lin.out_features, lin.in_features)
+
+
+def _linear_T(g, lin):
+    """d loss / d input of _linear"""
+    return ops.dense(g, lin.weight, None, lin.in_features, lin.out_features, transpose_w=True)
+
+
+def _leaky(x, s=None, t=None, slope=0.01):
+    """LeakyReLU, then the per-channel affine s*v + t where given, on [M, C]"""
+    y = torch.empty_like(x)
+    L.check(L.load().sa_leaky_affine(L.ptr(x), L.ptr(s), L.ptr(t), C.c_float(slope), x.shape[0], x.shape[1],
+                                     L.ptr(y), L.stream()), "sa_leaky_affine")
+    return y
+
+
+def _leaky_bwd(dy, x, s, slope=0.01):
+    dx = torch.empty_like(x)
+    L.check(L.load().sa_leaky_affine_bwd(L.ptr(dy), L.ptr(x), L.ptr(s), C.c_float(slope), x.shape[0], x.shape[1],
+                                         L.ptr(dx), L.stream()), "sa_leaky_affine_bwd")
+    return dx
+
+
+def _lens(lens, device):
+    return None if lens is None else lens.to(device).float().contiguous()
+
+
+def _time_pool(h, lens_d, noise):
+    B, T, Cc = h.shape
+    pooled = torch.empty(B, 2 * Cc, dtype=torch.float32, device=h.device)
+    L.check(L.load().sa_time_pool(L.ptr(h), L.ptr(lens_d), L.ptr(noise), B, T, Cc, C.c_float(1e-5), L.ptr(pooled),
+                                  L.stream()), "sa_time_pool")
+    return pooled
+
+
+def _time_pool_bwd(h, lens_d, g, pooled0):
+    B, T, Cc = h.shape
+    gh = torch.empty_like(h)
+    L.check(L.load().sa_time_pool_bwd(L.ptr(h), L.ptr(lens_d), L.ptr(g), L.ptr(pooled0), B, T, Cc, C.c_float(1e-5),
+                                      L.ptr(gh), L.stream()), "sa_time_pool_bwd")
+    return gh
+
+
+def _dgrad(g, conv, launch):
+    """data gradient of one TDNN block from g [B, T, Cy]: the packed data-gradient image, the
+    extended buffer [B, T + 2*pad, Cin], launch(lib, img, dxe, cred, npad), the reflect adjoint."""
     lib = L.load()
-    B, T, Cy = mask.shape
+    B, T, _ = g.shape
     Cin, K, dil = conv.conv.in_channels, conv.kernel_size, conv.dilation
-    _, _, s, _ = bn.affine()
     img, (cred, npad) = _packed_dgrad(conv)
     pad = dil * (K - 1) // 2
-    dxe = torch.empty(B, T + 2 * pad, Cin, dtype=torch.float32, device=dy.device)
-    L.check(lib.sa_tdnn_bwd_input(L.ptr(dy), L.ptr(mask), L.ptr(s), L.ptr(img), L.ptr(dxe), B, T,
-                                  Cy, cred, Cin, npad, K, dil, C.c_float(slope), L.stream()),
-            "sa_tdnn_bwd_input")
+    dxe = torch.empty(B, T + 2 * pad, Cin, dtype=torch.float32, device=g.device)
+    launch(lib, img, dxe, cred, npad)
     if pad == 0:
         return dxe
-    dx = torch.empty(B, T, Cin, dtype=torch.float32, device=dy.device)
+    dx = torch.empty(B, T, Cin, dtype=torch.float32, device=g.device)
     L.check(lib.sa_tdnn_fold(L.ptr(dxe), L.ptr(dx), B, T, Cin, pad, L.stream()), "sa_tdnn_fold")
     return dx
+
+
+def _tdnn_bwd(dy, mask, conv, bn, slope=0.01):
+    """d loss / d x of one frozen TDNN block from d loss / d y and the forward's LeakyReLU mask."""
+    B, T, Cy = mask.shape
+    s = bn.affine()[2]
+    return _dgrad(dy, conv, lambda lib, img, dxe, cred, npad: L.check(
+        lib.sa_tdnn_bwd_input(L.ptr(dy), L.ptr(mask), L.ptr(s), L.ptr(img), L.ptr(dxe), B, T, Cy, cred,
+                              conv.conv.in_channels, npad, conv.kernel_size, conv.dilation, C.c_float(slope),
+                              L.stream()), "sa_tdnn_bwd_input"))
 
 
 def _tdnn(x, conv, bn, slope=0.01, want_mask=False):
@@ -113,6 +168,36 @@ def _tdnn(x, conv, bn, slope=0.01, want_mask=False):
     return (y, mask) if want_mask else y
 
 
+def _frozen_embed(xv, feats, lens, want_masks):
+    """the eval-mode Xvector: (embedding [B, emb], masks, h, lens_d, pooled0).  Without masks (the
+    no-grad path) sa_time_pool adds the pooling noise and pooled0 is None; with them (in the
+    graph) it pools without noise and the noise is added afterwards, because the backward needs
+    the noise-free pooled0."""
+    h, masks = feats.contiguous().float(), []
+    for conv, bn in xv.tdnn():
+        h = _tdnn(h, conv, bn, want_mask=want_masks)
+        if want_masks:
+            h, m = h
+            masks.append(m)
+    B, _, Cc = h.shape
+    noise = ops.pooling_noise(xv.pooling_noise, B, Cc, h.device)
+    lens_d = _lens(lens, h.device)
+    if not want_masks:
+        return _linear(_time_pool(h, lens_d, noise), xv.blocks[-1].w), None, None, None, None
+    pooled = pooled0 = _time_pool(h, lens_d, None)
+    if noise is not None:
+        pooled = pooled0.clone()
+        pooled[:, :Cc] += 1e-5 * ((1.0 - 9.0) * noise + 9.0)
+    return _linear(pooled, xv.blocks[-1].w), masks, h, lens_d, pooled0
+
+
+def _frozen_head(cl, emb):
+    """the eval-mode Classifier on emb [B, emb]: (log-probabilities [B, classes], h1)"""
+    blk = cl.DNN["block_0"]
+    h1 = _linear(_leaky(emb, *cl.norm.affine()[2:]), blk.linear.w)
+    return ops.log_softmax(_linear(_leaky(h1, *blk.norm.affine()[2:]), cl.out.w)), h1
+
+
 class Xvector(nn.Module):
     def __init__(self, in_channels=80, lin_neurons=128, tdnn_channels=(512, 512, 512, 512, 1500),
                  tdnn_kernel_sizes=(5, 3, 3, 1, 1), tdnn_dilations=(1, 2, 3, 1, 1), pooling_noise=True,
@@ -127,28 +212,13 @@ class Xvector(nn.Module):
         self.pooling_noise = pooling_noise
         self.eval()
 
+    def tdnn(self):
+        """the (conv, bn) pairs of the TDNN blocks, first to last"""
+        return [(self.blocks[i], self.blocks[i + 2]) for i in range(0, len(self.blocks) - 2, 3)]
+
     @torch.no_grad()
     def forward(self, x, lens=None):
-        lib = L.load()
-        x = x.contiguous().float()
-        nb = (len(self.blocks) - 2) // 3
-        for i in range(nb):
-            x = _tdnn(x, self.blocks[3 * i], self.blocks[3 * i + 2])
-        B, T, Cc = x.shape
-        noise = None
-        if torch.is_tensor(self.pooling_noise):
-            noise = self.pooling_noise.to(x.device).float().contiguous()
-        elif self.pooling_noise:
-            g = torch.randn(B, Cc, device=x.device)
-            g = g - g.min()
-            noise = (g / g.max()).contiguous()
-        pooled = torch.empty(B, 2 * Cc, dtype=torch.float32, device=x.device)
-        lens_d = None if lens is None else lens.to(x.device).float().contiguous()
-        L.check(lib.sa_time_pool(L.ptr(x), L.ptr(lens_d), L.ptr(noise), B, T, Cc, C.c_float(1e-5),
-                                 L.ptr(pooled), L.stream()), "sa_time_pool")
-        lin = self.blocks[-1].w
-        emb = ops.dense(pooled, lin.weight, lin.bias, lin.out_features, lin.in_features)
-        return emb.unsqueeze(1)                             # [B, 1, emb]
+        return _frozen_embed(self, x, lens, False)[0].unsqueeze(1)      # [B, 1, emb]
 
 
 class _Block(nn.Module):
@@ -168,34 +238,9 @@ class Classifier(nn.Module):
         self.out = _Lin(lin_neurons, out_neurons)
         self.eval()
 
-    @staticmethod
-    def _leaky_bn(x, bn):
-        lib = L.load()
-        _, _, s, t = bn.affine()
-        y = torch.empty_like(x)
-        L.check(lib.sa_leaky_affine(L.ptr(x), L.ptr(s), L.ptr(t), C.c_float(0.01), x.shape[0], x.shape[1],
-                                    L.ptr(y), L.stream()), "sa_leaky_affine")
-        return y
-
     @torch.no_grad()
     def forward(self, x):
-        v = x.reshape(x.shape[0], -1).contiguous().float()
-        v = self._leaky_bn(v, self.norm)
-        blk = self.DNN["block_0"]
-        v = ops.dense(v, blk.linear.w.weight, blk.linear.w.bias, blk.linear.w.out_features,
-                      blk.linear.w.in_features)
-        v = self._leaky_bn(v, blk.norm)
-        v = ops.dense(v, self.out.w.weight, self.out.w.bias, self.out.w.out_features, self.out.w.in_features)
-        return ops.log_softmax(v).unsqueeze(1)              # [B, 1, classes]
-
-
-def _leaky_bn_bwd(dy, x, bn):
-    lib = L.load()
-    _, _, s, _ = bn.affine()
-    dx = torch.empty_like(x)
-    L.check(lib.sa_leaky_affine_bwd(L.ptr(dy), L.ptr(x), L.ptr(s), C.c_float(0.01), x.shape[0], x.shape[1],
-                                    L.ptr(dx), L.stream()), "sa_leaky_affine_bwd")
-    return dx
+        return _frozen_head(self, x.reshape(x.shape[0], -1).contiguous().float())[0].unsqueeze(1)  # [B, 1, classes]
 
 
 class _XvFn(torch.autograd.Function):
@@ -203,64 +248,22 @@ class _XvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, feats, lens):
-        lib = L.load()
-        xv, cl = enc.embedding_model, enc.classifier
-        x = feats.detach().contiguous().float()
-        nb = (len(xv.blocks) - 2) // 3
-        h, masks = x, []
-        for i in range(nb):
-            h, m = _tdnn(h, xv.blocks[3 * i], xv.blocks[3 * i + 2], want_mask=True)
-            masks.append(m)
-        B, T, Cc = h.shape
-        lens_d = None if lens is None else lens.to(h.device).float().contiguous()
-        pooled0 = torch.empty(B, 2 * Cc, dtype=torch.float32, device=h.device)
-        L.check(lib.sa_time_pool(L.ptr(h), L.ptr(lens_d), None, B, T, Cc, C.c_float(1e-5), L.ptr(pooled0),
-                                 L.stream()), "sa_time_pool")
-        pooled = pooled0
-        noise = xv.pooling_noise
-        if noise is not None and noise is not False:
-            if torch.is_tensor(noise):
-                g = noise.to(h.device).float()
-            else:
-                g = torch.randn(B, Cc, device=h.device)
-                g = g - g.min()
-                g = g / g.max()
-            pooled = pooled0.clone()
-            pooled[:, :Cc] += 1e-5 * ((1.0 - 9.0) * g + 9.0)
-        lin = xv.blocks[-1].w
-        emb = ops.dense(pooled, lin.weight, lin.bias, lin.out_features, lin.in_features)
-        v1 = Classifier._leaky_bn(emb, cl.norm)
-        blk = cl.DNN["block_0"]
-        h1 = ops.dense(v1, blk.linear.w.weight, blk.linear.w.bias, blk.linear.w.out_features,
-                       blk.linear.w.in_features)
-        v2 = Classifier._leaky_bn(h1, blk.norm)
-        logits = ops.dense(v2, cl.out.w.weight, cl.out.w.bias, cl.out.w.out_features, cl.out.w.in_features)
-        logp = ops.log_softmax(logits)
+        emb, masks, h, lens_d, pooled0 = _frozen_embed(enc.embedding_model, feats.detach(), lens, True)
+        logp, h1 = _frozen_head(enc.classifier, emb)
         ctx.enc, ctx.saved = enc, (masks, h, lens_d, pooled0, emb, h1, logp)
         return logp
 
     @staticmethod
     def backward(ctx, d_logp):
-        lib = L.load()
-        enc = ctx.enc
-        xv, cl = enc.embedding_model, enc.classifier
+        xv, cl = ctx.enc.embedding_model, ctx.enc.classifier
         masks, h, lens_d, pooled0, emb, h1, logp = ctx.saved
         blk = cl.DNN["block_0"]
-        g = ops.log_softmax_bwd(d_logp.contiguous().float(), logp)
-        g = ops.dense(g, cl.out.w.weight, None, cl.out.w.in_features, cl.out.w.out_features, transpose_w=True)
-        g = _leaky_bn_bwd(g, h1, blk.norm)
-        g = ops.dense(g, blk.linear.w.weight, None, blk.linear.w.in_features, blk.linear.w.out_features,
-                      transpose_w=True)
-        g = _leaky_bn_bwd(g, emb, cl.norm)
-        lin = xv.blocks[-1].w
-        gp = ops.dense(g, lin.weight, None, lin.in_features, lin.out_features, transpose_w=True)
-        B, T, Cc = h.shape
-        gh = torch.empty_like(h)
-        L.check(lib.sa_time_pool_bwd(L.ptr(h), L.ptr(lens_d), L.ptr(gp), L.ptr(pooled0), B, T, Cc,
-                                     C.c_float(1e-5), L.ptr(gh), L.stream()), "sa_time_pool_bwd")
-        nb = (len(xv.blocks) - 2) // 3
-        for i in reversed(range(nb)):
-            gh = _tdnn_bwd(gh, masks[i], xv.blocks[3 * i], xv.blocks[3 * i + 2])
+        g = _linear_T(ops.log_softmax_bwd(d_logp.contiguous().float(), logp), cl.out.w)
+        g = _linear_T(_leaky_bwd(g, h1, blk.norm.affine()[2]), blk.linear.w)
+        g = _linear_T(_leaky_bwd(g, emb, cl.norm.affine()[2]), xv.blocks[-1].w)
+        gh = _time_pool_bwd(h, lens_d, g, pooled0)
+        for (conv, bn), mask in zip(reversed(xv.tdnn()), reversed(masks)):
+            gh = _tdnn_bwd(gh, mask, conv, bn)
         ctx.saved = None
         return None, gh, None
 
@@ -348,36 +351,18 @@ def _tdnn_wgrad(dpre, x, s_in, t_in, conv, dW):
 
 
 def _tdnn_dgrad(dpre, conv):
-    lib = L.load()
     B, T, Cy = dpre.shape
-    Cin, K, dil = conv.conv.in_channels, conv.kernel_size, conv.dilation
     _stale(conv)
-    img, (cred, npad) = _packed_dgrad(conv)
-    pad = dil * (K - 1) // 2
-    dxe = torch.empty(B, T + 2 * pad, Cin, dtype=torch.float32, device=dpre.device)
-    L.check(lib.sa_xv_tdnn_dgrad(L.ptr(dpre), L.ptr(img), L.ptr(dxe), B, T, Cy, cred, Cin, npad, K, dil,
-                                 L.stream()), "sa_xv_tdnn_dgrad")
-    if pad == 0:
-        return dxe
-    dx = torch.empty(B, T, Cin, dtype=torch.float32, device=dpre.device)
-    L.check(lib.sa_tdnn_fold(L.ptr(dxe), L.ptr(dx), B, T, Cin, pad, L.stream()), "sa_tdnn_fold")
-    return dx
-
-
-def _leaky(x, s=None, t=None, slope=0.01):
-    y = torch.empty_like(x)
-    L.check(L.load().sa_leaky_affine(L.ptr(x), L.ptr(s), L.ptr(t), C.c_float(slope), x.shape[0], x.shape[1],
-                                     L.ptr(y), L.stream()), "sa_leaky_affine")
-    return y
+    return _dgrad(dpre, conv, lambda lib, img, dxe, cred, npad: L.check(
+        lib.sa_xv_tdnn_dgrad(L.ptr(dpre), L.ptr(img), L.ptr(dxe), B, T, Cy, cred, conv.conv.in_channels, npad,
+                             conv.kernel_size, conv.dilation, L.stream()), "sa_xv_tdnn_dgrad"))
 
 
 def train_parameters(xv, cl):
     """the 30 trainable tensors in the order _XvTrainFn takes them"""
     out = []
-    nb = (len(xv.blocks) - 2) // 3
-    for i in range(nb):
-        c, n = xv.blocks[3 * i].conv, xv.blocks[3 * i + 2].norm
-        out += [c.weight, c.bias, n.weight, n.bias]
+    for conv, bn in xv.tdnn():
+        out += [conv.conv.weight, conv.conv.bias, bn.norm.weight, bn.norm.bias]
     lin = xv.blocks[-1].w
     blk = cl.DNN["block_0"]
     out += [lin.weight, lin.bias, cl.norm.norm.weight, cl.norm.norm.bias, blk.linear.w.weight,
@@ -388,42 +373,36 @@ def train_parameters(xv, cl):
 class _XvTrainFn(torch.autograd.Function):
     """Xvector + Classifier in TRAIN mode: log-probabilities [B, classes] as a function of all 30
     parameters (BatchNorms on batch statistics, their running statistics updated).  Forward and
-    backward on libsa_hip.so (sa_xvector_train.hip, sa_head.hip); no gradient to the features."""
+    backward on libsa_hip.so (sa_xvector.hip, sa_head.hip); no gradient to the features."""
 
     @staticmethod
     def forward(ctx, xv, cl, feats, lens, noise, *params):
         lib = L.load()
         x = feats.detach().contiguous().float()
         B, T, _ = x.shape
-        nb = (len(xv.blocks) - 2) // 3
         zs, fs, h, s_in, t_in = [], [], x, None, None
-        for i in range(nb):
-            z, sums = _tdnn_train(h, s_in, t_in, xv.blocks[3 * i])
-            f = _bn_train_stats(sums, xv.blocks[3 * i + 2].norm, B * T)
+        for conv, bn in xv.tdnn():
+            z, sums = _tdnn_train(h, s_in, t_in, conv)
+            f = _bn_train_stats(sums, bn.norm, B * T)
             zs.append(z)
             fs.append(f)
             h, s_in, t_in = z, f[2], f[3]
         Cc = h.shape[2]
-        lens_d = None if lens is None else lens.to(h.device).float().contiguous()
-        pz = torch.empty(B, 2 * Cc, dtype=torch.float32, device=h.device)
-        L.check(lib.sa_time_pool(L.ptr(h), L.ptr(lens_d), None, B, T, Cc, C.c_float(1e-5), L.ptr(pz), L.stream()),
-                "sa_time_pool")
+        lens_d = _lens(lens, h.device)
+        pz = _time_pool(h, lens_d, None)
         pooled = torch.empty_like(pz)
         L.check(lib.sa_xv_pool_affine(L.ptr(pz), L.ptr(s_in), L.ptr(t_in), L.ptr(noise), B, Cc, C.c_float(1e-5),
                                       L.ptr(pooled), L.stream()), "sa_xv_pool_affine")
-        lin = xv.blocks[-1].w
-        emb = ops.dense(pooled, lin.weight, lin.bias, lin.out_features, lin.in_features)
+        emb = _linear(pooled, xv.blocks[-1].w)
         blk = cl.DNN["block_0"]
         u1 = _leaky(emb)
         f1 = _bn_train_stats(_colsums(u1), cl.norm.norm, B)
         v1 = _leaky(emb, f1[2], f1[3])
-        h1 = ops.dense(v1, blk.linear.w.weight, blk.linear.w.bias, blk.linear.w.out_features,
-                       blk.linear.w.in_features)
+        h1 = _linear(v1, blk.linear.w)
         u2 = _leaky(h1)
         f2 = _bn_train_stats(_colsums(u2), blk.norm.norm, B)
         v2 = _leaky(h1, f2[2], f2[3])
-        logits = ops.dense(v2, cl.out.w.weight, cl.out.w.bias, cl.out.w.out_features, cl.out.w.in_features)
-        logp = ops.log_softmax(logits)
+        logp = ops.log_softmax(_linear(v2, cl.out.w))
         ctx.mods = (xv, cl)
         ctx.saved = (x, zs, fs, lens_d, pz, pooled, u1, f1, v1, u2, f2, v2, logp)
         return logp
@@ -440,37 +419,30 @@ class _XvTrainFn(torch.autograd.Function):
         nb = len(zs)
         (gW, gb, gg1, gb1, gW1, gbl1, gg2, gb2, gWo, gbo) = grads[4 * nb:]
         blk = cl.DNN["block_0"]
-        lin = xv.blocks[-1].w
         # ---- head: out Linear <- BatchNorm/LeakyReLU <- Linear <- BatchNorm/LeakyReLU <- embedding Linear
         g = ops.log_softmax_bwd(d_logp.contiguous().float(), logp)
         ops.dense_wgrad(g, v2, gWo)
         _fin_bias(_colsums(g), gbo)
-        g = ops.dense(g, cl.out.w.weight, None, cl.out.w.in_features, cl.out.w.out_features, transpose_w=True)
+        g = _linear_T(g, cl.out.w)
         gp = torch.empty_like(g)
         _fin_bias(_bn_leaky_bwd(g, u2, blk.norm.norm, f2, B, gg2, gb2, gp), gbl1)
         ops.dense_wgrad(gp, v1, gW1)
-        g = ops.dense(gp, blk.linear.w.weight, None, blk.linear.w.in_features, blk.linear.w.out_features,
-                      transpose_w=True)
+        g = _linear_T(gp, blk.linear.w)
         gp = torch.empty_like(g)
         _fin_bias(_bn_leaky_bwd(g, u1, cl.norm.norm, f1, B, gg1, gb1, gp), gb)
         ops.dense_wgrad(gp, pooled, gW)
-        gpool = ops.dense(gp, lin.weight, None, lin.in_features, lin.out_features, transpose_w=True)
+        gpool = _linear_T(gp, xv.blocks[-1].w)
         # ---- statistics pooling of the last block's BatchNorm output
-        Cc = zs[-1].shape[2]
-        f = fs[-1]
         gz = torch.empty_like(gpool)
-        L.check(lib.sa_xv_pool_affine_bwd(L.ptr(gpool), L.ptr(f[2]), B, Cc, L.ptr(gz), L.stream()),
+        L.check(lib.sa_xv_pool_affine_bwd(L.ptr(gpool), L.ptr(fs[-1][2]), B, zs[-1].shape[2], L.ptr(gz), L.stream()),
                 "sa_xv_pool_affine_bwd")
-        dy = torch.empty_like(zs[-1])
-        L.check(lib.sa_time_pool_bwd(L.ptr(zs[-1]), L.ptr(lens_d), L.ptr(gz), L.ptr(pz), B, T, Cc, C.c_float(1e-5),
-                                     L.ptr(dy), L.stream()), "sa_time_pool_bwd")
+        dy = _time_pool_bwd(zs[-1], lens_d, gz, pz)
         # ---- TDNN blocks, last to first
-        for i in reversed(range(nb)):
-            conv, norm = xv.blocks[3 * i], xv.blocks[3 * i + 2].norm
+        for i, (conv, bn) in reversed(list(enumerate(xv.tdnn()))):
             gw, gbias, ggam, gbet = grads[4 * i: 4 * i + 4]
             z = zs[i]
             dpre = torch.empty_like(z)
-            bsum = _bn_leaky_bwd(dy.view(B * T, -1), z.view(B * T, -1), norm, fs[i], B * T, ggam, gbet,
+            bsum = _bn_leaky_bwd(dy.view(B * T, -1), z.view(B * T, -1), bn.norm, fs[i], B * T, ggam, gbet,
                                  dpre.view(B * T, -1))
             _fin_bias(bsum, gbias)
             xin, s_in, t_in = (x, None, None) if i == 0 else (zs[i - 1], fs[i - 1][2], fs[i - 1][3])
@@ -496,16 +468,8 @@ def train_log_probs(embedding_model, classifier, feats, lens=None):
     B = feats.shape[0]
     if B < 2:
         raise ValueError("Expected more than 1 value per channel when training (batch of one utterance)")
-    noise = embedding_model.pooling_noise
-    Cc = embedding_model.blocks[-5].conv.out_channels
-    if torch.is_tensor(noise):
-        noise = noise.to(feats.device).float().contiguous()
-    elif noise:
-        g = torch.randn(B, Cc, device=feats.device)
-        g = g - g.min()
-        noise = (g / g.max()).contiguous()
-    else:
-        noise = None
+    Cc = embedding_model.tdnn()[-1][0].conv.out_channels
+    noise = ops.pooling_noise(embedding_model.pooling_noise, B, Cc, feats.device)
     return _XvTrainFn.apply(embedding_model, classifier, feats, lens, noise, *params).unsqueeze(1)
 
 

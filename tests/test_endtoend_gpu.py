@@ -35,15 +35,21 @@ def hip_classifier(oclf, pooling_noise=None):
     return enc.to(DEV).eval()
 
 
-@pytest.mark.parametrize("cfg", [(80, 512, 5, 1), (512, 512, 3, 2), (512, 512, 3, 3), (512, 512, 1, 1), (512, 1500, 1, 1)],
-                         ids=["80-512k5", "512-512k3d2", "512-512k3d3", "512-512k1", "512-1500k1"])
-def test_tdnn_block_input_gradient(cfg):
+TDNN_SHAPES = [(80, 512, 5, 1), (512, 512, 3, 2), (512, 512, 3, 3), (512, 512, 1, 1), (512, 1500, 1, 1)]
+TDNN_IDS = ["80-512k5", "512-512k3d2", "512-512k3d3", "512-512k1", "512-1500k1"]
+
+
+@pytest.mark.parametrize("cfg,T", [(c, 150) for c in TDNN_SHAPES] + [(c, 126) for c in TDNN_SHAPES],
+                         ids=TDNN_IDS + [i + "-T126" for i in TDNN_IDS])
+def test_tdnn_block_input_gradient(cfg, T):
     """one frozen TDNN block (speechbrain Conv1d 'same' reflect padding -> LeakyReLU -> BatchNorm(eval)):
-    sa_tdnn_bwd_input + sa_tdnn_fold against autograd through the oracle's layers (fp64)."""
+    sa_tdnn_bwd_input + sa_tdnn_fold against autograd through the oracle's layers (fp64).  T = 126 is the
+    smallest length whose extended range T + 2*pad takes two 128-row tiles in the data gradient while
+    the forward takes one."""
     from oracle import xvector as OX
     from speech_anonymization_amd import xvector as HX
     cin, cout, k, d = cfg
-    B, T = 2, 150
+    B = 2
     g = torch.Generator().manual_seed(cin + cout + k + d)
     oc, ob = OX.Conv1d(cin, cout, k, d), OX.BatchNorm1d(cout)
     with torch.no_grad():

@@ -1,5 +1,5 @@
 """x-vector gender classifier in TRAIN mode (speech_anonymization_amd.xvector.train_log_probs,
-sa_xvector_train.hip) against the CPU oracle (oracle/xvector.py in float64, torch autograd):
+sa_xvector.hip) against the CPU oracle (oracle/xvector.py in float64, torch autograd):
 one whole train step, each TDNN kernel per layer shape, bit-reproducibility, and the recipe end to
 end (gender_classifier_train.py --synthetic, then its checkpoint as the external classifier)."""
 import os
@@ -95,16 +95,18 @@ def test_train_step_matches_oracle(B, T, lens):
         assert v <= 1e-4, (k, v)
 
 
-@pytest.mark.parametrize("cfg", SHAPES, ids=IDS)
-def test_tdnn_train_kernels(cfg):
+@pytest.mark.parametrize("cfg,T", [(c, 150) for c in SHAPES] + [(c, 126) for c in SHAPES],
+                         ids=IDS + [i + "-T126" for i in IDS])
+def test_tdnn_train_kernels(cfg, T):
     """one TDNN block in train mode, T not a multiple of the 128-frame tile: sa_xv_tdnn_fwd_train
     (z and the batch statistics), the BatchNorm/LeakyReLU backward (dpre, d gamma, d beta, d bias),
     sa_xv_tdnn_wgrad (d W) and sa_xv_tdnn_dgrad + sa_tdnn_fold (d x, reflected ends included)
-    against fp64 autograd; rel-MSE <= 1e-8 each."""
+    against fp64 autograd; rel-MSE <= 1e-8 each.  T = 126: the data gradient's extended range
+    T + 2*pad takes two row tiles, the forward one."""
     from oracle import xvector as OX
     from speech_anonymization_amd import xvector as HX
     cin, cout, k, d = cfg
-    B, T = 2, 150
+    B = 2
     g = torch.Generator().manual_seed(cin + cout + k + d)
     oc, ob = OX.Conv1d(cin, cout, k, d).double(), OX.BatchNorm1d(cout).double()
     with torch.no_grad():
@@ -162,7 +164,7 @@ def test_tdnn_train_kernels(cfg):
     if pad:
         errs["d x ends"] = rel_mse(torch.cat([dx[:, :2 * pad + 1], dx[:, -2 * pad - 1:]], 1),
                                    torch.cat([xr.grad[:, :2 * pad + 1], xr.grad[:, -2 * pad - 1:]], 1))
-    print(f"\n{cfg}: " + ", ".join(f"{kk} {v:.2e}" for kk, v in errs.items()))
+    print(f"\n{cfg} T={T}: " + ", ".join(f"{kk} {v:.2e}" for kk, v in errs.items()))
     for kk, v in errs.items():
         assert v <= 1e-8, (kk, v)
 
