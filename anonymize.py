@@ -19,6 +19,11 @@ vocoder's own loss, the baseline to compare against.  model_type endtoend also t
 --recon_ckpt nor --passthrough.  ``--report_f0 true`` adds, in any mode, the mean voiced F0 (``f0_mean_hz``) and the
 share of voiced frames (``voiced_share``) of every waveform written.
 
+``--pitch_norm true --preserve_formants true`` (or ``--formant_ratio X`` with it) moves the pitch and scales the
+spectral envelope by 1 (by X) instead of by the pitch ratio.  ``--formant_ratio X`` on its own
+runs no model either: OUT receives the waveforms with their formants scaled by X and their pitch untouched; it
+takes neither --recon_ckpt nor --passthrough.  ``--lifter n`` sets the envelope's cepstral length (default 30).
+
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
 sample count and the peak |wav| before write_audio clamps to [-1, 1]."""
@@ -60,9 +65,10 @@ def _f0_report(wav, lens):
 
 def _pitch_norm(settings, device, bs, seed):
     """--pitch_norm true: every utterance pitch-normalised and written, no model and no features"""
+    formant = pitchnorm.check_formant_options(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
-                                   momentum=float(settings.get("momentum", 0.99)), seed=seed)
+                                   momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant)
     utts = []
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
@@ -78,8 +84,32 @@ def _pitch_norm(settings, device, bs, seed):
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
-                      "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}))
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
+                           "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}, **formant)))
+
+
+def _formant_shift(settings, device, bs, seed):
+    """--formant_ratio X on its own: every utterance's envelope scaled by X and written, no model and no features"""
+    formant = pitchnorm.check_formant_options(settings)
+    fs = pitchnorm.FormantShifter(formant["formant_ratio"], n_iter=int(settings.get("n_iter", 32)),
+                                  momentum=float(settings.get("momentum", 0.99)), seed=seed,
+                                  lifter=formant.get("lifter", 30))
+    utts = []
+    for ids, batch in _batches(settings, bs, seed):
+        wavs, lens = batch.sig
+        out = fs(wavs.to(device).contiguous(), lens)
+        rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        out = out.cpu()
+        N = out.shape[1]
+        for i, uid in enumerate(ids):
+            n = int(round(float(lens[i]) * N))
+            sig = out[i, :n]
+            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0})
+            if rep:
+                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True, "n_iter": fs.gl.n_iter,
+                           "seed": seed, "utterances": utts}, **formant)))
 
 
 def main(argv):
@@ -94,6 +124,10 @@ def main(argv):
         torch.cuda.set_device(device)
         os.makedirs(settings["out_dir"], exist_ok=True)
         return _pitch_norm(settings, device, bs, seed)
+    if settings.get("formant_ratio") is not None:
+        torch.cuda.set_device(device)
+        os.makedirs(settings["out_dir"], exist_ok=True)
+        return _formant_shift(settings, device, bs, seed)
     mt = settings["model_type"]
     model = norm = None
     if not passthrough:

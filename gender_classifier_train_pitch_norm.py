@@ -6,10 +6,15 @@ alike, has its voiced F0 scaled to a mean of ``pitch_target_hz`` before the clas
 still recover once the mean pitch is gone?" -- the number the learned anonymisers are compared against.
 
     python gender_classifier_train_pitch_norm.py speechbrain_configs/gender_classifier_pitch_norm.yaml \
-        --device cuda:0 [--pitch_target_hz 170] [--synthetic N] [--key value ...]
+        --device cuda:0 [--pitch_target_hz 170] [--preserve_formants true | --formant_ratio X] [--lifter 30] \
+        [--synthetic N] [--key value ...]
+
+``--preserve_formants true`` moves the pitch and leaves the spectral envelope where it was (what the reference's
+WORLD re-synthesis does); ``--formant_ratio X`` scales it by X instead.  Without either the
+formants move with the pitch.
 
 Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
-summary as the last line (with pitch_target_hz added)."""
+summary as the last line (with pitch_target_hz added, and the envelope settings that were given)."""
 import json
 import os
 import sys
@@ -60,9 +65,10 @@ def main(argv):
 
     brain.fit(counter, Loader(train), Loader(valid))
     brain.evaluate(test(), min_key="error")
-    print(json.dumps({"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
-                      "best_checkpoint": getattr(brain, "best_checkpoint", None),
-                      "pitch_target_hz": pn["target_hz"]}))
+    summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
+               "best_checkpoint": getattr(brain, "best_checkpoint", None), "pitch_target_hz": pn["target_hz"]}
+    summary.update({k: pn[k] for k in ("preserve_formants", "formant_ratio", "lifter") if k in pn})
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":

@@ -555,6 +555,24 @@ int sa_pitch_stretch_mag(const void* R, const float* ratio, int B, int T, int To
 int sa_pitch_resample(const float* y, const float* ratio, const int* n_valid, int B, int Nin, int Nout, float* out,
                       void* stream);
 
+/* ---- spectral envelope and formant warp (sa_envelope.hip): the source-filter split of the
+ * pitch path.  n_fft 400, 201 bins, w_k = 2 pi k / 400.  For every frame of magnitudes S [B][T][201] >= 0:
+ *     L[k] = ln(max(S[k], floor_rel max_k S, 1e-10));
+ *     c_n = (1 / 400) [L_0 + (-1)^n L_200 + 2 sum_{k = 1..199} L_k cos(2 pi n k / 400)], n = 0..n_c (the real
+ *       cepstrum of the even extension);
+ *     E(w) = c_0 + 2 sum_{n = 1..n_c} c_n cos(n w);
+ *     g[k] = clamp(E(min(pi, q_b w_k)) - E(w_k), +-max_gain_ln);  out[k] = S[k] exp(g[k]).
+ *   An all-zero frame gives zeros; a row with q_b == 1 is copied bit for bit.  q [B] is read on the device: a
+ *   value outside [0.25, 4] is taken as the nearer bound, a NaN as 1.  env: NULL, or [B][T][201] to receive
+ *   E(w_k) (tests).  out != S.
+ *   sa_env_dim(which): 0 n_fft 400, 1 bins 201, 2 frames per workgroup, 3 the largest n_c 64, 4 threads per
+ *     workgroup; else -EINVAL.
+ *   -EINVAL: a NULL pointer (env may be NULL), B < 1 or > 65535 (grid.y), T < 1 or > 2^23, n_c outside 1..64,
+ *     floor_rel outside (0, 1), max_gain_ln <= 0. */
+int sa_env_dim(int which);
+int sa_env_warp(const float* S, const float* q, int B, int T, int n_c, float floor_rel, float max_gain_ln,
+                float* out, float* env, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -1079,3 +1079,35 @@ def pitch_resample(y, ratio, n_valid, Nout):
     L.check(L.load().sa_pitch_resample(_f(y), _f(ratio), _f(n_valid), B, Nin, Nout, _f(out), L.stream()),
             "sa_pitch_resample")
     return out
+
+
+# ---- spectral envelope and formant warp (csrc/sa_envelope.hip; pitchnorm.py) ----
+ENV_NC_MAX = 64
+LN10_OVER_20 = 0.11512925464970229       # dB -> natural log of an amplitude ratio
+
+_env_in = functools.partial(_aug_in, family="envelope")
+
+
+def env_warp(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
+    """magnitudes S fp32 [B, T, 201], warp factors q fp32 [B] -> out [B, T, 201] = S exp(g), g = clamp(E(min(pi, q w_k))
+    - E(w_k), +-max_gain_db ln 10 / 20), E the cepstral envelope of ln max(S, floor_rel max S, 1e-10) liftered to
+    n_c coefficients (sa_env_warp).  return_env: also E(w_k) [B, T, 201] (tests)."""
+    if _env_in(S, "S").dim() != 3 or S.shape[2] != 201:
+        raise L.SaHipError(f"S: expected [B, T, 201], got {tuple(S.shape)}")
+    B, T, _ = S.shape
+    if B < 1 or B > GL_MAX_B or T < 1 or T > GL_MAX_T:
+        raise L.SaHipError(f"S: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 1..{GL_MAX_T}")
+    _env_in(q, "q", shape=(B,))
+    n_c = int(n_c)
+    if not 1 <= n_c <= ENV_NC_MAX:
+        raise L.SaHipError(f"env_warp: n_c = {n_c} in 1..{ENV_NC_MAX} expected")
+    if not 0.0 < float(floor_rel) < 1.0:
+        raise L.SaHipError(f"env_warp: floor_rel = {floor_rel} in (0, 1) expected")
+    if not float(max_gain_db) > 0.0:
+        raise L.SaHipError(f"env_warp: max_gain_db = {max_gain_db} > 0 expected")
+    out = torch.empty_like(S)
+    env = torch.empty_like(S) if return_env else None
+    L.check(L.load().sa_env_warp(_f(S), _f(q), B, T, n_c, C.c_float(float(floor_rel)),
+                                 C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
+            "sa_env_warp")
+    return (out, env) if return_env else out

@@ -10,7 +10,12 @@ reference's gender_classifier_train_pitch_norm.py, which does it with WORLD).  T
 
 Stretching by r_b and reading r_b times as fast keeps the duration and multiplies every frequency -- pitch and
 formants alike -- by r_b.  The one device-to-host copy of the path is the B ratios, which size the stretched
-spectrogram."""
+spectrogram.
+
+Formants apart from pitch: with ``formant_ratio`` beta (``preserve_formants``: beta = 1) the
+stretched magnitudes pass through sa_env_warp with q_b = r_b / beta before Griffin-Lim -- their cepstral envelope
+is read q_b times as far up, so that after the resampling the harmonics sit at r_b f and the envelope at beta f.
+``FormantShifter`` is the same warp with no pitch change at all: |STFT| -> warp by 1 / beta -> Griffin-Lim."""
 import math
 
 import torch
@@ -22,6 +27,8 @@ from .features import HOP
 SAMPLE_RATE, W, TAU_MIN, TAU_MAX = 16000, 400, 40, 266
 R_LOW, R_HIGH = 0.5, 2.0                     # what the kernels take
 TARGET_LOW, TARGET_HIGH = 60.0, 400.0        # the tracker's range: 16000 / tau_max .. 16000 / tau_min
+BETA_LOW, BETA_HIGH = 0.5, 2.0               # formant ratios: q = r / beta stays in the [0.25, 4] the kernel takes
+LIFTER_MAX = 64                              # sa_env_dim(3)
 
 
 def f0_track(wav, threshold=0.15):
@@ -35,13 +42,33 @@ def stretched_frames(Tp, ratio):
     return int(math.ceil((int(Tp) - 1) * float(ratio))) + 1
 
 
+def envelope_settings(who, preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db):
+    """-> (beta or None, lifter, floor_rel, max_gain_db), or ValueError: what both classes take for the warp"""
+    if preserve_formants and formant_ratio is not None:
+        raise ValueError(f"{who}: preserve_formants means formant_ratio 1; give one of the two")
+    beta = 1.0 if preserve_formants else (None if formant_ratio is None else float(formant_ratio))
+    if beta is not None and not BETA_LOW <= beta <= BETA_HIGH:
+        raise ValueError(f"{who}: formant_ratio {formant_ratio} in {BETA_LOW}..{BETA_HIGH} expected")
+    if int(lifter) != lifter or not 1 <= int(lifter) <= LIFTER_MAX:
+        raise ValueError(f"{who}: lifter {lifter} in 1..{LIFTER_MAX} expected")
+    if not 0.0 < float(floor_rel) < 1.0:
+        raise ValueError(f"{who}: floor_rel {floor_rel} in (0, 1) expected")
+    if not float(max_gain_db) > 0.0:
+        raise ValueError(f"{who}: max_gain_db {max_gain_db} > 0 expected")
+    return beta, int(lifter), float(floor_rel), float(max_gain_db)
+
+
 class PitchNormalizer:
     """wavs [B, N] (device), relative lengths [B] -> wavs of the same shape whose voiced F0 has mean ~ target_hz;
     samples from round(lens_b N) on are zero.  ``last``: (ratio, mean f0, voiced frames) of the last batch, on
-    the device."""
+    the device.  ``formant_ratio`` beta (``preserve_formants=True``: 1) scales the spectral envelope by beta
+    instead of by the pitch ratio; without either the envelope moves with the pitch and no warp is launched."""
 
     def __init__(self, target_hz=170.0, n_iter=32, momentum=0.99, seed=1, r_min=0.5, r_max=2.0, min_voiced=5,
-                 threshold=0.15):
+                 threshold=0.15, preserve_formants=False, formant_ratio=None, lifter=30, floor_rel=1e-4,
+                 max_gain_db=40.0):
+        self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
+            "PitchNormalizer", preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db)
         if not TARGET_LOW <= float(target_hz) <= TARGET_HIGH:
             raise ValueError(f"PitchNormalizer: target_hz {target_hz} in {TARGET_LOW:g}..{TARGET_HIGH:g} expected")
         if not R_LOW <= float(r_min) <= float(r_max) <= R_HIGH:
@@ -75,9 +102,74 @@ class PitchNormalizer:
         wp = torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs
         R = vocoder.stft(wp.contiguous())
         Tout = max(stretched_frames(R.shape[1], r) for r in host)
-        y = self.gl(ops.pitch_stretch_mag(R, ratio, Tout))
+        S = ops.pitch_stretch_mag(R, ratio, Tout)
+        if self.formant_ratio is not None:                   # q_b = r_b / beta, formed on the device
+            q = (ratio.float() / self.formant_ratio).contiguous()
+            S = ops.env_warp(S, q, self.lifter, self.floor_rel, self.max_gain_db)
+        y = self.gl(S)
         n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N).to(torch.int32)
         return ops.pitch_resample(y, ratio, n_valid, N)
+
+
+class FormantShifter:
+    """wavs [B, N] (device), relative lengths [B] -> wavs of the same shape whose spectral envelope is scaled along
+    frequency by ``formant_ratio`` while the pitch stays: |STFT| -> sa_env_warp at q = 1 / beta -> Griffin-Lim.  No
+    stretch, no resampling, no tracker, and no device-to-host copy.  Samples from round(lens_b N) on are zero."""
+
+    def __init__(self, formant_ratio, n_iter=32, momentum=0.99, seed=1, lifter=30, floor_rel=1e-4, max_gain_db=40.0):
+        if formant_ratio is None:
+            raise ValueError("FormantShifter: formant_ratio expected")
+        self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
+            "FormantShifter", False, formant_ratio, lifter, floor_rel, max_gain_db)
+        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed)
+
+    @torch.no_grad()
+    def __call__(self, wavs, lens):
+        from . import ops
+        if not torch.is_tensor(wavs) or not wavs.is_cuda:
+            raise L.SaHipError("FormantShifter runs on the GPU only (no CPU fallback)")
+        B, N = wavs.shape
+        Np = HOP * -(-N // HOP)
+        wp = torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs
+        R = vocoder.stft(wp.contiguous())
+        one = torch.ones(B, dtype=torch.float32, device=wavs.device)
+        S = ops.pitch_stretch_mag(R, one, R.shape[1])        # |R| exactly: the stretch at ratio 1
+        S = ops.env_warp(S, one / self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db)
+        y = self.gl(S)[:, :N]
+        n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N)
+        live = torch.arange(N, device=wavs.device)[None, :] < n_valid[:, None]
+        return torch.where(live, y, torch.zeros((), dtype=y.dtype, device=y.device)).contiguous()
+
+
+def check_formant_options(settings, block=None):
+    """the envelope settings of a recipe's ``pitch_norm:`` block (if any) under the top-level overrides ->
+    a dict of the keys that were given (preserve_formants, formant_ratio, lifter), each refused in one line"""
+    block = block or {}
+    given = {}
+    for key in ("preserve_formants", "formant_ratio", "lifter"):
+        value = settings.get(key, block.get(key))
+        if value is not None:
+            given[key] = value
+    if "preserve_formants" in given:
+        if not isinstance(given["preserve_formants"], bool):
+            raise SystemExit(f"--preserve_formants {given['preserve_formants']}: true or false")
+    if "formant_ratio" in given:
+        try:
+            beta = float(given["formant_ratio"])
+        except (TypeError, ValueError):
+            beta = float("nan")
+        if not BETA_LOW <= beta <= BETA_HIGH:
+            raise SystemExit(f"--formant_ratio {given['formant_ratio']}: a factor between {BETA_LOW:g} and "
+                             f"{BETA_HIGH:g} by which the formants are scaled")
+        given["formant_ratio"] = beta
+        if given.get("preserve_formants"):
+            raise SystemExit("--preserve_formants true and --formant_ratio exclude each other: preserving the "
+                             "formants is formant_ratio 1")
+    if "lifter" in given:
+        n = given["lifter"]
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= LIFTER_MAX:
+            raise SystemExit(f"--lifter {n}: a count of cepstral coefficients, 1 to {LIFTER_MAX}")
+    return given
 
 
 def check_pitch_target(value):
@@ -105,4 +197,4 @@ def check_pitch_options(settings, run_opts, environ=None):
                          "for it")
     if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
         raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
-    return dict(pn, target_hz=target, r_min=r_min, r_max=r_max)
+    return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn))

@@ -161,9 +161,24 @@ def check_anonymize_options(settings, run_opts, environ=None):
     import os
     environ = os.environ if environ is None else environ
     mt = settings.get("model_type")
-    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm"):   # (pitch normalisation runs no model)
+    from .pitchnorm import check_formant_options
+    formant = check_formant_options(settings)
+    shift_only = "formant_ratio" in formant and not settings.get("pitch_norm")
+    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only:   # (those run no model)
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
-    if settings.get("pitch_norm"):
+    if formant.get("preserve_formants") and not settings.get("pitch_norm"):
+        raise SystemExit("--preserve_formants true goes with --pitch_norm true: it keeps the formants where the "
+                         "pitch normalisation would move them")
+    if "lifter" in formant and not settings.get("pitch_norm") and not shift_only:
+        raise SystemExit("--lifter goes with --formant_ratio or --pitch_norm true --preserve_formants true")
+    if shift_only:
+        if settings.get("passthrough"):
+            raise SystemExit("--formant_ratio and --passthrough true exclude each other: one writes the "
+                             "formant-shifted waveforms, the other the vocoded originals")
+        if settings.get("recon_ckpt"):
+            raise SystemExit("--formant_ratio takes no --recon_ckpt: no anonymiser runs, the waveforms are "
+                             "formant-shifted")
+    elif settings.get("pitch_norm"):
         if settings.get("passthrough"):
             raise SystemExit("--pitch_norm true and --passthrough true exclude each other: one writes the "
                              "pitch-normalised waveforms, the other the vocoded originals")
