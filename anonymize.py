@@ -24,6 +24,13 @@ spectral envelope by 1 (by X) instead of by the pitch ratio.
 runs no model either: OUT receives the waveforms with their formants scaled by X and their pitch untouched; it
 takes neither --recon_ckpt nor --passthrough.  ``--lifter n`` sets the envelope's cepstral length (default 30).
 
+``--mcadams A`` (or ``--mcadams_min LO --mcadams_max HI``: one coefficient per utterance, drawn from [LO, HI]) runs no
+model and reads no checkpoint either: OUT receives the McAdams-transformed waveforms
+(speech_anonymization_amd.mcadams) -- every frame's LPC poles moved from angle phi to phi^A, pitch
+and timing untouched, no Griffin-Lim.  It takes none of --pitch_norm, --formant_ratio, --preserve_formants,
+--recon_ckpt and --passthrough.  Its JSON line carries ``"mcadams": true`` and per utterance ``alpha``, ``gain``,
+``silent_frames``, ``fallback_frames`` and ``peak``.
+
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
 sample count and the peak |wav| before write_audio clamps to [-1, 1]."""
@@ -34,7 +41,7 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, features, gender, pitchnorm, vocoder
+from speech_anonymization_amd import data, features, gender, mcadams, pitchnorm, vocoder
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -112,6 +119,30 @@ def _formant_shift(settings, device, bs, seed):
                            "seed": seed, "utterances": utts}, **formant)))
 
 
+def _mcadams(settings, device, bs, seed):
+    """--mcadams A / --mcadams_min LO --mcadams_max HI: every utterance McAdams-transformed and written, no model"""
+    opts = mcadams.check_mcadams_options(settings)
+    mc = mcadams.McAdams(**opts)
+    utts = []
+    for ids, batch in _batches(settings, bs, seed):
+        wavs, lens = batch.sig
+        out = mc(wavs.to(device).contiguous(), lens)
+        rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        alpha, gain, counts = (v.cpu().tolist() for v in mc.last)
+        out = out.cpu()
+        N = out.shape[1]
+        for i, uid in enumerate(ids):
+            n = int(round(float(lens[i]) * N))
+            sig = out[i, :n]
+            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0, "alpha": alpha[i],
+                         "gain": gain[i], "silent_frames": counts[i][1], "fallback_frames": counts[i][2]})
+            if rep:
+                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
+    shown = {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown)))
+
+
 def main(argv):
     hparams_file, run_opts, overrides = parse_arguments(argv)
     with open(hparams_file) as fin:
@@ -120,6 +151,10 @@ def main(argv):
     device = torch.device(run_opts.get("device", "cuda:0"))
     passthrough = bool(settings.get("passthrough"))
     bs, seed = int(settings.get("batch_size", 3)), int(settings.get("seed", 1986))
+    if any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")):
+        torch.cuda.set_device(device)
+        os.makedirs(settings["out_dir"], exist_ok=True)
+        return _mcadams(settings, device, bs, seed)
     if settings.get("pitch_norm"):
         torch.cuda.set_device(device)
         os.makedirs(settings["out_dir"], exist_ok=True)

@@ -573,6 +573,32 @@ int sa_env_dim(int which);
 int sa_env_warp(const float* S, const float* q, int B, int T, int n_c, float floor_rel, float max_gain_ln,
                 float* out, float* env, void* stream);
 
+/* ---- McAdams-coefficient anonymisation (sa_mcadams.hip; mcadams.py): VoicePrivacy's
+ * signal-processing baseline.  wav [B][N] fp32, alpha [B] fp32, n_valid [B] int32 -> out [B][N] fp32, out != wav.
+ * Frames of W = 320 at hop H = 160 under the periodic sqrt-Hann window w, T = (N + 159) / 160 + 1 of them, frame t
+ * over the samples [160 t - 160, 160 t + 160); a sample outside [0, n_valid_b) reads as 0.  Per frame, in fp64:
+ *     f = w x;  r_k = sum_j f[j] f[j + k], k = 0..20;  r_0 < 1e-10: silent (status 1), rec = f;  r_0 *= 1 + 1e-9;
+ *     a[0..20] by Levinson-Durbin; some |k_i| >= 1 or a prediction error <= 0: fallback (status 2), rec = f;
+ *     the 20 roots z of a by Aberth-Ehrlich from 0.9 exp(2 pi i (j + 0.25) / 20), stopped when the largest
+ *       correction is under 1e-14, given up (fallback) after 64 iterations;  a root is real when
+ *       |Im z| <= 1e-6 |z|, kept when Im z > 1e-6 |z|, dropped otherwise;  2 kept + real != 20: fallback;
+ *     a' = prod_real (1 - Re z x) prod_kept (1 - 2 |z| cos(phi^alpha) x + |z|^2 x^2), phi = arg z;
+ *     res = FIR(a) f, rec = IIR(1 / a') res, both from zero history;  the frame stored is fp32(rec w).
+ *   y[n] = F_t0[n - 160 t0 + 160] + F_{t0 + 1}[n - 160 t0], t0 = n / 160 (fp32);  out[n] = fp32(g_b y[n]) for
+ *   n < n_valid_b and 0 from there on;  level != 0: g_b = sqrt(sum x^2 / sum y^2) over n < n_valid_b (fp64, a fixed
+ *   order; 1 when either sum is 0), else 1.  alpha is read on the device: a value outside [0.25, 2] is taken as the
+ *   nearer bound, a NaN as 1; a row whose alpha is 1 is copied bit for bit below n_valid_b (gain 1, status 0).
+ *   n_valid_b is clamped to [0, N].  The same bits on every run.
+ *   ws: the caller's, 4 B T 320 + 8 (2 B ceil(N / C) + B) bytes, 8-byte aligned, C = sa_mcadams_dim(6); its
+ *     contents mean nothing between calls.  status: NULL, or int32 [B][T].  gain: NULL, or fp32 [B].
+ *   sa_mcadams_dim(which): 0 W 320, 1 H 160, 2 P 20, 3 frames per workgroup, 4 threads per workgroup, 5 the largest
+ *     iteration count 64, 6 samples per block of the level sums; else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer (status and gain may be NULL), B < 1 or > 65535 (grid.y), N < 1 or
+ *     > 2^30, T > 2^23. */
+int sa_mcadams_dim(int which);
+int sa_mcadams(const float* wav, const float* alpha, const int* n_valid, int B, int N, int level, float* out,
+               void* ws, int* status, float* gain, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -122,6 +122,7 @@ SYMBOLS = [
     "sa_gl_tile", "sa_mel_to_mag", "sa_gl_istft", "sa_gl_project",
     "sa_yin_dim", "sa_yin_f0", "sa_pitch_ratio", "sa_pitch_stretch_mag", "sa_pitch_resample",
     "sa_env_dim", "sa_env_warp",
+    "sa_mcadams_dim", "sa_mcadams",
 ]
 
 _lib = None

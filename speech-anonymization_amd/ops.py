@@ -1111,3 +1111,43 @@ def env_warp(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
                                  C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
             "sa_env_warp")
     return (out, env) if return_env else out
+
+
+# ---- McAdams-coefficient anonymisation (csrc/sa_mcadams.hip; mcadams.py) ----
+MC_W, MC_H, MC_CHUNK = 320, 160, 4096      # sa_mcadams_dim(0), (1), (6)
+
+_mc_in = functools.partial(_aug_in, family="McAdams")
+
+
+def mcadams_frames(N):
+    """T = (N + 159) // 160 + 1: the frames of N samples"""
+    return (int(N) + MC_H - 1) // MC_H + 1
+
+
+def mcadams_workspace(B, N, device):
+    """the workspace sa_mcadams takes: [B][T][320] fp32 frames, then the level sums (fp64 [B][ceil(N / 4096)][2]) and
+    gains (fp64 [B]), as one 8-byte-aligned buffer"""
+    words = B * mcadams_frames(N) * MC_W // 2 + 2 * B * (-(-int(N) // MC_CHUNK)) + B       # (320 B T is even)
+    return torch.empty(words, dtype=torch.float64, device=device)
+
+
+def mcadams(wav, alpha, n_valid, level=True, return_status=False):
+    """wav fp32 [B, N], alpha fp32 [B], n_valid int32 [B] -> (out fp32 [B, N], gain fp32 [B]): every frame's LPC poles
+    moved from angle phi to phi^alpha_b and the frame re-synthesised from its own residual; ``level``: the RMS over
+    the samples below n_valid_b brought back to the input's (sa_mcadams).  return_status: also int32 [B, T], 0 a frame
+    that was transformed, 1 a silent one, 2 one kept as it was (tests, reports)."""
+    if _mc_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    T = mcadams_frames(N)
+    if B > GL_MAX_B or N > PN_MAX_N or T > GL_MAX_T:
+        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
+    _mc_in(alpha, "alpha", shape=(B,))
+    _mc_in(n_valid, "n_valid", torch.int32, (B,))
+    out = torch.empty_like(wav)
+    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
+    status = torch.empty(B, T, dtype=torch.int32, device=wav.device) if return_status else None
+    ws = mcadams_workspace(B, N, wav.device)
+    L.check(L.load().sa_mcadams(_f(wav), _f(alpha), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws), _f(status),
+                                _f(gain), L.stream()), "sa_mcadams")
+    return (out, gain, status) if return_status else (out, gain)

@@ -164,14 +164,29 @@ def check_anonymize_options(settings, run_opts, environ=None):
     from .pitchnorm import check_formant_options
     formant = check_formant_options(settings)
     shift_only = "formant_ratio" in formant and not settings.get("pitch_norm")
-    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only:   # (those run no model)
+    mcadams = any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max"))
+    if mcadams:                                             # (no model, no checkpoint)
+        from .mcadams import check_mcadams_options
+        check_mcadams_options(settings)
+        for flag, given in (("--pitch_norm true", settings.get("pitch_norm")),
+                            ("--formant_ratio", "formant_ratio" in formant),
+                            ("--preserve_formants true", formant.get("preserve_formants")),
+                            ("--recon_ckpt", settings.get("recon_ckpt")),
+                            ("--passthrough true", settings.get("passthrough"))):
+            if given:
+                raise SystemExit(f"--mcadams and {flag} exclude each other: the McAdams transform runs no model, "
+                                 "no pitch change and no envelope warp")
+        shift_only = False
+    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only and not mcadams:
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
     if formant.get("preserve_formants") and not settings.get("pitch_norm"):
         raise SystemExit("--preserve_formants true goes with --pitch_norm true: it keeps the formants where the "
                          "pitch normalisation would move them")
     if "lifter" in formant and not settings.get("pitch_norm") and not shift_only:
         raise SystemExit("--lifter goes with --formant_ratio or --pitch_norm true --preserve_formants true")
-    if shift_only:
+    if mcadams:
+        pass
+    elif shift_only:
         if settings.get("passthrough"):
             raise SystemExit("--formant_ratio and --passthrough true exclude each other: one writes the "
                              "formant-shifted waveforms, the other the vocoded originals")
