@@ -31,6 +31,12 @@ and timing untouched, no Griffin-Lim.  It takes none of --pitch_norm, --formant_
 --recon_ckpt and --passthrough.  Its JSON line carries ``"mcadams": true`` and per utterance ``alpha``, ``gain``,
 ``silent_frames``, ``fallback_frames`` and ``peak``.
 
+``--report_stoi true`` adds, in any mode, the intelligibility of every waveform written against the waveform it was
+made from (speech_anonymization_amd.ops.stoi): per utterance ``stoi``, ``estoi`` (both null when the
+utterance has fewer than 30 frames within 40 dB of its loudest) and ``stoi_segments``, and ``stoi_mean`` and
+``estoi_mean`` over the scored utterances in the final object.  The two are compared over their common width, up to
+the smaller of their sample counts.
+
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
 sample count and the peak |wav| before write_audio clamps to [-1, 1]."""
@@ -41,7 +47,7 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, features, gender, mcadams, pitchnorm, vocoder
+from speech_anonymization_amd import data, features, gender, mcadams, metrics, pitchnorm, vocoder
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -70,17 +76,56 @@ def _f0_report(wav, lens):
     return mean.cpu().tolist(), (voiced.double() / frames.double()).cpu().tolist()
 
 
+class _StoiReport:
+    """--report_stoi true: STOI / ESTOI of every waveform about to be written against the input waveform"""
+
+    def __init__(self, settings):
+        self.on = bool(settings.get("report_stoi"))
+        self.stats = metrics.IntelligibilityStats()
+        self.rows = None
+
+    def score(self, ids, wavs, lens, out, counts):
+        """wavs, out [B, *] on the device, lens the relative lengths, counts the samples written per row"""
+        if not self.on:
+            return
+        from speech_anonymization_amd import ops
+        width = min(wavs.shape[1], out.shape[1])
+        n_in = [int(round(float(v) * wavs.shape[1])) for v in lens]
+        nv = torch.tensor([min(a, b, width) for a, b in zip(n_in, counts)], dtype=torch.int32).to(out.device)
+        s, e, _, seg = ops.stoi(wavs[:, :width].float().contiguous(), out[:, :width].float().contiguous(), nv)
+        self.stats.append(ids, s, e, seg)
+        self.rows = s.cpu().tolist(), e.cpu().tolist(), seg.cpu().tolist()
+
+    def keys(self, i):
+        if not self.on:
+            return {}
+        s, e, seg = (v[i] for v in self.rows)
+        return {"stoi": s if seg else None, "estoi": e if seg else None, "stoi_segments": seg}
+
+    def summary(self):
+        if not self.on:
+            return {}
+        tot = self.stats.summarize()
+        return {"stoi_mean": tot["stoi"], "estoi_mean": tot["estoi"]}
+
+
+def _counts(lens, N):
+    return [int(round(float(v) * N)) for v in lens]
+
+
 def _pitch_norm(settings, device, bs, seed):
     """--pitch_norm true: every utterance pitch-normalised and written, no model and no features"""
     formant = pitchnorm.check_formant_options(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
                                    momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant)
-    utts = []
+    utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
-        out = pn(wavs.to(device).contiguous(), lens)
+        wavs = wavs.to(device).contiguous()
+        out = pn(wavs, lens)
         rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         ratio = pn.last[0].cpu().tolist()
         out = out.cpu()
         N = out.shape[1]
@@ -90,9 +135,10 @@ def _pitch_norm(settings, device, bs, seed):
             utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0, "ratio": ratio[i]})
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
-                           "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}, **formant)))
+                           "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}, **formant, **sto.summary())))
 
 
 def _formant_shift(settings, device, bs, seed):
@@ -101,11 +147,13 @@ def _formant_shift(settings, device, bs, seed):
     fs = pitchnorm.FormantShifter(formant["formant_ratio"], n_iter=int(settings.get("n_iter", 32)),
                                   momentum=float(settings.get("momentum", 0.99)), seed=seed,
                                   lifter=formant.get("lifter", 30))
-    utts = []
+    utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
-        out = fs(wavs.to(device).contiguous(), lens)
+        wavs = wavs.to(device).contiguous()
+        out = fs(wavs, lens)
         rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         out = out.cpu()
         N = out.shape[1]
         for i, uid in enumerate(ids):
@@ -114,20 +162,23 @@ def _formant_shift(settings, device, bs, seed):
             utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0})
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True, "n_iter": fs.gl.n_iter,
-                           "seed": seed, "utterances": utts}, **formant)))
+                           "seed": seed, "utterances": utts}, **formant, **sto.summary())))
 
 
 def _mcadams(settings, device, bs, seed):
     """--mcadams A / --mcadams_min LO --mcadams_max HI: every utterance McAdams-transformed and written, no model"""
     opts = mcadams.check_mcadams_options(settings)
     mc = mcadams.McAdams(**opts)
-    utts = []
+    utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
-        out = mc(wavs.to(device).contiguous(), lens)
+        wavs = wavs.to(device).contiguous()
+        out = mc(wavs, lens)
         rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         alpha, gain, counts = (v.cpu().tolist() for v in mc.last)
         out = out.cpu()
         N = out.shape[1]
@@ -138,9 +189,10 @@ def _mcadams(settings, device, bs, seed):
                          "gain": gain[i], "silent_frames": counts[i][1], "fallback_frames": counts[i][2]})
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     shown = {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown)))
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown, **sto.summary())))
 
 
 def main(argv):
@@ -181,7 +233,7 @@ def main(argv):
                             seed=seed)
     pad = 36 if (mt != "fcae" and not passthrough) else None
     os.makedirs(settings["out_dir"], exist_ok=True)
-    utts = []
+    utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device)
@@ -200,6 +252,7 @@ def main(argv):
         wav, _, S = vocoder.invert_features(recon, nz, lens, frames=T, return_magnitude=True, gl=gl)
         sc = vocoder.spectral_convergence(wav, S).cpu()
         rep = _f0_report(wav, lens) if settings.get("report_f0") else None
+        sto.score(ids, wavs, lens, wav, [int(float(v) * wav.shape[1]) for v in lens])
         wav = wav.cpu()
         N = wav.shape[1]
         for i, uid in enumerate(ids):
@@ -209,10 +262,11 @@ def main(argv):
                          "peak": float(sig.abs().max()) if n else 0.0})
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+            utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
                       "recon_ckpt": settings.get("recon_ckpt"), "n_iter": gl.n_iter, "seed": seed,
-                      "utterances": utts}))
+                      "utterances": utts}, **sto.summary())))
 
 
 if __name__ == "__main__":

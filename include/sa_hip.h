@@ -599,6 +599,43 @@ int sa_mcadams_dim(int which);
 int sa_mcadams(const float* wav, const float* alpha, const int* n_valid, int B, int N, int level, float* out,
                void* ws, int* status, float* gain, void* stream);
 
+/* ---- STOI / ESTOI intelligibility scoring (sa_stoi.hip; ops.stoi): Taal et al. 2011 and
+ * Jensen & Taal 2016 on the original and the processed waveform, no pretrained model.  ref, deg [B][N] fp32 at
+ * 16 kHz, n_valid [B] int32 (clamped to [0, N]; a sample at or beyond n_valid_b reads as 0 in both signals) ->
+ * stoi, estoi [B] fp32, frames, segments [B] int32.  In exact terms (the kernels evaluate it in fp64), eps = 2^-52:
+ *   (1) to 10 kHz: n10 = (5 n_valid + 7) / 8;  x10[m] = sum_n x[n] h[8 m - 5 n] over |8 m - 5 n| <= 80 (at most 33
+ *       taps, ascending n);  h[k] = (5/8) sinc(k/8) I0(5 sqrt(1 - (k/80)^2)) / I0(5), k = -80..80: taps[k + 80],
+ *       161 doubles in device memory, built by the caller.  deg the same way.
+ *   (2) silent frames, decided on ref:  w[j] = 0.5 - 0.5 cos(2 pi (j + 1) / 257), j = 0..255;
+ *       F = (n10 - 256) / 128 + 1 frames when n10 >= 256, else 0, frame t over [128 t, 128 t + 256);
+ *       e_t = sum_j (w[j] x10[128 t + j])^2;  kept when e_t > 1e-4 max_t e_t (strict; 40 dB in the power domain);
+ *       K kept frames t_0 < ... < t_{K-1}.
+ *   (3) xs[n] = sum_{i : 128 i <= n < 128 i + 256} w[n - 128 i] x10[128 t_i + n - 128 i], n < 128 (K + 1); the same
+ *       t_i for deg.
+ *   (4) frame m = 0..K-1 of xs times w, zero-padded to 512, P[m][k] = |DFT|^2;
+ *       X[j][m] = sqrt(sum_{lo_j <= k < hi_j} P[m][k]) over the 15 third-octave bands (centres 150 2^(j/3) Hz, edges
+ *       at -+1/6 octave, rounded to the nearest bin): (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43)
+ *       (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219).  Y from deg.
+ *   (5) segments m = 30..K over the frames m - 30..m - 1: S = K - 29 when K >= 30, else 0.
+ *       STOI, per band and segment: alpha = |x| / (|y| + eps);  y' = min(alpha y, (1 + 10^0.75) x);
+ *         x~ = (x - mean x) / (|x - mean x| + eps), y~ the same of y';  d = sum x~ y~;  stoi = the mean of d over the
+ *         15 S pairs.
+ *       ESTOI, per segment on the 15 x 30 matrices: rows made zero-mean and unit-norm along time, then columns
+ *         along the bands, every norm + eps;  d_m = (1/30) sum of the element-wise product;  estoi = mean_m d_m.
+ *   A row with S = 0 (fewer than 30 kept frames, an all-zero ref, n_valid = 0) gets stoi = estoi = 0, segments = 0.
+ *   estoi, frames and segments may be NULL.  No atomics, every sum in a fixed order: the same bits on every run.
+ *   ws: the caller's, 8 B (2 M + 33 F) + 4 B (F + 2) bytes, 8-byte aligned, with M = (5 N + 7) / 8 and
+ *     F = (M - sa_stoi_dim(1)) / sa_stoi_dim(2) + 1 when M >= sa_stoi_dim(1), else 1; its contents mean nothing
+ *     between calls.
+ *   sa_stoi_dim(which): 0 the inner rate 10000, 1 the frame 256, 2 the hop 128, 3 the transform 512, 4 bands 15,
+ *     5 frames per segment 30, 6 taps 161, 7 compacted frames per workgroup of the band kernel, 8 segments per
+ *     workgroup, 9 threads per workgroup; else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer (estoi, frames and segments may be NULL), B < 1 or > 65535 (grid.y),
+ *     N < 1 or > 2^24. */
+int sa_stoi_dim(int which);
+int sa_stoi(const float* ref, const float* deg, const int* n_valid, int B, int N, const double* taps,
+            float* stoi, float* estoi, int* frames, int* segments, void* ws, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

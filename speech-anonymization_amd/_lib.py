@@ -123,6 +123,7 @@ SYMBOLS = [
     "sa_yin_dim", "sa_yin_f0", "sa_pitch_ratio", "sa_pitch_stretch_mag", "sa_pitch_resample",
     "sa_env_dim", "sa_env_warp",
     "sa_mcadams_dim", "sa_mcadams",
+    "sa_stoi_dim", "sa_stoi",
 ]
 
 _lib = None

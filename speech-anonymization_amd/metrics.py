@@ -48,3 +48,30 @@ class SimilarityMetricsStats:
             self.scores = torch.stack(self.scores)
         self.summary["average"] = torch.sum(self.scores) / self.scores.shape[0]
         return self.summary["average"]
+
+
+class IntelligibilityStats:
+    """STOI / ESTOI of a set of utterances (ops.stoi), accumulated on the device: the means are
+    over the rows that could be scored (segments > 0); the others are counted apart."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.ids = []
+        self.stoi_sum, self.estoi_sum, self.scored, self.total = 0.0, 0.0, 0, 0
+
+    def append(self, ids, stoi, estoi, segments):
+        """ids: a sequence of B names; stoi, estoi fp32 [B]; segments int [B] (tensors, on any one device)"""
+        ok = segments.detach() > 0
+        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+        self.ids.extend(ids)
+        self.stoi_sum = self.stoi_sum + torch.where(ok, stoi.detach().double(), zero).sum()
+        self.estoi_sum = self.estoi_sum + torch.where(ok, estoi.detach().double(), zero).sum()
+        self.scored = self.scored + ok.sum()
+        self.total += int(ok.numel())
+
+    def summarize(self):
+        n = int(self.scored)
+        return {"stoi": float(self.stoi_sum) / n if n else None, "estoi": float(self.estoi_sum) / n if n else None,
+                "scored": n, "unscored": self.total - n}

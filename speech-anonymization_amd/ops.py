@@ -1151,3 +1151,58 @@ def mcadams(wav, alpha, n_valid, level=True, return_status=False):
     L.check(L.load().sa_mcadams(_f(wav), _f(alpha), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws), _f(status),
                                 _f(gain), L.stream()), "sa_mcadams")
     return (out, gain, status) if return_status else (out, gain)
+
+
+# ---- STOI / ESTOI intelligibility scoring (csrc/sa_stoi.hip) ----
+STOI_W, STOI_H, STOI_SEG, STOI_HALF, STOI_MAX_N = 256, 128, 30, 80, 1 << 24      # sa_stoi_dim(1), (2), (5), (6) // 2
+
+_stoi_in = functools.partial(_aug_in, family="STOI")
+_stoi_taps = {}
+
+
+def stoi_taps(device):
+    """h[k + 80] = (5/8) sinc(k/8) I0(5 sqrt(1 - (k/80)^2)) / I0(5), k = -80..80, fp64: built on the host once per
+    device (the 16 kHz -> 10 kHz Kaiser windowed sinc)"""
+    device = torch.device(device)
+    t = _stoi_taps.get(device)
+    if t is None:
+        k = torch.arange(-STOI_HALF, STOI_HALF + 1, dtype=torch.float64)
+        five = torch.tensor(5.0, dtype=torch.float64)
+        h = 0.625 * torch.sinc(k / 8.0) * torch.special.i0(5.0 * torch.sqrt(1.0 - (k / STOI_HALF) ** 2))
+        t = _stoi_taps[device] = (h / torch.special.i0(five)).to(device)
+    return t
+
+
+def stoi_frames(N):
+    """(M, F): the 10 kHz samples and the frames of N samples at 16 kHz, as the workspace is laid out"""
+    M = (5 * int(N) + 7) // 8
+    return M, ((M - STOI_W) // STOI_H + 1 if M >= STOI_W else 1)
+
+
+def stoi_workspace(B, N, device):
+    """the workspace sa_stoi takes: 8 B (2 M + 33 F) + 4 B (F + 2) bytes as one 8-byte-aligned buffer"""
+    M, F = stoi_frames(N)
+    return torch.empty(B * (2 * M + 33 * F) + (B * (F + 2) + 1) // 2, dtype=torch.float64, device=device)
+
+
+def stoi(ref, deg, n_valid, extended=True):
+    """ref, deg fp32 [B, N] at 16 kHz, n_valid int32 [B] -> (stoi fp32 [B], estoi fp32 [B] | None, frames int32 [B],
+    segments int32 [B]): the short-time objective intelligibility of deg against ref and its extended form over the
+    samples below n_valid_b, both 0 where a row has fewer than 30 frames within 40 dB of its loudest (segments = 0).
+    Everything stays on the device (sa_stoi)."""
+    if _stoi_in(ref, "ref").dim() != 2 or ref.numel() == 0:
+        raise L.SaHipError(f"ref: expected [B, N] with B, N >= 1, got {tuple(ref.shape)}")
+    B, N = ref.shape
+    if B > GL_MAX_B or N > STOI_MAX_N:
+        raise L.SaHipError(f"ref: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {STOI_MAX_N}")
+    _stoi_in(deg, "deg", shape=(B, N))
+    _stoi_in(n_valid, "n_valid", torch.int32, (B,))
+    dev = ref.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    ext = torch.empty(B, dtype=torch.float32, device=dev) if extended else None
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    segments = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = stoi_workspace(B, N, dev)
+    L.check(L.load().sa_stoi(_f(ref), _f(deg), _f(n_valid), B, N, _f(stoi_taps(dev)), _f(out), _f(ext), _f(frames),
+                             _f(segments), _f(ws), L.stream()), "sa_stoi")
+    return out, ext, frames, segments

@@ -211,6 +211,11 @@ def check_anonymize_options(settings, run_opts, environ=None):
         raise SystemExit("--csv FILE and --synthetic N exclude each other")
     if not settings.get("csv") and not settings.get("synthetic"):
         raise SystemExit("one of --csv FILE and --synthetic N is required")
+    if settings.get("report_stoi") is not None:             # (any mode, 16 kHz only)
+        if not isinstance(settings["report_stoi"], bool):
+            raise SystemExit(f"--report_stoi {settings['report_stoi']!r}: true or false")
+        if settings["report_stoi"] and int(settings.get("sample_rate", 16000)) != 16000:
+            raise SystemExit("--report_stoi true scores 16 kHz waveforms only")
     if int(settings.get("n_iter", 32)) < 0:
         raise SystemExit(f"--n_iter {settings.get('n_iter')}: a count of iterations, 0 or more")
     if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:

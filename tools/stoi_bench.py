@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Times the STOI / ESTOI scorer (csrc/sa_stoi.hip, ops.stoi) at B = 32 utterances of 10 s: the
+synthetic set against its own McAdams(0.8) output.
+
+Device events around each call after a warm-up; the median of --steps calls.  Prints one JSON line (and writes it
+to --out):
+  stoi_ms, utts_per_s           sa_stoi through ops.stoi: the six launches and the workspace allocation
+  torch_ms                      the same computation written with torch operators in fp64 on the same GPU (conv1d for
+                                the resampler, unfold, rfft, a band matrix; the compaction row by row, since its
+                                shapes depend on the data), and max_abs_diff of its scores from sa_stoi's
+  ref_utts_per_s                the fp64 restatement (tests/stoi_ref.py, numpy) on the host, one row
+  stage_transform_ms, stage_stoi_ms, stage_stoi_to_host_ms
+                                anonymize.py --mcadams 0.8 --report_stoi true: the transform, the scorer as the script
+                                calls it (slices, n_valid, ops.stoi, the running means) and the copy of the three
+                                result rows to the host"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+SR = 16000
+BANDS = (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
+EPS = 2.0 ** -52
+
+
+def time_calls(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts)
+
+
+def _unit(v, dim):
+    v = v - v.mean(dim, keepdim=True)
+    return v / (v.pow(2).sum(dim, keepdim=True).sqrt() + EPS)
+
+
+def torch_stoi(ref, deg, nv, taps):
+    """the definition of include/sa_hip.h with torch operators, fp64 -> (stoi, estoi) [B] fp64"""
+    B, N = ref.shape
+    dev = ref.device
+    live = torch.arange(N, device=dev)[None, :] < nv[:, None]
+    x = torch.stack([ref, deg]).double() * live                                     # [2, B, N]
+    up = torch.zeros(2 * B, 1, 5 * N, dtype=torch.float64, device=dev)
+    up[:, 0, ::5] = x.reshape(2 * B, N)
+    x10 = torch.nn.functional.conv1d(up, taps.reshape(1, 1, -1), stride=8, padding=80).reshape(2, B, -1)
+    w = 0.5 - 0.5 * torch.cos(2.0 * torch.pi * (torch.arange(256, dtype=torch.float64, device=dev) + 1.0) / 257.0)
+    fr = x10.unfold(2, 256, 128) * w                                                # [2, B, F, 256]
+    n10 = (5 * nv.long() + 7) // 8
+    F_b = torch.where(n10 >= 256, (n10 - 256) // 128 + 1, torch.zeros_like(n10))
+    valid = torch.arange(fr.shape[2], device=dev)[None, :] < F_b[:, None]
+    e = torch.where(valid, fr[0].pow(2).sum(-1), torch.full((), -1.0, dtype=torch.float64, device=dev))
+    keep = valid & (e > 1e-4 * e.max(1, keepdim=True).values)
+    bands = torch.zeros(257, 15, dtype=torch.float64, device=dev)
+    for j in range(15):
+        bands[BANDS[j]:BANDS[j + 1], j] = 1.0
+    zero = torch.zeros(2, 128, dtype=torch.float64, device=dev)
+    st, es = torch.zeros(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.float64, device=dev)
+    for b in range(B):
+        fk = fr[:, b][:, keep[b]]                                                   # [2, K, 256]
+        K = fk.shape[1]
+        if K < 30:
+            continue
+        xs = torch.cat([fk[:, :, :128].reshape(2, -1), zero], 1) + torch.cat([zero, fk[:, :, 128:].reshape(2, -1)], 1)
+        spec = torch.fft.rfft(xs.unfold(1, 256, 128) * w, 512)
+        X = (spec.real.pow(2) + spec.imag.pow(2)).matmul(bands).sqrt()              # [2, K, 15]
+        seg = X.unfold(1, 30, 1)                                                    # [2, S, 15, 30]
+        xb, yb = seg[0], seg[1]
+        alpha = xb.pow(2).sum(-1, keepdim=True).sqrt() / (yb.pow(2).sum(-1, keepdim=True).sqrt() + EPS)
+        yc = torch.minimum(alpha * yb, (1.0 + 10.0 ** 0.75) * xb)
+        st[b] = (_unit(xb, -1) * _unit(yc, -1)).sum(-1).mean()
+        es[b] = (_unit(_unit(xb, -1), -2) * _unit(_unit(yb, -1), -2)).sum((-1, -2)).mean() / 30.0
+    return st, es
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--alpha", type=float, default=0.8)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stoi_bench.json"))
+    a = ap.parse_args()
+    assert a.steps >= 20, "the median of at least 20 calls"
+    dev = torch.device("cuda:0")
+    from speech_anonymization_amd import data, mcadams, metrics, ops
+    from tests import stoi_ref as R
+    B, N = a.B, int(a.seconds * SR)
+    wav_cpu, lens_cpu = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N))).sig
+    wav, lens = wav_cpu.to(dev), lens_cpu.to(dev)
+    nv = torch.round(lens.double() * N).to(torch.int32)
+    mc = mcadams.McAdams(a.alpha)
+    deg = mc(wav, lens_cpu)
+
+    s, e, frames, segments = ops.stoi(wav, deg, nv)
+    ms = time_calls(lambda: ops.stoi(wav, deg, nv), a.warmup, a.steps)
+    taps = ops.stoi_taps(dev)
+    ts, te = torch_stoi(wav, deg, nv, taps)
+    ms_torch = time_calls(lambda: torch_stoi(wav, deg, nv, taps), a.warmup, a.steps)
+    out = {"B": B, "N": N, "alpha": a.alpha, "steps": a.steps, "frames": int(frames.sum()),
+           "segments": int(segments.sum()), "stoi_mean": round(float(s.mean()), 6),
+           "estoi_mean": round(float(e.mean()), 6), "stoi_ms": round(ms, 4), "utts_per_s": round(B / ms * 1e3),
+           "torch_ms": round(ms_torch, 4),
+           "max_abs_diff": float(f"{max(float((s.double() - ts).abs().max()), float((e.double() - te).abs().max())):.3e}")}
+
+    t0 = time.perf_counter()
+    ref = R.stoi(wav_cpu[:1].numpy(), deg[:1].cpu().numpy(), nv[:1].cpu().numpy())
+    out["ref_utts_per_s"] = round(1.0 / (time.perf_counter() - t0), 2)
+    out["max_abs_diff_vs_ref_first_row"] = float(f"{max(abs(float(s[0]) - ref.stoi[0]), abs(float(e[0]) - ref.estoi[0])):.3e}")
+
+    counts = [int(round(float(v) * N)) for v in lens_cpu]
+    ids = [str(i) for i in range(B)]
+    stats = metrics.IntelligibilityStats()
+
+    def score():
+        n = torch.tensor([min(c, N) for c in counts], dtype=torch.int32).to(dev)
+        r = ops.stoi(wav[:, :N].float().contiguous(), deg[:, :N].float().contiguous(), n)
+        stats.append(ids, r[0], r[1], r[3])
+        return r
+
+    for name, fn in (("stage_transform_ms", lambda: mc(wav, lens_cpu)), ("stage_stoi_ms", score),
+                     ("stage_stoi_to_host_ms", lambda: (s.cpu().tolist(), e.cpu().tolist(), segments.cpu().tolist()))):
+        out[name] = round(time_calls(fn, a.warmup, a.steps), 4)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
