@@ -4,6 +4,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
 
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
+        [--phase griffin_lim|vocoder]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
 normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
@@ -30,6 +31,11 @@ model and reads no checkpoint either: OUT receives the McAdams-transformed wavef
 and timing untouched, no Griffin-Lim.  It takes none of --pitch_norm, --formant_ratio, --preserve_formants,
 --recon_ckpt and --passthrough.  Its JSON line carries ``"mcadams": true`` and per utterance ``alpha``, ``gain``,
 ``silent_frames``, ``fallback_frames`` and ``peak``.
+
+``--phase vocoder`` (with --pitch_norm true and/or --formant_ratio X) carries the input's own phases through the
+stretch instead of reconstructing them with Griffin-Lim (speech_anonymization_amd.ops.pv_synth):
+one pass, no iterations, no random numbers.  It takes none of --recon_ckpt, --passthrough and --mcadams, which have
+no input phase to carry.  The JSON line then carries ``"phase": "vocoder"`` and ``"n_iter": null``.
 
 ``--report_stoi true`` adds, in any mode, the intelligibility of every waveform written against the waveform it was
 made from (speech_anonymization_amd.ops.stoi): per utterance ``stoi``, ``estoi`` (both null when the
@@ -116,9 +122,10 @@ def _counts(lens, N):
 def _pitch_norm(settings, device, bs, seed):
     """--pitch_norm true: every utterance pitch-normalised and written, no model and no features"""
     formant = pitchnorm.check_formant_options(settings)
+    phase = pitchnorm.check_phase_option(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
-                                   momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant)
+                                   momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant, **phase)
     utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
@@ -138,15 +145,17 @@ def _pitch_norm(settings, device, bs, seed):
             utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
-                           "n_iter": pn.gl.n_iter, "seed": seed, "utterances": utts}, **formant, **sto.summary())))
+                           "n_iter": pn.gl.n_iter if pn.gl else None, "seed": seed, "utterances": utts}, **formant,
+                          **phase, **sto.summary())))
 
 
 def _formant_shift(settings, device, bs, seed):
     """--formant_ratio X on its own: every utterance's envelope scaled by X and written, no model and no features"""
     formant = pitchnorm.check_formant_options(settings)
+    phase = pitchnorm.check_phase_option(settings)
     fs = pitchnorm.FormantShifter(formant["formant_ratio"], n_iter=int(settings.get("n_iter", 32)),
                                   momentum=float(settings.get("momentum", 0.99)), seed=seed,
-                                  lifter=formant.get("lifter", 30))
+                                  lifter=formant.get("lifter", 30), **phase)
     utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
@@ -164,8 +173,9 @@ def _formant_shift(settings, device, bs, seed):
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
             utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True, "n_iter": fs.gl.n_iter,
-                           "seed": seed, "utterances": utts}, **formant, **sto.summary())))
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True,
+                           "n_iter": fs.gl.n_iter if fs.gl else None, "seed": seed, "utterances": utts}, **formant,
+                          **phase, **sto.summary())))
 
 
 def _mcadams(settings, device, bs, seed):

@@ -636,6 +636,34 @@ int sa_stoi_dim(int which);
 int sa_stoi(const float* ref, const float* deg, const int* n_valid, int B, int N, const double* taps,
             float* stoi, float* estoi, int* frames, int* segments, void* ws, void* stream);
 
+/* ---- phase-vocoder resynthesis (sa_phasevoc.hip; ops.pv_synth): the stretch of
+ * sa_pitch_stretch_mag with the input's phases carried through it.  R [B][T][201] complex64 (the STFT of the padded
+ * waveform), ratio [B] fp32, read on the device as sa_pitch_stretch_mag reads it (outside [0.5, 2]: the nearer bound,
+ * NaN: 1) -> C [B][Tout][201] complex64, C != R.  Phases in turns (1 turn = 2 pi), fp64:
+ *     theta[i][k] = atan2(im, re) / (2 pi) of R[i][k], formed in fp64 from the fp32 values (IEEE signed zeros;
+ *       (0, 0) -> 0);
+ *     T'_b, pos, i_s = min(floor(pos), T - 2) and a_s of output frame s exactly as in sa_pitch_stretch_mag;
+ *     phi'[0][k] = theta[0][k] mod 1;  phi'[t' + 1][k] = (phi'[t'][k] + theta[i_t' + 1][k] - theta[i_t'][k]) mod 1
+ *       for t' + 1 < T'_b (x mod 1 = x - floor(x): the accumulator never leaves [0, 1]);
+ *     C[t'][k] = S'[t'][k] (cospi(2 phi'), sinpi(2 phi')), formed in fp64, each component rounded once to fp32;
+ *       0 for t' >= T'_b.
+ *   S: the magnitudes S' [B][Tout][201] fp32 (e.g. sa_env_warp's output), or NULL: S' = (1 - a) |R_i| + a |R_{i+1}|,
+ *     bit for bit what sa_pitch_stretch_mag writes.  phase: NULL, or fp64 [B][Tout][201] to receive phi' (0 for
+ *     t' >= T'_b; tests).  At ratio 1 the sum telescopes: C = R S' / |R|.
+ *   The sum runs as a chunked scan of three launches (chunk totals, chunk offsets, synthesis): sums of a different
+ *   grouping than the recurrence above, in a fixed order -- the same bits on every run, within (Tout + 8) 2^-50
+ *   turns of the recurrence.  No atomics, and no workgroup waits on another.
+ *   ws: the caller's, sa_pv_workspace_bytes(B, Tout) = 8 B ceil(Tout / Tc) 201 bytes, 8-byte aligned, Tc =
+ *     sa_pv_dim(3); its contents mean nothing between calls.  (-EINVAL for a B or Tout sa_pv_synth refuses.)
+ *   sa_pv_dim(which): 0 n_fft 400, 1 hop 160, 2 bins 201, 3 output frames per chunk Tc, 4 threads per workgroup;
+ *     else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer (S and phase may be NULL), B < 1 or > 65535 (grid.y), T < 2 or
+ *     > 2^23, Tout < 1 or > 2^23. */
+int sa_pv_dim(int which);
+long long sa_pv_workspace_bytes(int B, int Tout);
+int sa_pv_synth(const void* R, const float* S, const float* ratio, int B, int T, int Tout, void* C, double* phase,
+                void* ws, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -124,6 +124,7 @@ SYMBOLS = [
     "sa_env_dim", "sa_env_warp",
     "sa_mcadams_dim", "sa_mcadams",
     "sa_stoi_dim", "sa_stoi",
+    "sa_pv_dim", "sa_pv_synth",
 ]
 
 _lib = None
@@ -144,6 +145,7 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         for s in SYMBOLS:
             getattr(_lib, s).restype = C.c_int
+        _lib.sa_pv_workspace_bytes.restype = C.c_longlong     # (the one entry point that does not return an int)
         for i, rec in enumerate((SaConvArgs, SaWgradArgs, SaEwArgs, SaPackDesc, SaTaps, SaBiasMulti, SaWredMulti, SaFlats)):
             if _lib.sa_abi_sizeof(i) != C.sizeof(rec):
                 raise SaHipError(f"{rec.__name__}: binding has {C.sizeof(rec)} bytes, {LIB_PATH} "

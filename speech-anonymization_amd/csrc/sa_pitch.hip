@@ -6,6 +6,7 @@
 //   sa_pitch_resample     windowed-sinc read of the re-synthesised waveform at n r_b (duration back, pitch times r_b)
 // Plain fp32 FMAs (positions and filter weights in fp64), no atomics, the same bits on every run.
 #include "sa_common.h"
+#include "sa_pitch_stretch.h"
 #include <errno.h>
 #include <limits.h>
 
@@ -21,10 +22,7 @@
 #define YIN_LAGS (YIN_K * SA_WAVE)       // 320 lag slots, 1..266 of them used
 #define YIN_XS ((YIN_G - 1) * YIN_HOP + YIN_W + YIN_LAGS + YIN_K + 3)   // 1848: what the idle slots read too
 #define YIN_DP (YIN_LAGS + 2)            // d' slots per frame in LDS
-#define PN_MAX_B 65535                   // grid.y
 #define PN_MAX_N (1 << 30)
-#define PN_MAX_T (1 << 23)               // the vocoder's bound
-#define PN_NBIN 201
 #define RS_TILE 256                      // outputs per workgroup of sa_pitch_resample
 #define RS_HALF 16.0                     // filter half-width in periods of the cut-off
 #define RS_SPAN (2 * RS_TILE + 2 * 32 + 2)
@@ -41,10 +39,6 @@ extern "C" int sa_yin_dim(int which) {
     case 7: return RS_TILE;
     default: return -EINVAL;
   }
-}
-
-__device__ static inline float pn_ratio(float r) {         // a ratio no kernel can be led out of bounds by
-  return r >= 0.5f && r <= 2.0f ? r : (r > 2.0f ? 2.0f : (r < 0.5f ? 0.5f : 1.0f));
 }
 
 // ---- F0 ----------------------------------------------------------------------------------------------
@@ -218,15 +212,12 @@ __global__ __launch_bounds__(256) void sa_pitch_stretch_mag_kernel(const float2*
   if (e >= Tout * PN_NBIN) return;
   const int tp = e / PN_NBIN, k = e - tp * PN_NBIN;
   const double r = (double)pn_ratio(ratio[b]);
-  const int Tb = (int)ceil((double)(T - 1) * r) + 1;
   float v = 0.0f;
-  if (tp < Tb) {
-    const double pos = fmin((double)tp / r, (double)(T - 1));
-    const int i = min((int)floor(pos), T - 2);
-    const float a = (float)(pos - (double)i);
+  if (tp < pn_frames(T, r)) {
+    float a;
+    const int i = pn_position(tp, r, T, &a);
     const float2 p = R[((size_t)b * T + i) * PN_NBIN + k], q = R[((size_t)b * T + i + 1) * PN_NBIN + k];
-    const float mp = sqrtf(fmaf(p.x, p.x, p.y * p.y)), mq = sqrtf(fmaf(q.x, q.x, q.y * q.y));
-    v = fmaf(a, mq, (1.0f - a) * mp);
+    v = pn_mix(a, pn_mag(p), pn_mag(q));           // (sa_pitch_stretch.h: sa_pv_synth writes the same bits)
   }
   S[((size_t)b * Tout) * PN_NBIN + e] = v;
 }

@@ -1081,6 +1081,35 @@ def pitch_resample(y, ratio, n_valid, Nout):
     return out
 
 
+# ---- phase-vocoder resynthesis (csrc/sa_phasevoc.hip; pitchnorm.py) ----
+_pv_in = functools.partial(_aug_in, family="phase-vocoder")
+
+
+def pv_synth(R, ratio, Tout, S=None, return_phase=False):
+    """R complex64 [B, T, 201] (vocoder.stft of the padded waveform), ratio fp32 [B] -> C complex64 [B, Tout, 201]: the
+    stretch of pitch_stretch_mag with R's own phases carried through it -- frame t' < ceil((T - 1) r_b) + 1 has the
+    phase theta[0] + sum_{s < t'} (theta[i_s + 1] - theta[i_s]) and the magnitude S[b, t'] (fp32 [B, Tout, 201], e.g.
+    env_warp's output) or, without S, what pitch_stretch_mag gives bit for bit; zero from there on (sa_pv_synth).
+    return_phase: also the phases in turns, fp64 [B, Tout, 201] (tests).  Everything stays on the device."""
+    if _pv_in(R, "R", torch.complex64).dim() != 3 or R.shape[2] != 201:
+        raise L.SaHipError(f"R: expected [B, T, 201], got {tuple(R.shape)}")
+    B, T, _ = R.shape
+    Tout = int(Tout)
+    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T or Tout < 1 or Tout > GL_MAX_T:
+        raise L.SaHipError(f"pv_synth: [B, T] = [{B}, {T}], Tout = {Tout} -- B in 1..{GL_MAX_B} (a grid extent), T in "
+                           f"2..{GL_MAX_T}, Tout in 1..{GL_MAX_T}")
+    _pv_in(ratio, "ratio", shape=(B,))
+    if S is not None:
+        _pv_in(S, "S", shape=(B, Tout, 201))
+    lib = L.load()
+    Cx = torch.empty(B, Tout, 201, dtype=torch.complex64, device=R.device)
+    phase = torch.empty(B, Tout, 201, dtype=torch.float64, device=R.device) if return_phase else None
+    ws = torch.empty(lib.sa_pv_workspace_bytes(B, Tout) // 8, dtype=torch.float64, device=R.device)
+    L.check(lib.sa_pv_synth(_f(R), _f(S), _f(ratio), B, T, Tout, _f(Cx), _f(phase), _f(ws), L.stream()),
+            "sa_pv_synth")
+    return (Cx, phase) if return_phase else Cx
+
+
 # ---- spectral envelope and formant warp (csrc/sa_envelope.hip; pitchnorm.py) ----
 ENV_NC_MAX = 64
 LN10_OVER_20 = 0.11512925464970229       # dB -> natural log of an amplitude ratio

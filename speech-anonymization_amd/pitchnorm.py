@@ -15,7 +15,11 @@ spectrogram.
 Formants apart from pitch: with ``formant_ratio`` beta (``preserve_formants``: beta = 1) the
 stretched magnitudes pass through sa_env_warp with q_b = r_b / beta before Griffin-Lim -- their cepstral envelope
 is read q_b times as far up, so that after the resampling the harmonics sit at r_b f and the envelope at beta f.
-``FormantShifter`` is the same warp with no pitch change at all: |STFT| -> warp by 1 / beta -> Griffin-Lim."""
+``FormantShifter`` is the same warp with no pitch change at all: |STFT| -> warp by 1 / beta -> Griffin-Lim.
+
+The input's own phase: with ``phase="vocoder"`` both classes carry the phases of STFT(wav) through
+the stretch (sa_pv_synth, a phase vocoder) and invert once, in place of Griffin-Lim's 32 iterations from random
+phases: stretch [-> warp] -> sa_pv_synth -> one sa_gl_istft.  ``"griffin_lim"`` stays the default."""
 import math
 
 import torch
@@ -29,6 +33,7 @@ R_LOW, R_HIGH = 0.5, 2.0                     # what the kernels take
 TARGET_LOW, TARGET_HIGH = 60.0, 400.0        # the tracker's range: 16000 / tau_max .. 16000 / tau_min
 BETA_LOW, BETA_HIGH = 0.5, 2.0               # formant ratios: q = r / beta stays in the [0.25, 4] the kernel takes
 LIFTER_MAX = 64                              # sa_env_dim(3)
+PHASES = ("griffin_lim", "vocoder")          # where the re-synthesis takes its phases from
 
 
 def f0_track(wav, threshold=0.15):
@@ -58,24 +63,33 @@ def envelope_settings(who, preserve_formants, formant_ratio, lifter, floor_rel, 
     return beta, int(lifter), float(floor_rel), float(max_gain_db)
 
 
+def phase_setting(who, phase):
+    if phase not in PHASES:
+        raise ValueError(f"{who}: phase {phase!r}: one of {', '.join(PHASES)} expected")
+    return phase
+
+
 class PitchNormalizer:
     """wavs [B, N] (device), relative lengths [B] -> wavs of the same shape whose voiced F0 has mean ~ target_hz;
     samples from round(lens_b N) on are zero.  ``last``: (ratio, mean f0, voiced frames) of the last batch, on
     the device.  ``formant_ratio`` beta (``preserve_formants=True``: 1) scales the spectral envelope by beta
-    instead of by the pitch ratio; without either the envelope moves with the pitch and no warp is launched."""
+    instead of by the pitch ratio; without either the envelope moves with the pitch and no warp is launched.
+    ``phase="vocoder"`` carries the input's phases through the stretch instead of running Griffin-Lim: no iterations,
+    no random numbers (n_iter, momentum and seed are then unused, and ``gl`` is None)."""
 
     def __init__(self, target_hz=170.0, n_iter=32, momentum=0.99, seed=1, r_min=0.5, r_max=2.0, min_voiced=5,
                  threshold=0.15, preserve_formants=False, formant_ratio=None, lifter=30, floor_rel=1e-4,
-                 max_gain_db=40.0):
+                 max_gain_db=40.0, phase="griffin_lim"):
         self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
             "PitchNormalizer", preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db)
+        self.phase = phase_setting("PitchNormalizer", phase)
         if not TARGET_LOW <= float(target_hz) <= TARGET_HIGH:
             raise ValueError(f"PitchNormalizer: target_hz {target_hz} in {TARGET_LOW:g}..{TARGET_HIGH:g} expected")
         if not R_LOW <= float(r_min) <= float(r_max) <= R_HIGH:
             raise ValueError(f"PitchNormalizer: {R_LOW} <= r_min {r_min} <= r_max {r_max} <= {R_HIGH} expected")
         self.target_hz, self.r_min, self.r_max = float(target_hz), float(r_min), float(r_max)
         self.min_voiced, self.threshold = int(min_voiced), float(threshold)
-        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed)
+        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed) if phase == "griffin_lim" else None
         self.last = None
 
     @torch.no_grad()
@@ -102,11 +116,17 @@ class PitchNormalizer:
         wp = torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs
         R = vocoder.stft(wp.contiguous())
         Tout = max(stretched_frames(R.shape[1], r) for r in host)
-        S = ops.pitch_stretch_mag(R, ratio, Tout)
+        S = None                                             # (the vocoder path forms the plain stretch itself)
+        if self.gl is not None or self.formant_ratio is not None:
+            S = ops.pitch_stretch_mag(R, ratio, Tout)
         if self.formant_ratio is not None:                   # q_b = r_b / beta, formed on the device
             q = (ratio.float() / self.formant_ratio).contiguous()
             S = ops.env_warp(S, q, self.lifter, self.floor_rel, self.max_gain_db)
-        y = self.gl(S)
+        if self.gl is not None:
+            y = self.gl(S)
+        else:
+            w, tw, _ = vocoder.tables(wavs.device)
+            y = ops.gl_istft(ops.pv_synth(R, ratio, Tout, S), w, tw)
         n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N).to(torch.int32)
         return ops.pitch_resample(y, ratio, n_valid, N)
 
@@ -114,14 +134,18 @@ class PitchNormalizer:
 class FormantShifter:
     """wavs [B, N] (device), relative lengths [B] -> wavs of the same shape whose spectral envelope is scaled along
     frequency by ``formant_ratio`` while the pitch stays: |STFT| -> sa_env_warp at q = 1 / beta -> Griffin-Lim.  No
-    stretch, no resampling, no tracker, and no device-to-host copy.  Samples from round(lens_b N) on are zero."""
+    stretch, no resampling, no tracker, and no device-to-host copy.  Samples from round(lens_b N) on are zero.
+    ``phase="vocoder"`` keeps the input's phases under the warped magnitudes (sa_pv_synth at ratio 1) and inverts
+    once, instead of running Griffin-Lim (``gl`` is then None)."""
 
-    def __init__(self, formant_ratio, n_iter=32, momentum=0.99, seed=1, lifter=30, floor_rel=1e-4, max_gain_db=40.0):
+    def __init__(self, formant_ratio, n_iter=32, momentum=0.99, seed=1, lifter=30, floor_rel=1e-4, max_gain_db=40.0,
+                 phase="griffin_lim"):
         if formant_ratio is None:
             raise ValueError("FormantShifter: formant_ratio expected")
         self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
             "FormantShifter", False, formant_ratio, lifter, floor_rel, max_gain_db)
-        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed)
+        self.phase = phase_setting("FormantShifter", phase)
+        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed) if phase == "griffin_lim" else None
 
     @torch.no_grad()
     def __call__(self, wavs, lens):
@@ -135,7 +159,11 @@ class FormantShifter:
         one = torch.ones(B, dtype=torch.float32, device=wavs.device)
         S = ops.pitch_stretch_mag(R, one, R.shape[1])        # |R| exactly: the stretch at ratio 1
         S = ops.env_warp(S, one / self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db)
-        y = self.gl(S)[:, :N]
+        if self.gl is not None:
+            y = self.gl(S)[:, :N]
+        else:
+            w, tw, _ = vocoder.tables(wavs.device)
+            y = ops.gl_istft(ops.pv_synth(R, one, R.shape[1], S), w, tw)[:, :N]
         n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N)
         live = torch.arange(N, device=wavs.device)[None, :] < n_valid[:, None]
         return torch.where(live, y, torch.zeros((), dtype=y.dtype, device=y.device)).contiguous()
@@ -172,6 +200,18 @@ def check_formant_options(settings, block=None):
     return given
 
 
+def check_phase_option(settings, block=None):
+    """the ``phase`` of a recipe's ``pitch_norm:`` block (if any) under the top-level override -> a dict that carries
+    the key only when it was given; anything but griffin_lim and vocoder is refused in one line"""
+    value = settings.get("phase", (block or {}).get("phase"))
+    if value is None:
+        return {}
+    if value not in PHASES:
+        raise SystemExit(f"--phase {value}: griffin_lim (phases reconstructed by Griffin-Lim, the default) or vocoder "
+                         "(the input's own phases carried through the stretch)")
+    return {"phase": value}
+
+
 def check_pitch_target(value):
     target = float(value)
     if not TARGET_LOW <= target <= TARGET_HIGH:
@@ -197,4 +237,5 @@ def check_pitch_options(settings, run_opts, environ=None):
                          "for it")
     if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
         raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
-    return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn))
+    return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn),
+                **check_phase_option(settings, pn))

@@ -161,8 +161,9 @@ def check_anonymize_options(settings, run_opts, environ=None):
     import os
     environ = os.environ if environ is None else environ
     mt = settings.get("model_type")
-    from .pitchnorm import check_formant_options
+    from .pitchnorm import check_formant_options, check_phase_option
     formant = check_formant_options(settings)
+    phase = check_phase_option(settings)
     shift_only = "formant_ratio" in formant and not settings.get("pitch_norm")
     mcadams = any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max"))
     if mcadams:                                             # (no model, no checkpoint)
@@ -177,6 +178,14 @@ def check_anonymize_options(settings, run_opts, environ=None):
                 raise SystemExit(f"--mcadams and {flag} exclude each other: the McAdams transform runs no model, "
                                  "no pitch change and no envelope warp")
         shift_only = False
+    if phase.get("phase") == "vocoder":                     # (a real waveform's phases only)
+        for flag, given in (("--mcadams", mcadams), ("--passthrough true", settings.get("passthrough")),
+                            ("--recon_ckpt", settings.get("recon_ckpt"))):
+            if given:
+                raise SystemExit(f"--phase vocoder and {flag} exclude each other: there is no input phase to carry")
+        if not settings.get("pitch_norm") and not shift_only:
+            raise SystemExit("--phase vocoder goes with --pitch_norm true or --formant_ratio: the paths that "
+                             "re-synthesise a waveform they were given")
     if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only and not mcadams:
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
     if formant.get("preserve_formants") and not settings.get("pitch_norm"):

@@ -8,6 +8,9 @@ mode the mean STOI, ESTOI, voiced-mean F0 and voiced share of what it wrote (DES
   pitch_norm_preserve     the same with the formants kept in place
   formant_ratio_1.15      the envelope scaled by 1.15, the pitch untouched
   mcadams_0.8             the McAdams transform, alpha = 0.8
+  pitch_norm_pv, pitch_norm_preserve_pv, formant_ratio_1.15_pv
+                          the three Griffin-Lim rows with --phase vocoder: the input's own phases carried through
+                          
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech.
@@ -27,7 +30,10 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("pitch_norm", ["--pitch_norm", "true"]),
          ("pitch_norm_preserve", ["--pitch_norm", "true", "--preserve_formants", "true"]),
          ("formant_ratio_1.15", ["--formant_ratio", "1.15"]),
-         ("mcadams_0.8", ["--mcadams", "0.8"]))
+         ("mcadams_0.8", ["--mcadams", "0.8"]),
+         ("pitch_norm_pv", ["--pitch_norm", "true", "--phase", "vocoder"]),
+         ("pitch_norm_preserve_pv", ["--pitch_norm", "true", "--preserve_formants", "true", "--phase", "vocoder"]),
+         ("formant_ratio_1.15_pv", ["--formant_ratio", "1.15", "--phase", "vocoder"]))
 
 
 def _mean(vals):
