@@ -664,6 +664,52 @@ long long sa_pv_workspace_bytes(int B, int Tout);
 int sa_pv_synth(const void* R, const float* S, const float* ratio, int B, int T, int Tout, void* C, double* phase,
                 void* ws, void* stream);
 
+/* ---- F0-contour pitch modification (sa_contour.hip, with one variant each in sa_phasevoc.hip and sa_envelope.hip;
+ * DESIGN section 20): a ratio per frame on the phase-vocoder path, so that the output contour is target + gamma (f0
+ * - mean).  HOP 160.  Two tables per row carry it, both on the device:
+ *     rho_q [B][T] int32: the ratio of frame t in units of 2^-16, in [2^15, 2^17];
+ *     Q [B][T] int64: the time map, Q[0] = 0, Q[t + 1] = Q[t] + w[t], w[t] = rho_q[t] + rho_q[t + 1] (the mean ratio
+ *       of hop interval t in units of 2^-17);  T'_b = ((Q[T - 1] + 2^17 - 1) >> 17) + 1 output frames.
+ *   Every kernel clamps what it reads from them (rho_q to [2^15, 2^17], w to [2^16, 2^18], Q[T - 1] to [0, (T - 1)
+ *   2^18]) and every index it derives (i to [0, T - 2], a to [0, 1]).
+ *   sa_pitch_contour: f0 [B][T] (sa_yin_f0 of the padded waveform, T >= 2) -> rho_q, Q, Tq [B] = T'_b, and mean [B],
+ *     voiced [B] exactly as sa_pitch_ratio forms them (the first round(lens_b N) / 160 + 1 frames count; a frame
+ *     beyond them is not voiced whatever it holds).  A row with voiced_b < min_voiced, or with no voiced frame, gets
+ *     rho_q = 2^16 throughout.  Otherwise, in fp64, for every t < T:
+ *       f^[t] = f0[t] on a voiced frame, else f0[l] + (f0[n] - f0[l]) (t - l) / (n - l) between the last voiced
+ *         frame l before t and the first one n after it, or the value of the one that exists;
+ *       f~[t] = sum_{|j| <= s} (s + 1 - |j|) f^[clamp(t + j, 0, T - 1)] / (s + 1)^2, j ascending, s = smooth;
+ *       rho_q[t] = rint(2^16 clamp(max(60, target + gamma (f~[t] - mean_b)) / f~[t], r_min, r_max)).
+ *     One workgroup per row walks T in passes of sa_contour_dim(0) frames: l and n by a max- and a min-scan of the
+ *     voiced indices, Q by an int64 scan, each with a carry between the passes.
+ *   sa_pv_synth_map: sa_pv_synth with the stretch positions of the time map.  Output frame t' < T'_b, X = t' 2^17:
+ *     X >= Q[T - 1]: i = T - 2, a = 1; else i the largest index <= T - 2 with Q[i] <= X and a = (double)(X - Q[i]) /
+ *     (double)w[i] rounded once to fp32.  Phases and synthesis as in sa_pv_synth; the magnitude is (1 - a) M[i] +
+ *     a M[i + 1] with M [B][T][201] fp32 ON THE INPUT GRID, or |R| when M is NULL.  At a constant rho_q = r 2^16 it
+ *     writes sa_pv_synth's bits at ratio r.  ws: sa_pv_workspace_bytes(B, Tout).
+ *   sa_env_warp_frames: sa_env_warp with q [B][T], one factor per frame; for q constant along t, the same bits.
+ *   sa_pitch_resample_map: y [B][Nin] -> out [B][Nout].  For n < n_valid[b], t = min(n / 160, T - 2), u = n - 160 t:
+ *     Z = 160 Q[t] + w[t] u, ip = Z >> 17, fr = (Z mod 2^17) / 2^17, r = w[t] / 2^17, c = min(1, 1 / r), H = 16 / c;
+ *     out[n] = sum_i y[i] h(ip - i + fr) with sa_pitch_resample's h (weights in fp64, rounded once, fp32
+ *     accumulation in the order of i); i outside [0, min(Nin, (T'_b - 1) 160)) contributes nothing; 0 for
+ *     n >= n_valid[b].
+ *   sa_contour_dim(which): 0 frames per pass of sa_pitch_contour, 1 the largest smooth 8, 2 hop 160, 3 fraction bits
+ *     of rho_q 16, 4 of Q 17, 5 outputs per workgroup of sa_pitch_resample_map, 6 samples it stages; else -EINVAL.
+ *     (sa_pv_dim and sa_env_dim hold for the two variants.)
+ *   -EINVAL, before any launch: a NULL pointer (M, phase and env may be NULL), B < 1 or > 65535, T < 2 (sa_env_warp_
+ *     frames: < 1) or > 2^23, Tout < 1 or > 2^23, N, Nin < 1 or > 2^30, Nout < 1 or > 2^29, target <= 0, gamma
+ *     outside [0, 2], smooth outside 0..8, r_min < 0.5, r_max > 2, r_min > r_max, and sa_env_warp's conditions. */
+int sa_contour_dim(int which);
+int sa_pitch_contour(const float* f0, const float* lens, int B, int T, int N, float target, float gamma, int smooth,
+                     float r_min, float r_max, int min_voiced, int* rho_q, long long* Q, int* Tq, float* mean,
+                     int* voiced, void* stream);
+int sa_pv_synth_map(const void* R, const float* M, const int* rho_q, const long long* Q, int B, int T, int Tout,
+                    void* C, double* phase, void* ws, void* stream);
+int sa_env_warp_frames(const float* S, const float* q, int B, int T, int n_c, float floor_rel, float max_gain_ln,
+                       float* out, float* env, void* stream);
+int sa_pitch_resample_map(const float* y, const int* rho_q, const long long* Q, const int* n_valid, int B, int Nin,
+                          int Nout, int T, float* out, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -125,6 +125,7 @@ SYMBOLS = [
     "sa_mcadams_dim", "sa_mcadams",
     "sa_stoi_dim", "sa_stoi",
     "sa_pv_dim", "sa_pv_synth",
+    "sa_contour_dim", "sa_pitch_contour", "sa_pv_synth_map", "sa_env_warp_frames", "sa_pitch_resample_map",
 ]
 
 _lib = None

@@ -54,6 +54,10 @@ __device__ static inline float env_q(float q) {            // a warp factor no k
 //       cos(n theta_k) come from two Chebyshev recurrences in fp64 started at cospi, rounded to fp32 per term
 //       (theta depends on (k, b) only, so one recurrence serves the eight frames); 2 x 8 fp32 accumulators.
 // Frames from T on are staged as zeros and never stored.
+// FRAMES (sa_env_warp_frames): qrow is [B][T], one factor per frame, and stage (c) runs one theta
+// recurrence per frame instead of one per tile; everything else is the same text, and the per-frame accumulation is
+// the fmaf the packed FMA is made of, so that a q constant along t gives sa_env_warp's bits.
+template <bool FRAMES>
 __global__ __launch_bounds__(ENV_THREADS) void sa_env_warp_kernel(const float* __restrict__ S,
                                                                   const float* __restrict__ qrow, int T, int n_c,
                                                                   float floor_rel, float max_gain_ln,
@@ -143,6 +147,47 @@ __global__ __launch_bounds__(ENV_THREADS) void sa_env_warp_kernel(const float* _
   // (c)
   const int k = tid;
   if (k >= ENV_NBIN) return;
+  if constexpr (FRAMES) {
+    const double wk = (double)k * (1.0 / 200.0);            // w_k / pi
+    const double xw = cospi(wk), xw2 = 2.0 * xw;
+    float qf[ENV_G];
+    double h0[ENV_G], h1[ENV_G], xt2[ENV_G];
+    float Ew[ENV_G], Et[ENV_G];
+#pragma unroll
+    for (int f = 0; f < ENV_G; ++f) {
+      qf[f] = env_q(f < nf ? qrow[(size_t)b * T + t0 + f] : 1.0f);
+      const double xt = cospi(fmin(1.0, (double)qf[f] * wk));
+      h0[f] = 1.0, h1[f] = xt, xt2[f] = 2.0 * xt;
+      Ew[f] = Et[f] = 0.0f;
+    }
+    double w0 = 1.0, w1 = xw;
+    for (int n = 1; n <= n_c; ++n) {
+      const float cw = (float)w1;
+      const f32x4 ca = *(const f32x4*)(cep + n * ENV_G), cb = *(const f32x4*)(cep + n * ENV_G + 4);
+#pragma unroll
+      for (int f = 0; f < ENV_G; ++f) {
+        const float cf = f < 4 ? ca[f & 3] : cb[f & 3];
+        const float ct = (float)h1[f];
+        Ew[f] = fmaf(cf, cw, Ew[f]), Et[f] = fmaf(cf, ct, Et[f]);
+        const double h2 = fma(xt2[f], h1[f], -h0[f]);
+        h0[f] = h1[f], h1[f] = h2;
+      }
+      const double w2 = fma(xw2, w1, -w0);
+      w0 = w1, w1 = w2;
+    }
+#pragma unroll
+    for (int f = 0; f < ENV_G; ++f) {
+      if (f < nf) {
+        const float ew = fmaf(2.0f, Ew[f], cep[f]), et = fmaf(2.0f, Et[f], cep[f]);
+        const float g = fminf(fmaxf(et - ew, -max_gain_ln), max_gain_ln);
+        const float s = Ss[f * ENV_NBIN + k];
+        const size_t o = base + (size_t)f * ENV_NBIN + k;
+        out[o] = qf[f] == 1.0f ? s : s * expf(g);
+        if (env) env[o] = ew;
+      }
+    }
+    return;
+  }
   const float q = env_q(qrow[b]);
   const double wk = (double)k * (1.0 / 200.0);              // w_k / pi
   const double xw = cospi(wk), xt = cospi(fmin(1.0, (double)q * wk));
@@ -185,7 +230,17 @@ extern "C" int sa_env_warp(const float* S, const float* q, int B, int T, int n_c
   if (!S || !q || !out || B < 1 || B > ENV_MAX_B || T < 1 || T > ENV_MAX_T || n_c < 1 || n_c > ENV_NC_MAX ||
       !(floor_rel > 0.0f) || !(floor_rel < 1.0f) || !(max_gain_ln > 0.0f))
     return -EINVAL;
-  hipLaunchKernelGGL(sa_env_warp_kernel, dim3(sa_div_up(T, ENV_G), B), dim3(ENV_THREADS), 0, (hipStream_t)stream, S,
-                     q, T, n_c, floor_rel, max_gain_ln, out, env);
+  hipLaunchKernelGGL(sa_env_warp_kernel<false>, dim3(sa_div_up(T, ENV_G), B), dim3(ENV_THREADS), 0,
+                     (hipStream_t)stream, S, q, T, n_c, floor_rel, max_gain_ln, out, env);
+  return -(int)hipGetLastError();
+}
+
+extern "C" int sa_env_warp_frames(const float* S, const float* q, int B, int T, int n_c, float floor_rel,
+                                  float max_gain_ln, float* out, float* env, void* stream) {
+  if (!S || !q || !out || B < 1 || B > ENV_MAX_B || T < 1 || T > ENV_MAX_T || n_c < 1 || n_c > ENV_NC_MAX ||
+      !(floor_rel > 0.0f) || !(floor_rel < 1.0f) || !(max_gain_ln > 0.0f))
+    return -EINVAL;
+  hipLaunchKernelGGL(sa_env_warp_kernel<true>, dim3(sa_div_up(T, ENV_G), B), dim3(ENV_THREADS), 0,
+                     (hipStream_t)stream, S, q, T, n_c, floor_rel, max_gain_ln, out, env);
   return -(int)hipGetLastError();
 }

@@ -11,8 +11,11 @@
 //   sa_pv_scan_kernel<true>   grid (chunks, B): the increments again, from the offset on -> C (and phi')
 // The increments are recomputed (two atan2 per element in all) rather than kept: [B][Tout][201] fp64 through HBM
 // and back would cost more.
+// sa_pv_synth_map is the same three launches with the stretch positions of a time map in place
+// of a ratio's (MAP == true: sa_contour_map.h) and the magnitudes given on the input grid: one kernel text.
 #include "sa_common.h"
 #include "sa_pitch_stretch.h"
+#include "sa_contour_map.h"
 #include <errno.h>
 
 #define PV_TC 32                         // output frames per chunk
@@ -45,18 +48,33 @@ __device__ static inline double pv_mod1(double x) { return x - floor(x); }
 // frames it read last and computes only what is new (the branches are the same in every lane: i_s depends on the
 // row and s alone).  SYNTH == false stops at T'_b and leaves the chunk's total; SYNTH == true starts from the
 // chunk's offset and writes every frame of the chunk, zeros from T'_b on.
-template <bool SYNTH>
+// MAP: S is on the input grid [B][T][201] (or NULL: |R|) and is mixed as the stretch mixes |R|; rq and Q are the
+// row's tables, and the chunk finds its first i by a binary search over Q -- the same in every lane.
+template <bool SYNTH, bool MAP>
 __global__ __launch_bounds__(PV_THREADS) void sa_pv_scan_kernel(const float2* __restrict__ R,
                                                                 const float* __restrict__ S,
-                                                                const float* __restrict__ ratio, int T, int Tout,
+                                                                const float* __restrict__ ratio,
+                                                                const int* __restrict__ rq,
+                                                                const long long* __restrict__ Q, int T, int Tout,
                                                                 int nchunk, double* __restrict__ ws,
                                                                 float2* __restrict__ C, double* __restrict__ phase) {
   const int k = threadIdx.x, c = blockIdx.x, b = blockIdx.y;
   if (k >= PN_NBIN) return;
-  const double r = (double)pn_ratio(ratio[b]);
-  const int Tb = pn_frames(T, r), t0 = c * PV_TC, t1 = min(t0 + PV_TC, Tout);
+  double r = 1.0;
+  if constexpr (MAP) {
+    rq += (size_t)b * T;
+    Q += (size_t)b * T;
+  } else {
+    r = (double)pn_ratio(ratio[b]);
+  }
+  int Tb;
+  if constexpr (MAP) Tb = ct_frames(Q, T); else Tb = pn_frames(T, r);
+  const int t0 = c * PV_TC, t1 = min(t0 + PV_TC, Tout);
   if (!SYNTH && t0 >= Tb) return;                            // (a total nobody reads)
   const float2* Rb = R + (size_t)b * T * PN_NBIN + k;
+  const float* Sb = MAP && S ? S + (size_t)b * T * PN_NBIN + k : nullptr;
+  int i = 0;
+  if constexpr (MAP) i = ct_search(Q, T, (long long)t0 << CT_QBITS);
   double* w = ws + ((size_t)b * nchunk + c) * PN_NBIN + k;
   double acc = SYNTH && t0 < Tb ? *w : 0.0;
   int cur = -2;                                              // the frames held: cur and cur + 1
@@ -71,7 +89,7 @@ __global__ __launch_bounds__(PV_THREADS) void sa_pv_scan_kernel(const float2* __
       continue;
     }
     float a;
-    const int i = pn_position(tp, r, T, &a);
+    if constexpr (MAP) i = ct_position(Q, rq, T, tp, i, &a); else i = pn_position(tp, r, T, &a);
     if (i != cur) {
       if (i == cur + 1) {
         th_lo = th_hi;
@@ -79,15 +97,15 @@ __global__ __launch_bounds__(PV_THREADS) void sa_pv_scan_kernel(const float2* __
       } else {
         const float2 p = Rb[(size_t)i * PN_NBIN];
         th_lo = pv_theta(p);
-        m_lo = pn_mag(p);
+        m_lo = Sb ? Sb[(size_t)i * PN_NBIN] : pn_mag(p);
       }
       const float2 q = Rb[(size_t)(i + 1) * PN_NBIN];
       th_hi = pv_theta(q);
-      m_hi = pn_mag(q);
+      m_hi = Sb ? Sb[(size_t)(i + 1) * PN_NBIN] : pn_mag(q);
       cur = i;
     }
     if (SYNTH) {
-      const double mag = (double)(S ? S[o] : pn_mix(a, m_lo, m_hi));
+      const double mag = (double)(!MAP && S ? S[o] : pn_mix(a, m_lo, m_hi));
       double sn, cs;
       sincospi(2.0 * acc, &sn, &cs);
       C[o] = make_float2((float)(mag * cs), (float)(mag * sn));
@@ -100,12 +118,16 @@ __global__ __launch_bounds__(PV_THREADS) void sa_pv_scan_kernel(const float2* __
 
 // grid (B).  Thread k turns the totals of the chunks that start below T'_b into phi' at their first frames, in the
 // order of the chunks, reduced mod 1 at every step.
+template <bool MAP>
 __global__ __launch_bounds__(PV_THREADS) void sa_pv_offsets_kernel(const float2* __restrict__ R,
-                                                                   const float* __restrict__ ratio, int T, int Tout,
+                                                                   const float* __restrict__ ratio,
+                                                                   const long long* __restrict__ Q, int T, int Tout,
                                                                    int nchunk, double* __restrict__ ws) {
   const int k = threadIdx.x, b = blockIdx.x;
   if (k >= PN_NBIN) return;
-  const int Tb = min(pn_frames(T, (double)pn_ratio(ratio[b])), Tout);
+  int Tb;
+  if constexpr (MAP) Tb = ct_frames(Q + (size_t)b * T, T); else Tb = pn_frames(T, (double)pn_ratio(ratio[b]));
+  Tb = min(Tb, Tout);
   const int nuse = (Tb + PV_TC - 1) / PV_TC;                 // <= nchunk
   double* w = ws + (size_t)b * nchunk * PN_NBIN + k;
   double acc = pv_mod1(pv_theta(R[(size_t)b * T * PN_NBIN + k]));
@@ -121,11 +143,28 @@ extern "C" int sa_pv_synth(const void* R, const float* S, const float* ratio, in
   if (!R || !ratio || !C || !ws || !pv_shape_ok(B, Tout) || T < 2 || T > PN_MAX_T) return -EINVAL;
   const int nchunk = sa_div_up(Tout, PV_TC);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sa_pv_scan_kernel<false>, dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, S, ratio,
-                     T, Tout, nchunk, (double*)ws, (float2*)nullptr, (double*)nullptr);
-  hipLaunchKernelGGL(sa_pv_offsets_kernel, dim3(B), dim3(PV_THREADS), 0, st, (const float2*)R, ratio, T, Tout, nchunk,
-                     (double*)ws);
-  hipLaunchKernelGGL(sa_pv_scan_kernel<true>, dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, S, ratio, T,
-                     Tout, nchunk, (double*)ws, (float2*)C, phase);
+  hipLaunchKernelGGL((sa_pv_scan_kernel<false, false>), dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, S,
+                     ratio, (const int*)nullptr, (const long long*)nullptr, T, Tout, nchunk, (double*)ws,
+                     (float2*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL(sa_pv_offsets_kernel<false>, dim3(B), dim3(PV_THREADS), 0, st, (const float2*)R, ratio,
+                     (const long long*)nullptr, T, Tout, nchunk, (double*)ws);
+  hipLaunchKernelGGL((sa_pv_scan_kernel<true, false>), dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, S,
+                     ratio, (const int*)nullptr, (const long long*)nullptr, T, Tout, nchunk, (double*)ws, (float2*)C,
+                     phase);
+  return -(int)hipGetLastError();
+}
+
+extern "C" int sa_pv_synth_map(const void* R, const float* M, const int* rho_q, const long long* Q, int B, int T,
+                               int Tout, void* C, double* phase, void* ws, void* stream) {
+  if (!R || !rho_q || !Q || !C || !ws || !pv_shape_ok(B, Tout) || T < 2 || T > PN_MAX_T) return -EINVAL;
+  const int nchunk = sa_div_up(Tout, PV_TC);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((sa_pv_scan_kernel<false, true>), dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, M,
+                     (const float*)nullptr, rho_q, Q, T, Tout, nchunk, (double*)ws, (float2*)nullptr,
+                     (double*)nullptr);
+  hipLaunchKernelGGL(sa_pv_offsets_kernel<true>, dim3(B), dim3(PV_THREADS), 0, st, (const float2*)R,
+                     (const float*)nullptr, Q, T, Tout, nchunk, (double*)ws);
+  hipLaunchKernelGGL((sa_pv_scan_kernel<true, true>), dim3(nchunk, B), dim3(PV_THREADS), 0, st, (const float2*)R, M,
+                     (const float*)nullptr, rho_q, Q, T, Tout, nchunk, (double*)ws, (float2*)C, phase);
   return -(int)hipGetLastError();
 }

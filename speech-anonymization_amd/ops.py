@@ -1142,6 +1142,111 @@ def env_warp(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
     return (out, env) if return_env else out
 
 
+def env_warp_frames(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
+    """env_warp with warp factors q fp32 [B, T], one per frame (sa_env_warp_frames): for q constant
+    along t, env_warp's bits"""
+    if _env_in(S, "S").dim() != 3 or S.shape[2] != 201:
+        raise L.SaHipError(f"S: expected [B, T, 201], got {tuple(S.shape)}")
+    B, T, _ = S.shape
+    if B < 1 or B > GL_MAX_B or T < 1 or T > GL_MAX_T:
+        raise L.SaHipError(f"S: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 1..{GL_MAX_T}")
+    _env_in(q, "q", shape=(B, T))
+    n_c = int(n_c)
+    if not 1 <= n_c <= ENV_NC_MAX:
+        raise L.SaHipError(f"env_warp_frames: n_c = {n_c} in 1..{ENV_NC_MAX} expected")
+    if not 0.0 < float(floor_rel) < 1.0:
+        raise L.SaHipError(f"env_warp_frames: floor_rel = {floor_rel} in (0, 1) expected")
+    if not float(max_gain_db) > 0.0:
+        raise L.SaHipError(f"env_warp_frames: max_gain_db = {max_gain_db} > 0 expected")
+    out = torch.empty_like(S)
+    env = torch.empty_like(S) if return_env else None
+    L.check(L.load().sa_env_warp_frames(_f(S), _f(q), B, T, n_c, C.c_float(float(floor_rel)),
+                                        C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
+            "sa_env_warp_frames")
+    return (out, env) if return_env else out
+
+
+# ---- F0-contour pitch modification (csrc/sa_contour.hip; pitchnorm.py; DESIGN section 20) ----
+CT_SMOOTH_MAX = 8                          # sa_contour_dim(1)
+CT_RHO_ONE, CT_Q_ONE = 1 << 16, 1 << 17    # ratio 1 in rho_q; one input frame in Q
+
+_ct_in = functools.partial(_aug_in, family="contour")
+
+
+def _ct_tables(rho_q, Q, B, T):
+    _ct_in(rho_q, "rho_q", torch.int32, (B, T))
+    _ct_in(Q, "Q", torch.int64, (B, T))
+
+
+def pitch_contour(f0, lens, N, target_hz=170.0, gamma=1.0, smooth=2, r_min=0.5, r_max=2.0, min_voiced=5):
+    """f0 [B, T] (yin_f0 of the padded waveform), relative lengths lens [B], N samples per row -> (rho_q int32 [B, T],
+    Q int64 [B, T], Tq int32 [B], mean fp32 [B], voiced int32 [B]): the per-frame ratio that moves the contour to
+    target + gamma (f0 - mean), in units of 2^-16, its time map in units of 2^-17 frames and the frames T'_b the
+    stretch gives; mean and voiced as pitch_ratio's (sa_pitch_contour)"""
+    B, T = _pn_rows(f0, "f0")
+    _ct_in(lens, "lens", shape=(B,))
+    N, smooth = int(N), int(smooth)
+    if N < 1 or N > PN_MAX_N or T < 2 or T > GL_MAX_T:
+        raise L.SaHipError(f"pitch_contour: N = {N} in 1..{PN_MAX_N} and T = {T} in 2..{GL_MAX_T} expected")
+    if not (float(target_hz) > 0.0 and 0.5 <= float(r_min) <= float(r_max) <= 2.0):
+        raise L.SaHipError(f"pitch_contour: target {target_hz} > 0 and 0.5 <= r_min {r_min} <= r_max {r_max} <= 2 "
+                           "expected")
+    if not 0.0 <= float(gamma) <= 2.0 or not 0 <= smooth <= CT_SMOOTH_MAX:
+        raise L.SaHipError(f"pitch_contour: gamma {gamma} in [0, 2] and smooth {smooth} in 0..{CT_SMOOTH_MAX} expected")
+    dev = f0.device
+    rho_q = torch.empty(B, T, dtype=torch.int32, device=dev)
+    Q = torch.empty(B, T, dtype=torch.int64, device=dev)
+    Tq = torch.empty(B, dtype=torch.int32, device=dev)
+    mean = torch.empty(B, dtype=torch.float32, device=dev)
+    voiced = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.load().sa_pitch_contour(_f(f0), _f(lens), B, T, N, C.c_float(float(target_hz)), C.c_float(float(gamma)),
+                                      smooth, C.c_float(float(r_min)), C.c_float(float(r_max)), int(min_voiced),
+                                      _f(rho_q), _f(Q), _f(Tq), _f(mean), _f(voiced), L.stream()), "sa_pitch_contour")
+    return rho_q, Q, Tq, mean, voiced
+
+
+def pv_synth_map(R, rho_q, Q, Tout, M=None, return_phase=False):
+    """pv_synth with the stretch positions of a time map (pitch_contour's rho_q and Q, [B, T]) in place of a ratio's;
+    M fp32 [B, T, 201]: magnitudes ON THE INPUT GRID (e.g. env_warp_frames' output), mixed as the stretch mixes |R|;
+    without M, |R| (sa_pv_synth_map).  Everything stays on the device."""
+    if _pv_in(R, "R", torch.complex64).dim() != 3 or R.shape[2] != 201:
+        raise L.SaHipError(f"R: expected [B, T, 201], got {tuple(R.shape)}")
+    B, T, _ = R.shape
+    Tout = int(Tout)
+    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T or Tout < 1 or Tout > GL_MAX_T:
+        raise L.SaHipError(f"pv_synth_map: [B, T] = [{B}, {T}], Tout = {Tout} -- B in 1..{GL_MAX_B} (a grid extent), T "
+                           f"in 2..{GL_MAX_T}, Tout in 1..{GL_MAX_T}")
+    _ct_tables(rho_q, Q, B, T)
+    if M is not None:
+        _pv_in(M, "M", shape=(B, T, 201))
+    lib = L.load()
+    Cx = torch.empty(B, Tout, 201, dtype=torch.complex64, device=R.device)
+    phase = torch.empty(B, Tout, 201, dtype=torch.float64, device=R.device) if return_phase else None
+    ws = torch.empty(lib.sa_pv_workspace_bytes(B, Tout) // 8, dtype=torch.float64, device=R.device)
+    L.check(lib.sa_pv_synth_map(_f(R), _f(M), _f(rho_q), _f(Q), B, T, Tout, _f(Cx), _f(phase), _f(ws), L.stream()),
+            "sa_pv_synth_map")
+    return (Cx, phase) if return_phase else Cx
+
+
+def pitch_resample_map(y, rho_q, Q, n_valid, Nout):
+    """y [B, Nin], the time map (rho_q, Q: [B, T]), n_valid int32 [B] -> out [B, Nout]: the windowed-sinc read of y at
+    the positions the map gives output sample n < n_valid_b, zero from there on (sa_pitch_resample_map)"""
+    B, Nin = _pn_rows(y, "y")
+    if not torch.is_tensor(rho_q) or rho_q.dim() != 2:
+        raise L.SaHipError("rho_q: expected [B, T]")
+    T = rho_q.shape[1]
+    _ct_tables(rho_q, Q, B, T)
+    _ct_in(n_valid, "n_valid", torch.int32, (B,))
+    Nout = int(Nout)
+    if Nout < 1 or Nout > PN_MAX_N // 2 or T < 2 or T > GL_MAX_T:
+        raise L.SaHipError(f"pitch_resample_map: Nout = {Nout} in 1..{PN_MAX_N // 2} and T = {T} in 2..{GL_MAX_T} "
+                           "expected")
+    out = torch.empty(B, Nout, dtype=torch.float32, device=y.device)
+    L.check(L.load().sa_pitch_resample_map(_f(y), _f(rho_q), _f(Q), _f(n_valid), B, Nin, Nout, T, _f(out),
+                                           L.stream()), "sa_pitch_resample_map")
+    return out
+
+
 # ---- McAdams-coefficient anonymisation (csrc/sa_mcadams.hip; mcadams.py) ----
 MC_W, MC_H, MC_CHUNK = 320, 160, 4096      # sa_mcadams_dim(0), (1), (6)
 

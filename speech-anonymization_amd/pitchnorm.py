@@ -19,7 +19,11 @@ is read q_b times as far up, so that after the resampling the harmonics sit at r
 
 The input's own phase: with ``phase="vocoder"`` both classes carry the phases of STFT(wav) through
 the stretch (sa_pv_synth, a phase vocoder) and invert once, in place of Griffin-Lim's 32 iterations from random
-phases: stretch [-> warp] -> sa_pv_synth -> one sa_gl_istft.  ``"griffin_lim"`` stays the default."""
+phases: stretch [-> warp] -> sa_pv_synth -> one sa_gl_istft.  ``"griffin_lim"`` stays the default.
+
+The contour: with ``contour_scale`` gamma (and ``phase="vocoder"``) the ratio varies from frame to
+frame so that the output's F0 contour is target + gamma (f0 - mean) -- 1 the additive shift of the reference's
+baseline, 0 a monotone voice: sa_pitch_contour -> [sa_env_warp_frames] -> sa_pv_synth_map -> sa_pitch_resample_map."""
 import math
 
 import torch
@@ -34,6 +38,8 @@ TARGET_LOW, TARGET_HIGH = 60.0, 400.0        # the tracker's range: 16000 / tau_
 BETA_LOW, BETA_HIGH = 0.5, 2.0               # formant ratios: q = r / beta stays in the [0.25, 4] the kernel takes
 LIFTER_MAX = 64                              # sa_env_dim(3)
 PHASES = ("griffin_lim", "vocoder")          # where the re-synthesis takes its phases from
+CONTOUR_LOW, CONTOUR_HIGH = 0.0, 2.0         # contour_scale gamma: 0 a monotone voice, 1 the additive shift
+SMOOTH_MAX = 8                               # sa_contour_dim(1)
 
 
 def f0_track(wav, threshold=0.15):
@@ -69,20 +75,39 @@ def phase_setting(who, phase):
     return phase
 
 
+def contour_settings(who, contour_scale, contour_smooth, phase):
+    """-> (gamma or None, smooth), or ValueError: the contour needs the vocoder's phases"""
+    if contour_scale is None:
+        return None, int(contour_smooth)
+    if phase != "vocoder":
+        raise ValueError(f"{who}: contour_scale needs phase=\"vocoder\" (Griffin-Lim with a contour is not built)")
+    gamma = float(contour_scale)
+    if not CONTOUR_LOW <= gamma <= CONTOUR_HIGH:
+        raise ValueError(f"{who}: contour_scale {contour_scale} in {CONTOUR_LOW:g}..{CONTOUR_HIGH:g} expected")
+    if isinstance(contour_smooth, bool) or int(contour_smooth) != contour_smooth or \
+            not 0 <= int(contour_smooth) <= SMOOTH_MAX:
+        raise ValueError(f"{who}: contour_smooth {contour_smooth} in 0..{SMOOTH_MAX} expected")
+    return gamma, int(contour_smooth)
+
+
 class PitchNormalizer:
     """wavs [B, N] (device), relative lengths [B] -> wavs of the same shape whose voiced F0 has mean ~ target_hz;
     samples from round(lens_b N) on are zero.  ``last``: (ratio, mean f0, voiced frames) of the last batch, on
     the device.  ``formant_ratio`` beta (``preserve_formants=True``: 1) scales the spectral envelope by beta
     instead of by the pitch ratio; without either the envelope moves with the pitch and no warp is launched.
     ``phase="vocoder"`` carries the input's phases through the stretch instead of running Griffin-Lim: no iterations,
-    no random numbers (n_iter, momentum and seed are then unused, and ``gl`` is None)."""
+    no random numbers (n_iter, momentum and seed are then unused, and ``gl`` is None).  ``contour_scale`` gamma (needs
+    ``phase="vocoder"``) moves the contour to target + gamma (f0 - mean) with a ratio per frame, smoothed by a triangle
+    of half-width ``contour_smooth`` frames; ``last[0]`` is then the row's mean ratio.  None: one ratio per row."""
 
     def __init__(self, target_hz=170.0, n_iter=32, momentum=0.99, seed=1, r_min=0.5, r_max=2.0, min_voiced=5,
                  threshold=0.15, preserve_formants=False, formant_ratio=None, lifter=30, floor_rel=1e-4,
-                 max_gain_db=40.0, phase="griffin_lim"):
+                 max_gain_db=40.0, phase="griffin_lim", contour_scale=None, contour_smooth=2):
         self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
             "PitchNormalizer", preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db)
         self.phase = phase_setting("PitchNormalizer", phase)
+        self.contour_scale, self.contour_smooth = contour_settings("PitchNormalizer", contour_scale, contour_smooth,
+                                                                   self.phase)
         if not TARGET_LOW <= float(target_hz) <= TARGET_HIGH:
             raise ValueError(f"PitchNormalizer: target_hz {target_hz} in {TARGET_LOW:g}..{TARGET_HIGH:g} expected")
         if not R_LOW <= float(r_min) <= float(r_max) <= R_HIGH:
@@ -98,9 +123,38 @@ class PitchNormalizer:
         if not torch.is_tensor(wavs) or not wavs.is_cuda:
             raise L.SaHipError("PitchNormalizer runs on the GPU only (no CPU fallback)")
         lens = lens.to(wavs.device, torch.float32).contiguous()
+        if self.contour_scale is not None:
+            return self.shift_contour(wavs, lens)
         f0 = ops.yin_f0(wavs, self.threshold)
         self.last = ops.pitch_ratio(f0, lens, wavs.shape[1], self.target_hz, self.r_min, self.r_max, self.min_voiced)
         return self.shift(wavs, lens, self.last[0])
+
+    @torch.no_grad()
+    def shift_contour(self, wavs, lens):
+        """the contour path: pad -> yin_f0 of the padded waveform -> pitch_contour -> STFT [->
+        |R| -> env_warp_frames at q[b, t] = rho[b, t] / beta] -> pv_synth_map -> one gl_istft -> pitch_resample_map.
+        ``last`` is (the row's mean ratio Q[T - 1] / ((T - 1) 2^17), mean f0, voiced frames)."""
+        from . import ops
+        B, N = wavs.shape
+        Np = HOP * -(-N // HOP)
+        wp = (torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs).contiguous()
+        f0 = ops.yin_f0(wp, self.threshold)
+        rho_q, Q, Tq, mean, voiced = ops.pitch_contour(f0, lens, N, self.target_hz, self.contour_scale,
+                                                       self.contour_smooth, self.r_min, self.r_max, self.min_voiced)
+        T = f0.shape[1]
+        self.last = ((Q[:, T - 1].double() / float((T - 1) * ops.CT_Q_ONE)).float(), mean, voiced)
+        R = vocoder.stft(wp)
+        M = None
+        if self.formant_ratio is not None:                   # on the input grid: the frame's own ratio is known there
+            one = torch.ones(B, dtype=torch.float32, device=wavs.device)
+            q = (rho_q.float() / (ops.CT_RHO_ONE * self.formant_ratio)).contiguous()
+            M = ops.env_warp_frames(ops.pitch_stretch_mag(R, one, T), q, self.lifter, self.floor_rel,
+                                    self.max_gain_db)
+        Tout = int(Tq.max())                                 # the path's one synchronisation: T' is a shape
+        w, tw, _ = vocoder.tables(wavs.device)
+        y = ops.gl_istft(ops.pv_synth_map(R, rho_q, Q, Tout, M), w, tw)
+        n_valid = torch.round(lens.double() * N).clamp(0, N).to(torch.int32)
+        return ops.pitch_resample_map(y, rho_q, Q, n_valid, N)
 
     @torch.no_grad()
     def shift(self, wavs, lens, ratio):
@@ -212,6 +266,39 @@ def check_phase_option(settings, block=None):
     return {"phase": value}
 
 
+def check_contour_options(settings, block=None):
+    """``contour_scale`` and ``contour_smooth`` of a recipe's ``pitch_norm:`` block (if any) under the top-level
+    overrides -> a dict that carries a key only when it was given; each is refused in one line when out of range or
+    given without ``phase: vocoder``"""
+    block = block or {}
+    given = {}
+    for key in ("contour_scale", "contour_smooth"):
+        value = settings.get(key, block.get(key))
+        if value is not None:
+            given[key] = value
+    if not given:
+        return given
+    if settings.get("phase", block.get("phase")) != "vocoder":
+        raise SystemExit(f"--{next(iter(given))} needs --phase vocoder: the contour is moved on the phase-vocoder path "
+                         "only")
+    if "contour_scale" in given:
+        try:
+            gamma = float(given["contour_scale"])
+        except (TypeError, ValueError):
+            gamma = float("nan")
+        if isinstance(given["contour_scale"], bool) or not CONTOUR_LOW <= gamma <= CONTOUR_HIGH:
+            raise SystemExit(f"--contour_scale {given['contour_scale']}: a factor between {CONTOUR_LOW:g} (a monotone "
+                             f"voice) and {CONTOUR_HIGH:g} by which the F0 contour's excursions are scaled")
+        given["contour_scale"] = gamma
+    if "contour_smooth" in given:
+        s = given["contour_smooth"]
+        if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s <= SMOOTH_MAX:
+            raise SystemExit(f"--contour_smooth {s}: a half-width in frames, 0 to {SMOOTH_MAX}")
+        if "contour_scale" not in given:
+            raise SystemExit("--contour_smooth needs --contour_scale: there is no contour to smooth without it")
+    return given
+
+
 def check_pitch_target(value):
     target = float(value)
     if not TARGET_LOW <= target <= TARGET_HIGH:
@@ -238,4 +325,4 @@ def check_pitch_options(settings, run_opts, environ=None):
     if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
         raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
     return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn),
-                **check_phase_option(settings, pn))
+                **check_phase_option(settings, pn), **check_contour_options(settings, pn))

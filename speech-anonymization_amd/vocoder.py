@@ -186,6 +186,10 @@ def check_anonymize_options(settings, run_opts, environ=None):
         if not settings.get("pitch_norm") and not shift_only:
             raise SystemExit("--phase vocoder goes with --pitch_norm true or --formant_ratio: the paths that "
                              "re-synthesise a waveform they were given")
+    from .pitchnorm import check_contour_options
+    if check_contour_options(settings) and not settings.get("pitch_norm"):    # 
+        raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
+                         "pitch")
     if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only and not mcadams:
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
     if formant.get("preserve_formants") and not settings.get("pitch_norm"):

@@ -1,0 +1,260 @@
+#!/usr/bin/env python3
+"""Times the F0-contour pitch modification (csrc/sa_contour.hip and its two variants) at B = 32
+utterances of 10 s: each new entry point against the same definition in torch operators on the same device in the
+same run, PitchNormalizer(phase="vocoder") with and without ``contour_scale``, and the gender recipe's train step
+with it.  The utterances are data.synthetic_gender_dataset's with a vibrato of +-12 % at 3 Hz imposed by a
+time-varying resampling, so that the ratio moves from frame to frame.
+
+Device events around each call after a warm-up; the median of --steps calls.  Every figure is a call THROUGH THE BINDING:
+the launch and the binding's allocations are inside it.  The entry points that take tens of microseconds (the contour
+and sa_pitch_ratio) are timed as 32 calls back to back between one pair of events, divided by 32, so that the figure
+is the rate at which the stream retires them, not the cost of two events around one launch (contour_single_call_ms
+is that other figure).  Prints one JSON line (and writes it to --out):
+  contour_ms, torch_contour_ms          sa_pitch_contour / cummax, cummin, gather, a convolution, cumsum; rho_q_differ
+                                        counts the elements on which the two disagree (fp64 orders differ)
+  synth_map_ms, torch_synth_map_ms      sa_pv_synth_map (M = NULL) / searchsorted, angle, diff, gather, cumsum, polar;
+                                        synth_map_given_ms with M given; pv_synth_ms: the constant-ratio sibling on
+                                        the same R
+  warp_frames_ms, torch_warp_frames_ms  sa_env_warp_frames / log, two matrix products and a [B, T, n_c, 201] cosine
+                                        table in fp32; env_warp_ms: the per-row sibling
+  resample_map_ms, torch_resample_map_ms  sa_pitch_resample_map / a [B, N, 66] gather in fp64, in row chunks;
+                                        resample_ms: the constant-ratio sibling
+  normalizer_vocoder_ms, normalizer_contour_ms, normalizer_contour_formants_ms   the whole call
+  step_vocoder_ms, step_contour_ms      GenderPitchNormBrain.fit_batch on the same batch"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+SR, HOP, NBIN = 16000, 160, 201
+SHORT_REPS = 32                           # calls per sample of the entry points that take tens of microseconds
+
+
+def time_calls(fn, warmup, steps, reps=1):
+    """the median over ``steps`` samples of the time of one call; a sample is ``reps`` calls between one pair of events,
+    divided by reps (a single 20-30 us call between two events measures mostly the launch and the events)"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1) / reps)
+    return statistics.median(ts)
+
+
+def with_vibrato(wav, depth=0.12, rate=3.0):
+    """wav [B, N] on the device read at n + (depth / (2 pi rate / SR)) (1 - cos(2 pi rate n / SR)) by linear
+    interpolation: the pitch moves by +-depth around (1 + 0) times its own"""
+    B, N = wav.shape
+    n = torch.arange(N, device=wav.device, dtype=torch.float64)
+    w = 2.0 * math.pi * rate / SR
+    pos = (n + depth / w * (1.0 - torch.cos(w * n))).clamp(max=N - 1.001)
+    i = pos.floor().long()
+    a = (pos - i).float()
+    return ((1.0 - a) * wav[:, i] + a * wav[:, i + 1]).contiguous()
+
+
+def torch_contour(f0, lens, N, target, gamma, s, r_min, r_max, min_voiced):
+    B, T = f0.shape
+    dev = f0.device
+    idx = torch.arange(T, device=dev)[None, :].expand(B, T)
+    F = (torch.round(lens.double() * N).clamp(0, N).long() // HOP + 1).clamp(max=T)
+    f = f0.double()
+    v = (f0 > 0) & (idx < F[:, None])
+    cnt = v.sum(1)
+    mean = torch.where(v, f, torch.zeros_like(f)).sum(1) / cnt.clamp(min=1)
+    lft = torch.where(v, idx, torch.full_like(idx, -1)).cummax(1).values
+    rgt = torch.where(v, idx, torch.full_like(idx, T)).flip(1).cummin(1).values.flip(1)
+    fl, fn = f.gather(1, lft.clamp(min=0)), f.gather(1, rgt.clamp(max=T - 1))
+    mid = fl + (fn - fl) * (idx - lft).double() / (rgt - lft).clamp(min=1).double()
+    fh = torch.where(lft < 0, fn, torch.where(rgt >= T, fl, torch.where(lft == rgt, f, mid)))
+    k = (s + 1 - torch.arange(-s, s + 1, device=dev).abs()).double()
+    pad = torch.cat([fh[:, :1].expand(B, s), fh, fh[:, -1:].expand(B, s)], 1)
+    ft = torch.nn.functional.conv1d(pad[:, None], k[None, None])[:, 0] / float((s + 1) ** 2)
+    g = (target + gamma * (ft - mean[:, None])).clamp(min=60.0)
+    rho = torch.round((g / ft).clamp(r_min, r_max) * 65536.0).long()
+    moved = (cnt >= min_voiced) & (cnt > 0)
+    rho = torch.where(moved[:, None], rho, torch.full_like(rho, 1 << 16))
+    w = rho[:, :-1] + rho[:, 1:]
+    Q = torch.cat([torch.zeros_like(rho[:, :1]), w.cumsum(1)], 1)
+    return rho.int(), Q, (((Q[:, -1] + (1 << 17) - 1) >> 17) + 1).int()
+
+
+def torch_synth_map(R, rho_q, Q, Tout):
+    B, T, K = R.shape
+    X = (torch.arange(Tout, device=R.device) << 17)[None, :].expand(B, Tout).contiguous()
+    end = X >= Q[:, -1:]
+    live = X < (((Q[:, -1:] + (1 << 17) - 1) >> 17) + 1) << 17
+    i = (torch.searchsorted(Q[:, :T - 1].contiguous(), X, right=True) - 1).clamp(0, T - 2)
+    i = torch.where(end, torch.full_like(i, T - 2), i)
+    rq = rho_q.long()
+    w = rq.gather(1, i) + rq.gather(1, i + 1)
+    a = torch.where(end, torch.ones((), dtype=torch.float64, device=R.device),
+                    (X - Q.gather(1, i)).double() / w.double()).float()[:, :, None]
+    th = torch.angle(R.to(torch.complex128)) / (2.0 * math.pi)
+    ix = i[:, :, None].expand(-1, -1, K)
+    inc = torch.diff(th, dim=1).gather(1, ix)
+    phi = (th[:, :1] + inc.cumsum(1) - inc) % 1.0
+    mag = R.abs()
+    Sp = (1.0 - a) * mag.gather(1, ix) + a * mag.gather(1, ix + 1)
+    C = torch.polar(Sp.double(), 2.0 * math.pi * phi).to(torch.complex64)
+    return torch.where(live[:, :, None], C, torch.zeros((), dtype=C.dtype, device=C.device))
+
+
+def torch_warp_frames(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0):
+    B, T, K = S.shape
+    dev = S.device
+    lim = max_gain_db * 0.11512925464970229
+    k = torch.arange(K, device=dev, dtype=torch.float32)
+    n = torch.arange(n_c + 1, device=dev, dtype=torch.float32)
+    cos_nk = torch.cos(2.0 * math.pi * n[:, None] * k[None, :] / 400.0)                 # [n_c + 1, K]
+    wgt = torch.full((K,), 2.0, device=dev)
+    wgt[0] = wgt[-1] = 1.0
+    L = torch.log(torch.maximum(torch.maximum(S, floor_rel * S.amax(-1, keepdim=True)), torch.full_like(S, 1e-10)))
+    c = (L * wgt) @ cos_nk.T / 400.0                                                    # [B, T, n_c + 1]
+    c2 = torch.cat([c[..., :1], 2.0 * c[..., 1:]], -1)
+    env = c2 @ cos_nk
+    theta = (q[:, :, None] * k / 200.0).clamp(max=1.0) * math.pi                        # [B, T, K]
+    env_t = (c2[..., None] * torch.cos(n[None, None, :, None] * theta[:, :, None, :])).sum(2)
+    g = (env_t - env).clamp(-lim, lim)
+    return torch.where((q == 1.0)[:, :, None], S, S * torch.exp(g))
+
+
+def torch_resample_map(y, rho_q, Q, n_valid, Nout, rows=4):
+    B, Nin = y.shape
+    T = Q.shape[1]
+    dev = y.device
+    n = torch.arange(Nout, device=dev)
+    t = (n // HOP).clamp(max=T - 2)
+    tap = torch.arange(66, device=dev)
+    out = torch.zeros(B, Nout, dtype=torch.float32, device=dev)
+    rq = rho_q.long()
+    for b0 in range(0, B, rows):
+        sl = slice(b0, min(B, b0 + rows))
+        w = rq[sl][:, t] + rq[sl][:, t + 1]
+        Z = HOP * Q[sl][:, t] + w * (n - HOP * t)[None, :]
+        ip, fr, r = Z >> 17, (Z & ((1 << 17) - 1)).double() / (1 << 17), w.double() / (1 << 17)
+        c = (1.0 / r).clamp(max=1.0)[..., None]
+        H = 16.0 / c
+        end = (HOP * (((Q[sl][:, -1] + (1 << 17) - 1) >> 17))).clamp(max=Nin)[:, None, None]
+        i = (torch.floor(ip.double() + fr - H[..., 0]).long() + 1)[..., None] + tap
+        u = (ip[..., None] - i).double() + fr[..., None]
+        h = c * torch.sinc(c * u) * (0.5 + 0.5 * torch.cos(math.pi * u / H))
+        h = torch.where((u.abs() < H) & (i >= 0) & (i < end), h, torch.zeros_like(h)).float()
+        yy = y[sl].gather(1, i.clamp(0, Nin - 1).reshape(i.shape[0], -1)).reshape(i.shape)
+        o = (h * yy).sum(-1)
+        out[sl] = torch.where(n[None, :] < n_valid[sl][:, None], o, torch.zeros_like(o))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-step", action="store_true", help="skip the recipe-step timings")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "contour_bench.json"))
+    a = ap.parse_args()
+    assert a.steps >= 20, "the median of at least 20 calls"
+    dev = torch.device("cuda:0")
+    from speech_anonymization_amd import data, gender, ops, pitchnorm, vocoder
+    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    B, N = a.B, int(a.seconds * SR)
+    batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
+    wav_cpu, lens_cpu = batch.sig
+    wav, lens = with_vibrato(wav_cpu.to(dev)), lens_cpu.to(dev).float().contiguous()
+    batch.sig = (wav.cpu(), lens_cpu)
+    gamma, s = 0.0, 2
+
+    Np = HOP * -(-N // HOP)
+    wp = torch.nn.functional.pad(wav, (0, Np - N)).contiguous()
+    f0 = ops.yin_f0(wp)
+    args = (f0, lens, N, 170.0, gamma, s, 0.5, 2.0, 5)
+    rho_q, Q, Tq, mean, voiced = ops.pitch_contour(*args)
+    t_rho, t_Q, t_Tq = torch_contour(*args)
+    differ = int((t_rho != rho_q).sum())
+    R = vocoder.stft(wp)
+    T, Tout = R.shape[1], int(Tq.max())
+    one = torch.ones(B, device=dev)
+    mag = ops.pitch_stretch_mag(R, one, T)
+    q = (rho_q.float() / 65536.0).contiguous()
+    n_valid = torch.round(lens.double() * N).clamp(0, N).to(torch.int32)
+    C = ops.pv_synth_map(R, rho_q, Q, Tout)
+    d_synth = float((C - torch_synth_map(R, rho_q, Q, Tout)).abs().max() / mag.max())
+    M = ops.env_warp_frames(mag, q)
+    d_warp = float(((M - torch_warp_frames(mag, q)).abs() / M.clamp(min=1e-3 * float(M.max()))).max())
+    w, tw, _ = vocoder.tables(dev)
+    y = ops.gl_istft(C, w, tw)
+    res = ops.pitch_resample_map(y, rho_q, Q, n_valid, N)
+    d_res = float((res - torch_resample_map(y, rho_q, Q, n_valid, N)).abs().max() / y.abs().max())
+    assert d_synth <= 1e-5 and d_warp <= 1e-2 and d_res <= 1e-5, (d_synth, d_warp, d_res)
+    out = {"B": B, "N": N, "T": T, "Tout": Tout, "steps": a.steps, "gamma": gamma, "smooth": s,
+           "rho_q_min": int(rho_q.min()), "rho_q_max": int(rho_q.max()), "rho_q_differ_vs_torch": differ,
+           "synth_map_diff_vs_torch_rel": float(f"{d_synth:.3e}"), "warp_frames_diff_vs_torch_rel": float(f"{d_warp:.3e}"),
+           "resample_map_diff_vs_torch_rel": float(f"{d_res:.3e}")}
+    tm = lambda fn, reps=1: round(time_calls(fn, a.warmup, a.steps, reps), 4)
+    ratio = (Q[:, -1].double() / float((T - 1) << 17)).float().contiguous()
+    out["short_call_reps"] = SHORT_REPS
+    out["contour_ms"] = tm(lambda: ops.pitch_contour(*args), SHORT_REPS)
+    out["contour_single_call_ms"] = tm(lambda: ops.pitch_contour(*args))
+    out["torch_contour_ms"] = tm(lambda: torch_contour(*args), SHORT_REPS)
+    out["pitch_ratio_ms"] = tm(lambda: ops.pitch_ratio(f0, lens, N), SHORT_REPS)
+    out["synth_map_ms"] = tm(lambda: ops.pv_synth_map(R, rho_q, Q, Tout))
+    out["synth_map_given_ms"] = tm(lambda: ops.pv_synth_map(R, rho_q, Q, Tout, M=M))
+    out["pv_synth_ms"] = tm(lambda: ops.pv_synth(R, ratio, Tout))
+    out["torch_synth_map_ms"] = tm(lambda: torch_synth_map(R, rho_q, Q, Tout))
+    out["warp_frames_ms"] = tm(lambda: ops.env_warp_frames(mag, q))
+    out["env_warp_ms"] = tm(lambda: ops.env_warp(mag, ratio))
+    out["torch_warp_frames_ms"] = tm(lambda: torch_warp_frames(mag, q))
+    out["resample_map_ms"] = tm(lambda: ops.pitch_resample_map(y, rho_q, Q, n_valid, N))
+    out["resample_ms"] = tm(lambda: ops.pitch_resample(y, ratio, n_valid, N))
+    out["torch_resample_map_ms"] = tm(lambda: torch_resample_map(y, rho_q, Q, n_valid, N))
+    for key in ("contour", "synth_map", "warp_frames", "resample_map"):
+        out[f"{key}_speedup_vs_torch"] = round(out[f"torch_{key}_ms"] / out[f"{key}_ms"], 2)
+    del C, M, y, res, mag
+    torch.cuda.empty_cache()
+    for name, kw in (("vocoder", {}), ("contour", {"contour_scale": gamma}),
+                     ("contour_formants", {"contour_scale": gamma, "preserve_formants": True}),
+                     ("vocoder_formants", {"preserve_formants": True})):
+        norm = pitchnorm.PitchNormalizer(phase="vocoder", **kw)
+        out[f"normalizer_{name}_ms"] = tm(lambda: norm(wav, lens))
+
+    if not a.no_step:
+        with tempfile.TemporaryDirectory() as tmp:
+            for name, over in (("vocoder", {}), ("contour", {"contour_scale": gamma})):
+                with open(os.path.join(ROOT, "speechbrain_configs", "gender_classifier_pitch_norm.yaml")) as f:
+                    st = load_hyperpyyaml(f, dict({"output_folder": tmp, "batch_size": B, "phase": "vocoder"}, **over))
+                hp = dict(st, **gender.build(st))
+                hp["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pitchnorm.check_pitch_options(st, {}, {}))
+                b = gender.GenderPitchNormBrain(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp,
+                                                run_opts={"device": "cuda:0"})
+                b.on_fit_start()
+                b.modules.train()
+                out[f"step_{name}_ms"] = tm(lambda: b.fit_batch(batch))
+                del b
+                torch.cuda.empty_cache()
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
