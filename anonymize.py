@@ -4,7 +4,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
 
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
-        [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]]
+        [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
 normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
@@ -43,6 +43,11 @@ voice.  Every other mode refuses the option.  The JSON line then carries ``conto
 utterances' ``ratio`` is the mean ratio of the row, and with ``--report_f0 true`` each utterance also gains
 ``f0_std_hz``, the standard deviation of the voiced F0 over the counted frames.
 
+``--f0_method viterbi`` tracks F0 with a Viterbi decode through every frame's d' dips (speech_anonymization_amd.
+pitchnorm.f0_track) instead of first-dip YIN (``yin``, the default).  With ``--pitch_norm true`` it
+steers the normaliser; with ``--report_f0 true``, in any mode, the report is measured with it.  Without either it is
+refused: nothing tracks F0.  The JSON line carries ``"f0_method"`` only when the option is given.
+
 ``--report_stoi true`` adds, in any mode, the intelligibility of every waveform written against the waveform it was
 made from (speech_anonymization_amd.ops.stoi): per utterance ``stoi``, ``estoi`` (both null when the
 utterance has fewer than 30 frames within 40 dB of its loudest) and ``stoi_segments``, and ``stoi_mean`` and
@@ -77,13 +82,14 @@ def _batches(settings, bs, seed):
             yield list(batch.id), batch
 
 
-def _f0_report(wav, lens, want_std=False):
+def _f0_report(wav, lens, want_std=False, f0_method="yin"):
     """(mean voiced F0 in Hz, voiced share) per row of wav [B, N] on the device, over the frames of round(lens N)
-    samples; want_std: also the standard deviation of the voiced F0 over those frames (0 without a voiced frame)"""
+    samples; want_std: also the standard deviation of the voiced F0 over those frames (0 without a voiced frame);
+    f0_method: the tracker it is measured with (--f0_method)"""
     from speech_anonymization_amd import ops
     N = wav.shape[1]
     lens = lens.to(wav.device, torch.float32).contiguous()
-    f0 = pitchnorm.f0_track(wav.contiguous())
+    f0 = pitchnorm.f0_track(wav.contiguous(), method=f0_method, lens=lens)
     _, mean, voiced = ops.pitch_ratio(f0, lens, N)
     frames = (torch.round(lens.double() * N).long() // features.HOP + 1).clamp(max=N // features.HOP + 1)
     rep = mean.cpu().tolist(), (voiced.double() / frames.double()).cpu().tolist()
@@ -139,10 +145,11 @@ def _pitch_norm(settings, device, bs, seed):
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
     contour = pitchnorm.check_contour_options(settings)
+    f0m = pitchnorm.check_f0_option(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
                                    momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant, **phase,
-                                   **contour)
+                                   **contour, **f0m)
     if contour:
         contour = {"contour_scale": pn.contour_scale, "contour_smooth": pn.contour_smooth}
     utts, sto = [], _StoiReport(settings)
@@ -150,7 +157,7 @@ def _pitch_norm(settings, device, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
         out = pn(wavs, lens)
-        rep = _f0_report(out, lens, want_std=bool(contour)) if settings.get("report_f0") else None
+        rep = _f0_report(out, lens, want_std=bool(contour), **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         ratio = pn.last[0].cpu().tolist()
         out = out.cpu()
@@ -167,13 +174,14 @@ def _pitch_norm(settings, device, bs, seed):
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
                            "n_iter": pn.gl.n_iter if pn.gl else None, "seed": seed, "utterances": utts}, **formant,
-                          **phase, **contour, **sto.summary())))
+                          **phase, **contour, **f0m, **sto.summary())))
 
 
 def _formant_shift(settings, device, bs, seed):
     """--formant_ratio X on its own: every utterance's envelope scaled by X and written, no model and no features"""
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
+    f0m = pitchnorm.check_f0_option(settings)
     fs = pitchnorm.FormantShifter(formant["formant_ratio"], n_iter=int(settings.get("n_iter", 32)),
                                   momentum=float(settings.get("momentum", 0.99)), seed=seed,
                                   lifter=formant.get("lifter", 30), **phase)
@@ -182,7 +190,7 @@ def _formant_shift(settings, device, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
         out = fs(wavs, lens)
-        rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        rep = _f0_report(out, lens, **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         out = out.cpu()
         N = out.shape[1]
@@ -196,19 +204,20 @@ def _formant_shift(settings, device, bs, seed):
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True,
                            "n_iter": fs.gl.n_iter if fs.gl else None, "seed": seed, "utterances": utts}, **formant,
-                          **phase, **sto.summary())))
+                          **phase, **f0m, **sto.summary())))
 
 
 def _mcadams(settings, device, bs, seed):
     """--mcadams A / --mcadams_min LO --mcadams_max HI: every utterance McAdams-transformed and written, no model"""
     opts = mcadams.check_mcadams_options(settings)
     mc = mcadams.McAdams(**opts)
+    f0m = pitchnorm.check_f0_option(settings)
     utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
         out = mc(wavs, lens)
-        rep = _f0_report(out, lens) if settings.get("report_f0") else None
+        rep = _f0_report(out, lens, **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         alpha, gain, counts = (v.cpu().tolist() for v in mc.last)
         out = out.cpu()
@@ -223,7 +232,8 @@ def _mcadams(settings, device, bs, seed):
             utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     shown = {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown, **sto.summary())))
+    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown, **f0m,
+                          **sto.summary())))
 
 
 def main(argv):
@@ -263,6 +273,7 @@ def main(argv):
     gl = vocoder.GriffinLim(n_iter=int(settings.get("n_iter", 32)), momentum=float(settings.get("momentum", 0.99)),
                             seed=seed)
     pad = 36 if (mt != "fcae" and not passthrough) else None
+    f0m = pitchnorm.check_f0_option(settings)
     os.makedirs(settings["out_dir"], exist_ok=True)
     utts, sto = [], _StoiReport(settings)
     for ids, batch in _batches(settings, bs, seed):
@@ -282,7 +293,7 @@ def main(argv):
         recon = normed if passthrough else model.reconstruct(normed)
         wav, _, S = vocoder.invert_features(recon, nz, lens, frames=T, return_magnitude=True, gl=gl)
         sc = vocoder.spectral_convergence(wav, S).cpu()
-        rep = _f0_report(wav, lens) if settings.get("report_f0") else None
+        rep = _f0_report(wav, lens, **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, wav, [int(float(v) * wav.shape[1]) for v in lens])
         wav = wav.cpu()
         N = wav.shape[1]
@@ -297,7 +308,7 @@ def main(argv):
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
                       "recon_ckpt": settings.get("recon_ckpt"), "n_iter": gl.n_iter, "seed": seed,
-                      "utterances": utts}, **sto.summary())))
+                      "utterances": utts}, **f0m, **sto.summary())))
 
 
 if __name__ == "__main__":

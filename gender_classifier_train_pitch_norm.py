@@ -7,7 +7,8 @@ still recover once the mean pitch is gone?" -- the number the learned anonymiser
 
     python gender_classifier_train_pitch_norm.py speechbrain_configs/gender_classifier_pitch_norm.yaml \
         --device cuda:0 [--pitch_target_hz 170] [--preserve_formants true | --formant_ratio X] [--lifter 30] \
-        [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--synthetic N] [--key value ...]
+        [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi] \
+        [--synthetic N] [--key value ...]
 
 ``--preserve_formants true`` moves the pitch and leaves the spectral envelope where it was (what the reference's
 WORLD re-synthesis does); ``--formant_ratio X`` scales it by X instead.  Without either the
@@ -15,7 +16,9 @@ formants move with the pitch.  ``--phase vocoder`` re-synthesises with the input
 stretch instead of Griffin-Lim's reconstruction: one pass instead of 32 iterations.
 ``--contour_scale G`` (with ``--phase vocoder``) moves the F0 CONTOUR to target + G (f0 - mean) with a ratio per
 frame: 1 is the reference's additive shift, 0 a monotone voice; ``--contour_smooth S`` is the
-half-width in frames of the triangle the contour is smoothed with (default 2).
+half-width in frames of the triangle the contour is smoothed with (default 2).  ``--f0_method viterbi`` forms the F0
+track the ratios come from with a path decode through every frame's d' dips instead of first-dip
+YIN.
 
 Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
 summary as the last line (with pitch_target_hz added, and the envelope settings that were given)."""
@@ -72,7 +75,7 @@ def main(argv):
     summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
                "best_checkpoint": getattr(brain, "best_checkpoint", None), "pitch_target_hz": pn["target_hz"]}
     summary.update({k: pn[k] for k in ("preserve_formants", "formant_ratio", "lifter", "phase", "contour_scale",
-                                        "contour_smooth") if k in pn})
+                                        "contour_smooth", "f0_method") if k in pn})
     print(json.dumps(summary))
 
 

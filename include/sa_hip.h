@@ -710,6 +710,41 @@ int sa_env_warp_frames(const float* S, const float* q, int B, int T, int n_c, fl
 int sa_pitch_resample_map(const float* y, const int* rho_q, const long long* Q, const int* n_valid, int B, int Nin,
                           int Nout, int T, float* out, void* stream);
 
+/* ---- Viterbi F0 tracking (sa_f0track.hip; ops.f0_candidates, ops.f0_viterbi): a path through the
+ * dips of every frame's d' in place of YIN's first dip under the threshold.  dprime [B][T][267] fp32 is what
+ * sa_yin_f0 writes; tau_min = 40, tau_max = 266 (sa_yin_dim); K = 8 candidates per frame; states 0..7 are the
+ * candidates in ascending lag, state 8 is unvoiced.  Every cost is an integer in units of 2^-16.
+ *   sa_f0_candidates: a lag tau in [tau_min, tau_max - 1] is a dip when d'(tau) <= d'(tau - 1) and d'(tau) <
+ *     d'(tau + 1); its cost is q = rint(clamp(d'(tau), 0, 1) 2^16).  The K dips of smallest (q, tau), in that
+ *     lexicographic order, go to cand_tau, cand_q [B][T][K] int32 in ascending tau; unused slots hold tau = -1, q = 0.
+ *   sa_f0_viterbi, per row b over its first F_b = min(T, round(lens_b N) / 160 + 1) frames (formed as sa_pitch_ratio
+ *     forms it):  the weights voicing_cost v, switch_cost s, jump_cost j (per octave) and lag_bias beta (per octave)
+ *     become ints once, on the host: w_q = (int)lrint(w 2^16).  LOG = log_q, int32 [tau_max + 1], the caller's:
+ *     rint(log2(max(tau, 1)) 2^16).
+ *       local cost   l(t, i) = q + ((beta_q (LOG[tau] - LOG[tau_min])) >> 16) for a present candidate, l(t, 8) = v_q;
+ *                    an absent candidate (tau < 0) is not a state;
+ *       transition   0 unvoiced -> unvoiced;  s_q between voiced and unvoiced, either way;
+ *                    (j_q |LOG[tau_a] - LOG[tau_s]|) >> 16 between two candidates;
+ *       delta_0(s) = l(0, s);  delta_t(s) = l(t, s) + min_a (delta_{t-1}(a) + trans(a, s)), psi_t(s) the argmin;
+ *       ties go to the smaller state index, at every step and in the final argmin over delta at F_b - 1.
+ *     int64 sums throughout.  psi: the caller's workspace, uint8 [B][T][K + 1]; its contents mean nothing between
+ *     calls.  path [B][T] int32: the candidate index after the backtrace, -1 for unvoiced and for t >= F_b.
+ *     f0 [B][T] fp32: 16000 / (tau + off) of the chosen lag with sa_yin_f0's parabola (fp64 from the fp32 d', den > 0
+ *     else off = 0, rounded once) -- a frame on which both trackers choose the same lag carries the same bits; 0 for
+ *     unvoiced frames and for t >= F_b.
+ *   What the kernels read from device memory is clamped before it becomes an index: cand_tau to -1 or [tau_min,
+ *   tau_max - 1], cand_q to [0, 2^16], lens as sa_pitch_ratio does, every index into LOG to [0, tau_max].
+ *   One wave per frame (candidates) and per row (decode); no atomics: the same bits on every run.
+ *   sa_f0v_dim(which): 0 K = 8, 1 states 9, 2 frames per workgroup of sa_f0_candidates, 3 frames per staged chunk of
+ *     sa_f0_viterbi, 4 cost fraction bits 16; else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer, B < 1 or > 65535, T < 1 or > 2^23, N < 1 or > 2^30, a weight that is
+ *     NaN or outside [0, 4]. */
+int sa_f0v_dim(int which);
+int sa_f0_candidates(const float* dprime, int B, int T, int* cand_tau, int* cand_q, void* stream);
+int sa_f0_viterbi(const float* dprime, const int* cand_tau, const int* cand_q, const float* lens, const int* log_q,
+                  int B, int T, int N, float voicing_cost, float switch_cost, float jump_cost, float lag_bias,
+                  unsigned char* psi, int* path, float* f0, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

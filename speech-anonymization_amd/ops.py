@@ -1340,3 +1340,81 @@ def stoi(ref, deg, n_valid, extended=True):
     L.check(L.load().sa_stoi(_f(ref), _f(deg), _f(n_valid), B, N, _f(stoi_taps(dev)), _f(out), _f(ext), _f(frames),
                              _f(segments), _f(ws), L.stream()), "sa_stoi")
     return out, ext, frames, segments
+
+
+# ---- Viterbi F0 tracking (csrc/sa_f0track.hip; pitchnorm.f0_track) ----
+F0V_K, F0V_STATES, F0V_FRAC = 8, 9, 16     # sa_f0v_dim(0), (1), (4)
+F0V_TMIN = 40                              # sa_yin_dim(3)
+F0V_WEIGHT_MAX = 4.0
+
+_f0v_in = functools.partial(_aug_in, family="F0 tracking")
+_f0v_log, _f0v_ws = {}, {}
+
+
+def f0v_log_table(device):
+    """LOG[tau] = rint(log2(max(tau, 1)) 2^16), int32 [267]: computed once in fp64 on the host, kept per device"""
+    device = torch.device(device)
+    t = _f0v_log.get(device)
+    if t is None:
+        import numpy as np
+        lg = np.rint(np.log2(np.maximum(np.arange(YIN_TMAX + 1), 1).astype(np.float64)) * (1 << F0V_FRAC))
+        t = _f0v_log[device] = torch.from_numpy(lg.astype(np.int32)).to(device)
+    return t
+
+
+def _f0v_workspace(B, T, device):
+    """psi, uint8 [B, T, 9]: one buffer per device, grown when a call needs more; its contents mean nothing between
+    calls"""
+    device = torch.device(device)
+    ws = _f0v_ws.get(device)
+    if ws is None or ws.numel() < B * T * F0V_STATES:
+        ws = _f0v_ws[device] = torch.empty(B * T * F0V_STATES, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _f0v_dprime(dprime):
+    if _f0v_in(dprime, "dprime").dim() != 3 or dprime.shape[2] != YIN_TMAX + 1 or dprime.numel() == 0:
+        raise L.SaHipError(f"dprime: expected [B, T, {YIN_TMAX + 1}] with B, T >= 1, got {tuple(dprime.shape)}")
+    B, T, _ = dprime.shape
+    if B > GL_MAX_B or T > GL_MAX_T:
+        raise L.SaHipError(f"dprime: [B, T] = [{B}, {T}] -- B up to {GL_MAX_B} (a grid extent), T up to {GL_MAX_T}")
+    return B, T
+
+
+def f0_candidates(dprime):
+    """dprime fp32 [B, T, 267] (yin_f0's) -> (tau, q) int32 [B, T, 8]: per frame the 8 dips of d' with the smallest
+    (q, tau), q = rint(clamp(d', 0, 1) 2^16), in ascending lag; unused slots hold tau = -1, q = 0 (sa_f0_candidates)"""
+    B, T = _f0v_dprime(dprime)
+    tau = torch.empty(B, T, F0V_K, dtype=torch.int32, device=dprime.device)
+    q = torch.empty(B, T, F0V_K, dtype=torch.int32, device=dprime.device)
+    L.check(L.load().sa_f0_candidates(_f(dprime), B, T, _f(tau), _f(q), L.stream()), "sa_f0_candidates")
+    return tau, q
+
+
+def f0_viterbi(dprime, tau, q, lens, N, voicing_cost=0.15, switch_cost=0.14, jump_cost=0.35, lag_bias=0.01,
+               return_path=False, log_q=None):
+    """dprime [B, T, 267], f0_candidates' tau and q, relative lengths lens [B], N samples per row -> f0 fp32 [B, T] in
+    Hz along the cheapest path through the candidates and an unvoiced state, 0 where unvoiced and beyond the frames of
+    round(lens N) samples (sa_f0_viterbi).  The costs are per unit of d' (voicing, switch) and per octave (jump, lag
+    bias), each in [0, 4].  return_path: also path int32 [B, T], the candidate index or -1.  log_q: the int32 [267]
+    table of rint(log2(tau) 2^16) to use instead of the cached one (tests)."""
+    B, T = _f0v_dprime(dprime)
+    _f0v_in(tau, "tau", torch.int32, (B, T, F0V_K))
+    _f0v_in(q, "q", torch.int32, (B, T, F0V_K))
+    _f0v_in(lens, "lens", shape=(B,))
+    if log_q is not None:
+        _f0v_in(log_q, "log_q", torch.int32, (YIN_TMAX + 1,))
+    N = int(N)
+    if N < 1 or N > PN_MAX_N:
+        raise L.SaHipError(f"f0_viterbi: N = {N} in 1..{PN_MAX_N} expected")
+    costs = [float(voicing_cost), float(switch_cost), float(jump_cost), float(lag_bias)]
+    if not all(0.0 <= w <= F0V_WEIGHT_MAX for w in costs):
+        raise L.SaHipError(f"f0_viterbi: voicing, switch, jump and lag-bias costs in [0, {F0V_WEIGHT_MAX:g}] expected, "
+                           f"got {costs}")
+    dev = dprime.device
+    log_q = f0v_log_table(dev) if log_q is None else log_q
+    path = torch.empty(B, T, dtype=torch.int32, device=dev)
+    f0 = torch.empty(B, T, dtype=torch.float32, device=dev)
+    L.check(L.load().sa_f0_viterbi(_f(dprime), _f(tau), _f(q), _f(lens), _f(log_q), B, T, N, *(C.c_float(w) for w in costs),
+                                   _f(_f0v_workspace(B, T, dev)), _f(path), _f(f0), L.stream()), "sa_f0_viterbi")
+    return (f0, path) if return_path else f0

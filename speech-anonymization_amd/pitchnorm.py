@@ -23,7 +23,10 @@ phases: stretch [-> warp] -> sa_pv_synth -> one sa_gl_istft.  ``"griffin_lim"`` 
 
 The contour: with ``contour_scale`` gamma (and ``phase="vocoder"``) the ratio varies from frame to
 frame so that the output's F0 contour is target + gamma (f0 - mean) -- 1 the additive shift of the reference's
-baseline, 0 a monotone voice: sa_pitch_contour -> [sa_env_warp_frames] -> sa_pv_synth_map -> sa_pitch_resample_map."""
+baseline, 0 a monotone voice: sa_pitch_contour -> [sa_env_warp_frames] -> sa_pv_synth_map -> sa_pitch_resample_map.
+
+The track: with ``f0_method="viterbi"`` the F0 of every path above is a Viterbi decode through each
+frame's d' dips (sa_f0_candidates -> sa_f0_viterbi on sa_yin_f0's d') instead of the first dip under the threshold."""
 import math
 
 import torch
@@ -40,12 +43,42 @@ LIFTER_MAX = 64                              # sa_env_dim(3)
 PHASES = ("griffin_lim", "vocoder")          # where the re-synthesis takes its phases from
 CONTOUR_LOW, CONTOUR_HIGH = 0.0, 2.0         # contour_scale gamma: 0 a monotone voice, 1 the additive shift
 SMOOTH_MAX = 8                               # sa_contour_dim(1)
+F0_METHODS = ("yin", "viterbi")              # first dip under the threshold; a path through every frame's dips
+F0_COSTS = ("voicing_cost", "switch_cost", "jump_cost", "lag_bias")
+F0_COST_LOW, F0_COST_HIGH = 0.0, 4.0         # what sa_f0_viterbi takes
 
 
-def f0_track(wav, threshold=0.15):
-    """wav [B, N] (device, fp32) -> f0 [B, N // 160 + 1] in Hz, one value per Fbank frame, 0 where unvoiced"""
+def f0_track(wav, threshold=0.15, method="yin", lens=None, **costs):
+    """wav [B, N] (device, fp32) -> f0 [B, N // 160 + 1] in Hz, one value per Fbank frame, 0 where unvoiced.
+    ``method="viterbi"`` decodes a path through every frame's d' dips instead of taking the first
+    one under the threshold: sa_yin_f0's d' -> sa_f0_candidates -> sa_f0_viterbi.  ``lens`` [B] (relative lengths;
+    None: every frame counts) cuts the decode at the frames of round(lens N) samples, 0 beyond them; ``costs``:
+    voicing_cost, switch_cost, jump_cost, lag_bias of ops.f0_viterbi."""
     from . import ops
-    return ops.yin_f0(wav, threshold)
+    method, costs = f0_settings("f0_track", method, costs)
+    if method == "yin":
+        return ops.yin_f0(wav, threshold)
+    _, dprime = ops.yin_f0(wav, threshold, return_dprime=True)
+    if lens is None:
+        lens = torch.ones(wav.shape[0], dtype=torch.float32, device=wav.device)
+    tau, q = ops.f0_candidates(dprime)
+    return ops.f0_viterbi(dprime, tau, q, lens.to(wav.device, torch.float32).contiguous(), wav.shape[1], **costs)
+
+
+def f0_settings(who, method, costs):
+    """-> (method, costs as a dict of floats), or ValueError"""
+    if method not in F0_METHODS:
+        raise ValueError(f"{who}: f0_method {method!r}: one of {', '.join(F0_METHODS)} expected")
+    costs = dict(costs or {})
+    for key, value in costs.items():
+        if key not in F0_COSTS:
+            raise ValueError(f"{who}: unknown F0 cost {key!r}: {', '.join(F0_COSTS)} expected")
+        if isinstance(value, bool) or not F0_COST_LOW <= float(value) <= F0_COST_HIGH:
+            raise ValueError(f"{who}: {key} {value} in {F0_COST_LOW:g}..{F0_COST_HIGH:g} expected")
+        costs[key] = float(value)
+    if costs and method != "viterbi":
+        raise ValueError(f"{who}: {next(iter(costs))} needs f0_method=\"viterbi\" (YIN has no path costs)")
+    return method, costs
 
 
 def stretched_frames(Tp, ratio):
@@ -98,11 +131,15 @@ class PitchNormalizer:
     ``phase="vocoder"`` carries the input's phases through the stretch instead of running Griffin-Lim: no iterations,
     no random numbers (n_iter, momentum and seed are then unused, and ``gl`` is None).  ``contour_scale`` gamma (needs
     ``phase="vocoder"``) moves the contour to target + gamma (f0 - mean) with a ratio per frame, smoothed by a triangle
-    of half-width ``contour_smooth`` frames; ``last[0]`` is then the row's mean ratio.  None: one ratio per row."""
+    of half-width ``contour_smooth`` frames; ``last[0]`` is then the row's mean ratio.  None: one ratio per row.
+    ``f0_method="viterbi"`` forms the track with the path decode instead of first-dip YIN, with
+    ``f0_costs`` (a dict of voicing_cost, switch_cost, jump_cost, lag_bias) in place of its defaults."""
 
     def __init__(self, target_hz=170.0, n_iter=32, momentum=0.99, seed=1, r_min=0.5, r_max=2.0, min_voiced=5,
                  threshold=0.15, preserve_formants=False, formant_ratio=None, lifter=30, floor_rel=1e-4,
-                 max_gain_db=40.0, phase="griffin_lim", contour_scale=None, contour_smooth=2):
+                 max_gain_db=40.0, phase="griffin_lim", contour_scale=None, contour_smooth=2, f0_method="yin",
+                 f0_costs=None):
+        self.f0_method, self.f0_costs = f0_settings("PitchNormalizer", f0_method, f0_costs)
         self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
             "PitchNormalizer", preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db)
         self.phase = phase_setting("PitchNormalizer", phase)
@@ -125,9 +162,19 @@ class PitchNormalizer:
         lens = lens.to(wavs.device, torch.float32).contiguous()
         if self.contour_scale is not None:
             return self.shift_contour(wavs, lens)
-        f0 = ops.yin_f0(wavs, self.threshold)
+        f0 = self.track(wavs, lens)
         self.last = ops.pitch_ratio(f0, lens, wavs.shape[1], self.target_hz, self.r_min, self.r_max, self.min_voiced)
         return self.shift(wavs, lens, self.last[0])
+
+    def track(self, wavs, lens, N=None):
+        """the F0 track the ratios are formed from: sa_yin_f0, or with f0_method="viterbi" the decode over the frames
+        of round(lens N) samples (N: the unpadded width when wavs is padded)"""
+        from . import ops
+        if self.f0_method == "yin":
+            return ops.yin_f0(wavs, self.threshold)
+        _, dprime = ops.yin_f0(wavs, self.threshold, return_dprime=True)
+        tau, q = ops.f0_candidates(dprime)
+        return ops.f0_viterbi(dprime, tau, q, lens, wavs.shape[1] if N is None else N, **self.f0_costs)
 
     @torch.no_grad()
     def shift_contour(self, wavs, lens):
@@ -138,7 +185,7 @@ class PitchNormalizer:
         B, N = wavs.shape
         Np = HOP * -(-N // HOP)
         wp = (torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs).contiguous()
-        f0 = ops.yin_f0(wp, self.threshold)
+        f0 = self.track(wp, lens, N)
         rho_q, Q, Tq, mean, voiced = ops.pitch_contour(f0, lens, N, self.target_hz, self.contour_scale,
                                                        self.contour_smooth, self.r_min, self.r_max, self.min_voiced)
         T = f0.shape[1]
@@ -266,6 +313,18 @@ def check_phase_option(settings, block=None):
     return {"phase": value}
 
 
+def check_f0_option(settings, block=None):
+    """the ``f0_method`` of a recipe's ``pitch_norm:`` block (if any) under the top-level override -> a dict that
+    carries the key only when it was given; anything but yin and viterbi is refused in one line"""
+    value = settings.get("f0_method", (block or {}).get("f0_method"))
+    if value is None:
+        return {}
+    if not isinstance(value, str) or value not in F0_METHODS:
+        raise SystemExit(f"--f0_method {value}: yin (the first dip of d' under the threshold, the default) or viterbi "
+                         "(a path decoded through every frame's dips)")
+    return {"f0_method": value}
+
+
 def check_contour_options(settings, block=None):
     """``contour_scale`` and ``contour_smooth`` of a recipe's ``pitch_norm:`` block (if any) under the top-level
     overrides -> a dict that carries a key only when it was given; each is refused in one line when out of range or
@@ -325,4 +384,5 @@ def check_pitch_options(settings, run_opts, environ=None):
     if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
         raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
     return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn),
-                **check_phase_option(settings, pn), **check_contour_options(settings, pn))
+                **check_phase_option(settings, pn), **check_contour_options(settings, pn),
+                **check_f0_option(settings, pn))

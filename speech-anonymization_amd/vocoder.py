@@ -190,6 +190,9 @@ def check_anonymize_options(settings, run_opts, environ=None):
     if check_contour_options(settings) and not settings.get("pitch_norm"):    # 
         raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
                          "pitch")
+    from .pitchnorm import check_f0_option
+    if check_f0_option(settings) and not settings.get("pitch_norm") and not settings.get("report_f0"):
+        raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
     if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only and not mcadams:
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
     if formant.get("preserve_formants") and not settings.get("pitch_norm"):

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Times the Viterbi F0 tracker (csrc/sa_f0track.hip) at B = 32 utterances of 10 s: each new kernel
+through its binding, sa_yin_f0 with and without the d' output, the whole pitchnorm.f0_track(method="viterbi") call, and
+the same definition in torch operators on the same device in the same run (the candidates by a masked top-k and a
+sort; the decode by a loop over the frames on [B, 9, 9] int64 tensors, ties resolved by packing the predecessor's index
+under the cost).  The torch paths are first checked to give the kernels' candidates and paths exactly.
+
+Device events around each call after a warm-up; the median of --steps calls.  Also the share of counted frames on which
+the two methods' f0 differ on data.synthetic_gender_dataset's utterances (its clean harmonic rows: no real speech).
+Prints one JSON line (and writes it to --out)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+SR, HOP, TAU_MIN, TAU_MAX, K = 16000, 160, 40, 266, 8
+BIG = 1 << 40
+INF = 1 << 56
+
+
+def time_calls(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts)
+
+
+def torch_candidates(dp):
+    c = dp[..., TAU_MIN:TAU_MAX]
+    dip = (c <= dp[..., TAU_MIN - 1:TAU_MAX - 1]) & (c < dp[..., TAU_MIN + 1:TAU_MAX + 1])
+    q = torch.round(c.clamp(0.0, 1.0) * 65536.0).long()
+    tau = torch.arange(TAU_MIN, TAU_MAX, device=dp.device)
+    key = torch.where(dip, (q << 9) | tau, torch.full_like(q, BIG))
+    top = key.topk(K, dim=-1, largest=False).values
+    lag = torch.where(top < BIG, top & 511, torch.full_like(top, 1 << 20))
+    lag, order = lag.sort(-1)
+    cost = (top >> 9).gather(-1, order)
+    live = lag < (1 << 20)
+    return (torch.where(live, lag, torch.full_like(lag, -1)).int(),
+            torch.where(live, cost, torch.zeros_like(cost)).int())
+
+
+def torch_viterbi(tau, q, lens, N, LOG, wq):
+    """-> path int32 [B, T]"""
+    vq, sq, jq, bq = wq
+    B, T, _ = tau.shape
+    dev = tau.device
+    F = (torch.round(lens.double() * N).clamp(0, N).long() // HOP + 1).clamp(max=T)
+    LOG = LOG.long()
+    lg = LOG[tau.long().clamp(min=0)]
+    one = torch.ones(B, T, 1, dtype=torch.bool, device=dev)
+    present = torch.cat([tau >= 0, one], -1)
+    local = torch.cat([q.long() + ((bq * (lg - LOG[TAU_MIN])) >> 16), torch.full((B, T, 1), vq, device=dev)], -1)
+    lg9 = torch.cat([lg, torch.zeros(B, T, 1, dtype=torch.long, device=dev)], -1)
+    idx = torch.arange(K + 1, device=dev)
+    voiced = idx < K
+    both = voiced[:, None] & voiced[None, :]
+    mixed = voiced[:, None] ^ voiced[None, :]
+    inf = torch.full((), INF, device=dev)
+    delta = torch.where(present[:, 0], local[:, 0], inf)
+    psi = torch.zeros(B, T, K + 1, dtype=torch.long, device=dev)
+    for t in range(1, T):
+        jump = (jq * (lg9[:, t - 1, :, None] - lg9[:, t, None, :]).abs()) >> 16
+        tr = torch.where(both, jump, torch.where(mixed, torch.full_like(jump, sq), torch.zeros_like(jump)))
+        packed = ((delta[:, :, None] + tr) * 16 + idx[None, :, None]).min(1).values
+        psi[:, t] = packed & 15
+        new = torch.where(present[:, t], local[:, t] + (packed >> 4), inf)
+        delta = torch.where((t < F)[:, None], new, delta)
+    state = ((delta * 16 + idx).min(1).values & 15)
+    path = torch.full((B, T), -1, dtype=torch.long, device=dev)
+    rows = torch.arange(B, device=dev)
+    for t in range(T - 1, -1, -1):
+        on = t < F
+        path[:, t] = torch.where(on & (state < K), state, torch.full_like(state, -1))
+        state = torch.where(on, psi[rows, t, state], state)
+    return path.int()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "f0_viterbi_bench.json"))
+    a = ap.parse_args()
+    assert a.steps >= 20, "the median of at least 20 calls"
+    dev = torch.device("cuda:0")
+    from speech_anonymization_amd import data, ops, pitchnorm
+    from tests import f0v_ref as R
+    B, N = a.B, int(a.seconds * SR)
+    wav_cpu, lens_cpu = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N))).sig
+    wav, lens = wav_cpu.to(dev).float().contiguous(), lens_cpu.to(dev).float().contiguous()
+    f0_y, dp = ops.yin_f0(wav, return_dprime=True)
+    T = f0_y.shape[1]
+    tau, q = ops.f0_candidates(dp)
+    f0_v, path = ops.f0_viterbi(dp, tau, q, lens, N, return_path=True)
+    LOG, wq = ops.f0v_log_table(dev), R.weights_q()
+    t_tau, t_q = torch_candidates(dp)
+    assert torch.equal(t_tau, tau) and torch.equal(t_q, q), "torch candidates differ from the kernel's"
+    assert torch.equal(torch_viterbi(tau, q, lens, N, LOG, wq), path), "torch decode differs from the kernel's"
+    frames = (torch.round(lens.double() * N).clamp(0, N).long() // HOP + 1).clamp(max=T)
+    live = torch.arange(T, device=dev)[None, :] < frames[:, None]
+    differ = int(((f0_v != f0_y) & live).sum())
+    out = {"B": B, "N": N, "T": T, "steps": a.steps, "frames_counted": int(live.sum()), "frames_differ": differ,
+           "differ_share": round(differ / int(live.sum()), 6),
+           "voiced_yin": int(((f0_y > 0) & live).sum()), "voiced_viterbi": int((f0_v > 0).sum()),
+           "dprime_bytes": dp.numel() * 4}
+    tm = lambda fn: round(time_calls(fn, a.warmup, a.steps), 4)
+    out["yin_ms"] = tm(lambda: ops.yin_f0(wav))
+    out["yin_dprime_ms"] = tm(lambda: ops.yin_f0(wav, return_dprime=True))
+    out["candidates_ms"] = tm(lambda: ops.f0_candidates(dp))
+    out["viterbi_ms"] = tm(lambda: ops.f0_viterbi(dp, tau, q, lens, N))
+    out["f0_track_viterbi_ms"] = tm(lambda: pitchnorm.f0_track(wav, method="viterbi", lens=lens))
+    out["f0_track_yin_ms"] = tm(lambda: pitchnorm.f0_track(wav))
+    out["torch_candidates_ms"] = tm(lambda: torch_candidates(dp))
+    out["torch_viterbi_ms"] = tm(lambda: torch_viterbi(tau, q, lens, N, LOG, wq))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
