@@ -91,7 +91,7 @@ def _f0_report(wav, lens, want_std=False, f0_method="yin"):
     lens = lens.to(wav.device, torch.float32).contiguous()
     f0 = pitchnorm.f0_track(wav.contiguous(), method=f0_method, lens=lens)
     _, mean, voiced = ops.pitch_ratio(f0, lens, N)
-    frames = (torch.round(lens.double() * N).long() // features.HOP + 1).clamp(max=N // features.HOP + 1)
+    frames = (pitchnorm.n_valid(lens, N, wav.device).long() // features.HOP + 1).clamp(max=N // features.HOP + 1)
     rep = mean.cpu().tolist(), (voiced.double() / frames.double()).cpu().tolist()
     if not want_std:
         return rep
@@ -145,118 +145,55 @@ def _pitch_norm(settings, device, bs, seed):
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
     contour = pitchnorm.check_contour_options(settings)
-    f0m = pitchnorm.check_f0_option(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
                                    momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant, **phase,
-                                   **contour, **f0m)
+                                   **contour, **pitchnorm.check_f0_option(settings))
     if contour:
         contour = {"contour_scale": pn.contour_scale, "contour_smooth": pn.contour_smooth}
-    utts, sto = [], _StoiReport(settings)
-    for ids, batch in _batches(settings, bs, seed):
-        wavs, lens = batch.sig
-        wavs = wavs.to(device).contiguous()
+
+    def step(ids, wavs, lens):
         out = pn(wavs, lens)
-        rep = _f0_report(out, lens, want_std=bool(contour), **f0m) if settings.get("report_f0") else None
-        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
-        ratio = pn.last[0].cpu().tolist()
-        out = out.cpu()
-        N = out.shape[1]
-        for i, uid in enumerate(ids):
-            n = int(round(float(lens[i]) * N))
-            sig = out[i, :n]
-            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0, "ratio": ratio[i]})
-            if rep:
-                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
-                if contour:
-                    utts[-1].update(f0_std_hz=rep[2][i])
-            utts[-1].update(sto.keys(i))
-            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "pitch_norm": True, "pitch_target_hz": pn.target_hz,
-                           "n_iter": pn.gl.n_iter if pn.gl else None, "seed": seed, "utterances": utts}, **formant,
-                          **phase, **contour, **f0m, **sto.summary())))
+        return out, _counts(lens, out.shape[1]), [{"ratio": r} for r in pn.last[0].cpu().tolist()], None
+
+    return step, {"pitch_norm": True, "pitch_target_hz": pn.target_hz, "n_iter": pn.gl.n_iter if pn.gl else None,
+                  "seed": seed}, dict(formant, **phase, **contour)
 
 
 def _formant_shift(settings, device, bs, seed):
     """--formant_ratio X on its own: every utterance's envelope scaled by X and written, no model and no features"""
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
-    f0m = pitchnorm.check_f0_option(settings)
     fs = pitchnorm.FormantShifter(formant["formant_ratio"], n_iter=int(settings.get("n_iter", 32)),
                                   momentum=float(settings.get("momentum", 0.99)), seed=seed,
                                   lifter=formant.get("lifter", 30), **phase)
-    utts, sto = [], _StoiReport(settings)
-    for ids, batch in _batches(settings, bs, seed):
-        wavs, lens = batch.sig
-        wavs = wavs.to(device).contiguous()
+
+    def step(ids, wavs, lens):
         out = fs(wavs, lens)
-        rep = _f0_report(out, lens, **f0m) if settings.get("report_f0") else None
-        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
-        out = out.cpu()
-        N = out.shape[1]
-        for i, uid in enumerate(ids):
-            n = int(round(float(lens[i]) * N))
-            sig = out[i, :n]
-            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0})
-            if rep:
-                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
-            utts[-1].update(sto.keys(i))
-            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "formant_shift": True,
-                           "n_iter": fs.gl.n_iter if fs.gl else None, "seed": seed, "utterances": utts}, **formant,
-                          **phase, **f0m, **sto.summary())))
+        return out, _counts(lens, out.shape[1]), [{}] * len(ids), None
+
+    return step, {"formant_shift": True, "n_iter": fs.gl.n_iter if fs.gl else None, "seed": seed}, \
+        dict(formant, **phase)
 
 
 def _mcadams(settings, device, bs, seed):
     """--mcadams A / --mcadams_min LO --mcadams_max HI: every utterance McAdams-transformed and written, no model"""
     opts = mcadams.check_mcadams_options(settings)
     mc = mcadams.McAdams(**opts)
-    f0m = pitchnorm.check_f0_option(settings)
-    utts, sto = [], _StoiReport(settings)
-    for ids, batch in _batches(settings, bs, seed):
-        wavs, lens = batch.sig
-        wavs = wavs.to(device).contiguous()
+
+    def step(ids, wavs, lens):
         out = mc(wavs, lens)
-        rep = _f0_report(out, lens, **f0m) if settings.get("report_f0") else None
-        sto.score(ids, wavs, lens, out, _counts(lens, out.shape[1]))
         alpha, gain, counts = (v.cpu().tolist() for v in mc.last)
-        out = out.cpu()
-        N = out.shape[1]
-        for i, uid in enumerate(ids):
-            n = int(round(float(lens[i]) * N))
-            sig = out[i, :n]
-            utts.append({"id": uid, "samples": n, "peak": float(sig.abs().max()) if n else 0.0, "alpha": alpha[i],
-                         "gain": gain[i], "silent_frames": counts[i][1], "fallback_frames": counts[i][2]})
-            if rep:
-                utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
-            utts[-1].update(sto.keys(i))
-            data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    shown = {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "mcadams": True, "utterances": utts}, **shown, **f0m,
-                          **sto.summary())))
+        return out, _counts(lens, out.shape[1]), [
+            {"alpha": alpha[i], "gain": gain[i], "silent_frames": counts[i][1], "fallback_frames": counts[i][2]}
+            for i in range(len(ids))], None
+
+    return step, {"mcadams": True}, {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
 
 
-def main(argv):
-    hparams_file, run_opts, overrides = parse_arguments(argv)
-    with open(hparams_file) as fin:
-        settings = load_plain(fin, overrides)
-    vocoder.check_anonymize_options(settings, run_opts)
-    device = torch.device(run_opts.get("device", "cuda:0"))
-    passthrough = bool(settings.get("passthrough"))
-    bs, seed = int(settings.get("batch_size", 3)), int(settings.get("seed", 1986))
-    if any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")):
-        torch.cuda.set_device(device)
-        os.makedirs(settings["out_dir"], exist_ok=True)
-        return _mcadams(settings, device, bs, seed)
-    if settings.get("pitch_norm"):
-        torch.cuda.set_device(device)
-        os.makedirs(settings["out_dir"], exist_ok=True)
-        return _pitch_norm(settings, device, bs, seed)
-    if settings.get("formant_ratio") is not None:
-        torch.cuda.set_device(device)
-        os.makedirs(settings["out_dir"], exist_ok=True)
-        return _formant_shift(settings, device, bs, seed)
-    mt = settings["model_type"]
+def _model(settings, device, bs, seed):
+    """an anonymiser's reconstruction (or with --passthrough true the original features) inverted by Griffin-Lim"""
+    mt, passthrough = settings["model_type"], bool(settings.get("passthrough"))
     model = norm = None
     if not passthrough:
         ext = None
@@ -267,18 +204,13 @@ def main(argv):
         model = model.to(device)
     if settings.get("recon_ckpt"):
         norm = gender.load_recon_normalizer(settings["recon_ckpt"])
-    torch.cuda.set_device(device)
     fbank = features.Fbank(int(settings.get("sample_rate", 16000)), int(settings.get("n_fft", 400)),
                            int(settings.get("n_mels", 80))).to(device)
     gl = vocoder.GriffinLim(n_iter=int(settings.get("n_iter", 32)), momentum=float(settings.get("momentum", 0.99)),
                             seed=seed)
     pad = 36 if (mt != "fcae" and not passthrough) else None
-    f0m = pitchnorm.check_f0_option(settings)
-    os.makedirs(settings["out_dir"], exist_ok=True)
-    utts, sto = [], _StoiReport(settings)
-    for ids, batch in _batches(settings, bs, seed):
-        wavs, lens = batch.sig
-        wavs = wavs.to(device)
+
+    def step(ids, wavs, lens):
         feats = fbank(wavs)
         T = feats.shape[1]
         if T < 2:
@@ -292,23 +224,52 @@ def main(argv):
             normed = nz(feats, lens, epoch=1, pad_multiple=pad)
         recon = normed if passthrough else model.reconstruct(normed)
         wav, _, S = vocoder.invert_features(recon, nz, lens, frames=T, return_magnitude=True, gl=gl)
-        sc = vocoder.spectral_convergence(wav, S).cpu()
-        rep = _f0_report(wav, lens, **f0m) if settings.get("report_f0") else None
-        sto.score(ids, wavs, lens, wav, [int(float(v) * wav.shape[1]) for v in lens])
-        wav = wav.cpu()
-        N = wav.shape[1]
+        # (int() truncates here, as invert_features documents; the signal-processing modes round)
+        return wav, [int(float(v) * wav.shape[1]) for v in lens], [{}] * len(ids), \
+            vocoder.spectral_convergence(wav, S).cpu()
+
+    return step, {"model_type": mt, "passthrough": passthrough, "recon_ckpt": settings.get("recon_ckpt"),
+                  "n_iter": gl.n_iter, "seed": seed}, {}
+
+
+MODES = {"mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
+         "model": _model}
+
+
+def main(argv):
+    hparams_file, run_opts, overrides = parse_arguments(argv)
+    with open(hparams_file) as fin:
+        settings = load_plain(fin, overrides)
+    vocoder.check_anonymize_options(settings, run_opts)
+    device = torch.device(run_opts.get("device", "cuda:0"))
+    bs, seed = int(settings.get("batch_size", 3)), int(settings.get("seed", 1986))
+    torch.cuda.set_device(device)
+    os.makedirs(settings["out_dir"], exist_ok=True)
+    # step(ids, wavs on the device, lens) -> (the waveforms to write, on the device; the samples of each row; the
+    # mode's own keys per utterance; the spectral convergence per row or None); head and tail: the mode's keys of the
+    # final object before and after "utterances"
+    step, head, tail = MODES[vocoder.anonymize_mode(settings)](settings, device, bs, seed)
+    f0m = pitchnorm.check_f0_option(settings)
+    want_std = "contour_scale" in tail
+    utts, sto = [], _StoiReport(settings)
+    for ids, batch in _batches(settings, bs, seed):
+        wavs, lens = batch.sig
+        wavs = wavs.to(device).contiguous()
+        out, counts, extra, sc = step(ids, wavs, lens)
+        rep = _f0_report(out, lens, want_std=want_std, **f0m) if settings.get("report_f0") else None
+        sto.score(ids, wavs, lens, out, counts)
+        out = out.cpu()
         for i, uid in enumerate(ids):
-            n = int(float(lens[i]) * N)
-            sig = wav[i, :n]
-            utts.append({"id": uid, "spectral_convergence": float(sc[i]), "samples": n,
-                         "peak": float(sig.abs().max()) if n else 0.0})
+            sig = out[i, :counts[i]]
+            utts.append(dict({"id": uid}, **({} if sc is None else {"spectral_convergence": float(sc[i])}),
+                             samples=counts[i], peak=float(sig.abs().max()) if counts[i] else 0.0, **extra[i]))
             if rep:
                 utts[-1].update(f0_mean_hz=rep[0][i], voiced_share=rep[1][i])
+                if want_std:
+                    utts[-1].update(f0_std_hz=rep[2][i])
             utts[-1].update(sto.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps(dict({"out_dir": settings["out_dir"], "model_type": mt, "passthrough": passthrough,
-                      "recon_ckpt": settings.get("recon_ckpt"), "n_iter": gl.n_iter, "seed": seed,
-                      "utterances": utts}, **f0m, **sto.summary())))
+    print(json.dumps(dict({"out_dir": settings["out_dir"]}, **head, utterances=utts, **tail, **f0m, **sto.summary())))
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ import os
 import sys
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, gender
+from speech_anonymization_amd import gender
 from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
 
 
@@ -29,34 +29,10 @@ def main(argv):
     run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
     brain = gender.GenderBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,
                                run_opts=run_opts, checkpointer=hparams["checkpointer"])
-    bs, seed = int(hparams["batch_size"]), int(hparams["seed"])
     counter = hparams["epoch_counter"]
-    if synthetic:
-        n = int(synthetic)
-        held = max(bs, n // 4)
-        make = lambda k, s, ep=0: data.synthetic_gender_dataset(k, bs, seed=s + ep)
-        train = lambda epoch: make(n, seed, 1000 * epoch)
-        valid = lambda epoch: make(held, seed + 1)
-        test = lambda: make(held, seed + 2)
-    else:
-        rep = {"data_root": hparams["data_folder"]}
-        csv = {k: os.path.join(hparams["data_folder"], v) for k, v in hparams["manifests"].items()}
-        tr = data.CsvDataset(csv["train"], rep)
-        va = data.CsvDataset(csv["valid"], rep, "ascending")
-        te = data.CsvDataset(csv["test"], rep, "ascending")
-        train = lambda epoch: data.batches(tr, bs, bool(hparams.get("shuffle", True)), seed, epoch=epoch)
-        valid = lambda epoch: data.batches(va, bs)
-        test = lambda: data.batches(te, bs)
-
-    class Loader:
-        def __init__(self, f):
-            self.f = f
-
-        def __iter__(self):
-            return iter(self.f(max(1, int(counter.current))))
-
-    brain.fit(counter, Loader(train), Loader(valid))
-    brain.evaluate(test(), min_key="error")
+    train, valid, test = gender.loaders(hparams, synthetic, counter)
+    brain.fit(counter, train, valid)
+    brain.evaluate(test, min_key="error")
     print(json.dumps({"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
                       "best_checkpoint": getattr(brain, "best_checkpoint", None)}))
 

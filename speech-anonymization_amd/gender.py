@@ -25,7 +25,7 @@ import os
 
 import torch
 
-from . import features, losses, xvector
+from . import data, features, losses, xvector
 from .brain import Brain, EpochCounter, FileTrainLogger, Stage
 from .checkpoint import Checkpointer
 from .data import SEX
@@ -222,6 +222,39 @@ def augment_notice(script, settings):
     return (f"{script}: waveform augmentation on: speeds {list(c.speeds)}, frequency drop "
             f"{c.drop_freq_count_low}-{c.drop_freq_count_high} notches, chunk drop {c.drop_chunk_count_low}-"
             f"{c.drop_chunk_count_high} x {c.drop_chunk_length_low}-{c.drop_chunk_length_high} samples, {noise}")
+
+
+class _EpochLoader:
+    """an iterable that asks ``batches(epoch)`` anew on every pass, with the epoch the counter is in (1 before the
+    first)"""
+
+    def __init__(self, batches, counter):
+        self.batches, self.counter = batches, counter
+
+    def __iter__(self):
+        return iter(self.batches(max(1, int(self.counter.current))))
+
+
+def loaders(hparams, synthetic, counter):
+    """what the four gender recipes train on -> (train loader, valid loader, test iterable): ``synthetic`` utterances of
+    data.synthetic_gender_dataset (a fresh draw per training epoch, a quarter as many held out), or the manifests"""
+    bs, seed = int(hparams["batch_size"]), int(hparams["seed"])
+    if synthetic:
+        n = int(synthetic)
+        held = max(bs, n // 4)
+        make = lambda k, s, ep=0: data.synthetic_gender_dataset(k, bs, seed=s + ep)
+        train = lambda epoch: make(n, seed, 1000 * epoch)
+        valid = lambda epoch: make(held, seed + 1)
+        test = make(held, seed + 2)
+    else:
+        rep = {"data_root": hparams["data_folder"]}
+        csv = {k: os.path.join(hparams["data_folder"], v) for k, v in hparams["manifests"].items()}
+        tr = data.CsvDataset(csv["train"], rep)
+        va = data.CsvDataset(csv["valid"], rep, "ascending")
+        train = lambda epoch: data.batches(tr, bs, bool(hparams.get("shuffle", True)), seed, epoch=epoch)
+        valid = lambda epoch: data.batches(va, bs)
+        test = data.batches(data.CsvDataset(csv["test"], rep, "ascending"), bs)
+    return _EpochLoader(train, counter), _EpochLoader(valid, counter), test
 
 
 # ---------------------------------------------------------------------------------------------------

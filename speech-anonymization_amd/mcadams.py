@@ -5,7 +5,8 @@ formant moves by its own amount (phi = 1 rad, 2546 Hz, is the fixed point; below
 alpha < 1).  One library call, sa_mcadams, all on the GPU, no phase reconstruction and no device-to-host copy."""
 import torch
 
-from . import _lib as L
+from . import ops
+from .pitchnorm import gpu_only, n_valid
 
 ALPHA_LOW, ALPHA_HIGH = 0.5, 1.2             # what this layer accepts (the kernel itself takes 0.25..2)
 ALPHA_DEFAULT = 0.8
@@ -58,14 +59,12 @@ class McAdams:
 
     @torch.no_grad()
     def __call__(self, wavs, lens):
-        from . import ops
-        if not torch.is_tensor(wavs) or not wavs.is_cuda:
-            raise L.SaHipError("McAdams runs on the GPU only (no CPU fallback)")
+        gpu_only("McAdams", wavs)
         B, N = wavs.shape
         alpha = self.draw(B, wavs.device)
         self.calls += 1
-        n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N).to(torch.int32)
-        out, gain, status = ops.mcadams(wavs.contiguous(), alpha, n_valid, self.level, return_status=True)
+        out, gain, status = ops.mcadams(wavs.contiguous(), alpha, n_valid(lens, N, wavs.device).to(torch.int32),
+                                        self.level, return_status=True)
         counts = torch.stack([(status == k).sum(1) for k in range(3)], 1)
         self.last = (alpha, gain, counts)
         return out

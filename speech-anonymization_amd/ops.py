@@ -951,12 +951,14 @@ GL_MAX_B, GL_MAX_T = 65535, 1 << 23        # grid.y; 160 T + 400 stays an int
 _gl_in = functools.partial(_aug_in, family="vocoder")
 
 
-def _gl_spec(t, what, dtype):
-    if _gl_in(t, what, dtype).dim() != 3 or t.shape[2] != 201:
+def _gl_spec(t, what, dtype, family_in=_gl_in, t_min=2):
+    """(B, T) of t [B, T, 201] as the kernels of one family take it; t_min None: the caller checks the extents"""
+    if family_in(t, what, dtype).dim() != 3 or t.shape[2] != 201:
         raise L.SaHipError(f"{what}: expected [B, T, 201], got {tuple(t.shape)}")
     B, T, _ = t.shape
-    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T:
-        raise L.SaHipError(f"{what}: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 2..{GL_MAX_T}")
+    if t_min is not None and (B < 1 or B > GL_MAX_B or T < t_min or T > GL_MAX_T):
+        raise L.SaHipError(f"{what}: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in "
+                           f"{t_min}..{GL_MAX_T}")
     return B, T
 
 
@@ -1085,29 +1087,37 @@ def pitch_resample(y, ratio, n_valid, Nout):
 _pv_in = functools.partial(_aug_in, family="phase-vocoder")
 
 
+def _pv_dims(who, R, Tout):
+    B, T = _gl_spec(R, "R", torch.complex64, _pv_in, None)
+    Tout = int(Tout)
+    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T or Tout < 1 or Tout > GL_MAX_T:
+        raise L.SaHipError(f"{who}: [B, T] = [{B}, {T}], Tout = {Tout} -- B in 1..{GL_MAX_B} (a grid extent), T in "
+                           f"2..{GL_MAX_T}, Tout in 1..{GL_MAX_T}")
+    return B, T, Tout
+
+
+def _pv_launch(entry, R, mags, steer, B, T, Tout, return_phase):
+    """the output, the workspace and the call of sa_pv_synth and sa_pv_synth_map; steer: what places the frames"""
+    lib = L.load()
+    Cx = torch.empty(B, Tout, 201, dtype=torch.complex64, device=R.device)
+    phase = torch.empty(B, Tout, 201, dtype=torch.float64, device=R.device) if return_phase else None
+    ws = torch.empty(lib.sa_pv_workspace_bytes(B, Tout) // 8, dtype=torch.float64, device=R.device)
+    L.check(getattr(lib, entry)(_f(R), _f(mags), *(_f(t) for t in steer), B, T, Tout, _f(Cx), _f(phase), _f(ws),
+                                L.stream()), entry)
+    return (Cx, phase) if return_phase else Cx
+
+
 def pv_synth(R, ratio, Tout, S=None, return_phase=False):
     """R complex64 [B, T, 201] (vocoder.stft of the padded waveform), ratio fp32 [B] -> C complex64 [B, Tout, 201]: the
     stretch of pitch_stretch_mag with R's own phases carried through it -- frame t' < ceil((T - 1) r_b) + 1 has the
     phase theta[0] + sum_{s < t'} (theta[i_s + 1] - theta[i_s]) and the magnitude S[b, t'] (fp32 [B, Tout, 201], e.g.
     env_warp's output) or, without S, what pitch_stretch_mag gives bit for bit; zero from there on (sa_pv_synth).
     return_phase: also the phases in turns, fp64 [B, Tout, 201] (tests).  Everything stays on the device."""
-    if _pv_in(R, "R", torch.complex64).dim() != 3 or R.shape[2] != 201:
-        raise L.SaHipError(f"R: expected [B, T, 201], got {tuple(R.shape)}")
-    B, T, _ = R.shape
-    Tout = int(Tout)
-    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T or Tout < 1 or Tout > GL_MAX_T:
-        raise L.SaHipError(f"pv_synth: [B, T] = [{B}, {T}], Tout = {Tout} -- B in 1..{GL_MAX_B} (a grid extent), T in "
-                           f"2..{GL_MAX_T}, Tout in 1..{GL_MAX_T}")
+    B, T, Tout = _pv_dims("pv_synth", R, Tout)
     _pv_in(ratio, "ratio", shape=(B,))
     if S is not None:
         _pv_in(S, "S", shape=(B, Tout, 201))
-    lib = L.load()
-    Cx = torch.empty(B, Tout, 201, dtype=torch.complex64, device=R.device)
-    phase = torch.empty(B, Tout, 201, dtype=torch.float64, device=R.device) if return_phase else None
-    ws = torch.empty(lib.sa_pv_workspace_bytes(B, Tout) // 8, dtype=torch.float64, device=R.device)
-    L.check(lib.sa_pv_synth(_f(R), _f(S), _f(ratio), B, T, Tout, _f(Cx), _f(phase), _f(ws), L.stream()),
-            "sa_pv_synth")
-    return (Cx, phase) if return_phase else Cx
+    return _pv_launch("sa_pv_synth", R, S, (ratio,), B, T, Tout, return_phase)
 
 
 # ---- spectral envelope and formant warp (csrc/sa_envelope.hip; pitchnorm.py) ----
@@ -1117,53 +1127,35 @@ LN10_OVER_20 = 0.11512925464970229       # dB -> natural log of an amplitude rat
 _env_in = functools.partial(_aug_in, family="envelope")
 
 
+def _env_warp(who, S, q, per_frame, n_c, floor_rel, max_gain_db, return_env):
+    B, T = _gl_spec(S, "S", torch.float32, _env_in, 1)
+    _env_in(q, "q", shape=(B, T) if per_frame else (B,))
+    n_c = int(n_c)
+    if not 1 <= n_c <= ENV_NC_MAX:
+        raise L.SaHipError(f"{who}: n_c = {n_c} in 1..{ENV_NC_MAX} expected")
+    if not 0.0 < float(floor_rel) < 1.0:
+        raise L.SaHipError(f"{who}: floor_rel = {floor_rel} in (0, 1) expected")
+    if not float(max_gain_db) > 0.0:
+        raise L.SaHipError(f"{who}: max_gain_db = {max_gain_db} > 0 expected")
+    out = torch.empty_like(S)
+    env = torch.empty_like(S) if return_env else None
+    L.check(getattr(L.load(), "sa_" + who)(_f(S), _f(q), B, T, n_c, C.c_float(float(floor_rel)),
+                                           C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
+            "sa_" + who)
+    return (out, env) if return_env else out
+
+
 def env_warp(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
     """magnitudes S fp32 [B, T, 201], warp factors q fp32 [B] -> out [B, T, 201] = S exp(g), g = clamp(E(min(pi, q w_k))
     - E(w_k), +-max_gain_db ln 10 / 20), E the cepstral envelope of ln max(S, floor_rel max S, 1e-10) liftered to
     n_c coefficients (sa_env_warp).  return_env: also E(w_k) [B, T, 201] (tests)."""
-    if _env_in(S, "S").dim() != 3 or S.shape[2] != 201:
-        raise L.SaHipError(f"S: expected [B, T, 201], got {tuple(S.shape)}")
-    B, T, _ = S.shape
-    if B < 1 or B > GL_MAX_B or T < 1 or T > GL_MAX_T:
-        raise L.SaHipError(f"S: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 1..{GL_MAX_T}")
-    _env_in(q, "q", shape=(B,))
-    n_c = int(n_c)
-    if not 1 <= n_c <= ENV_NC_MAX:
-        raise L.SaHipError(f"env_warp: n_c = {n_c} in 1..{ENV_NC_MAX} expected")
-    if not 0.0 < float(floor_rel) < 1.0:
-        raise L.SaHipError(f"env_warp: floor_rel = {floor_rel} in (0, 1) expected")
-    if not float(max_gain_db) > 0.0:
-        raise L.SaHipError(f"env_warp: max_gain_db = {max_gain_db} > 0 expected")
-    out = torch.empty_like(S)
-    env = torch.empty_like(S) if return_env else None
-    L.check(L.load().sa_env_warp(_f(S), _f(q), B, T, n_c, C.c_float(float(floor_rel)),
-                                 C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
-            "sa_env_warp")
-    return (out, env) if return_env else out
+    return _env_warp("env_warp", S, q, False, n_c, floor_rel, max_gain_db, return_env)
 
 
 def env_warp_frames(S, q, n_c=30, floor_rel=1e-4, max_gain_db=40.0, return_env=False):
     """env_warp with warp factors q fp32 [B, T], one per frame (sa_env_warp_frames): for q constant
     along t, env_warp's bits"""
-    if _env_in(S, "S").dim() != 3 or S.shape[2] != 201:
-        raise L.SaHipError(f"S: expected [B, T, 201], got {tuple(S.shape)}")
-    B, T, _ = S.shape
-    if B < 1 or B > GL_MAX_B or T < 1 or T > GL_MAX_T:
-        raise L.SaHipError(f"S: [B, T] = [{B}, {T}] -- B in 1..{GL_MAX_B} (a grid extent), T in 1..{GL_MAX_T}")
-    _env_in(q, "q", shape=(B, T))
-    n_c = int(n_c)
-    if not 1 <= n_c <= ENV_NC_MAX:
-        raise L.SaHipError(f"env_warp_frames: n_c = {n_c} in 1..{ENV_NC_MAX} expected")
-    if not 0.0 < float(floor_rel) < 1.0:
-        raise L.SaHipError(f"env_warp_frames: floor_rel = {floor_rel} in (0, 1) expected")
-    if not float(max_gain_db) > 0.0:
-        raise L.SaHipError(f"env_warp_frames: max_gain_db = {max_gain_db} > 0 expected")
-    out = torch.empty_like(S)
-    env = torch.empty_like(S) if return_env else None
-    L.check(L.load().sa_env_warp_frames(_f(S), _f(q), B, T, n_c, C.c_float(float(floor_rel)),
-                                        C.c_float(float(max_gain_db) * LN10_OVER_20), _f(out), _f(env), L.stream()),
-            "sa_env_warp_frames")
-    return (out, env) if return_env else out
+    return _env_warp("env_warp_frames", S, q, True, n_c, floor_rel, max_gain_db, return_env)
 
 
 # ---- F0-contour pitch modification (csrc/sa_contour.hip; pitchnorm.py; DESIGN section 20) ----
@@ -1209,23 +1201,11 @@ def pv_synth_map(R, rho_q, Q, Tout, M=None, return_phase=False):
     """pv_synth with the stretch positions of a time map (pitch_contour's rho_q and Q, [B, T]) in place of a ratio's;
     M fp32 [B, T, 201]: magnitudes ON THE INPUT GRID (e.g. env_warp_frames' output), mixed as the stretch mixes |R|;
     without M, |R| (sa_pv_synth_map).  Everything stays on the device."""
-    if _pv_in(R, "R", torch.complex64).dim() != 3 or R.shape[2] != 201:
-        raise L.SaHipError(f"R: expected [B, T, 201], got {tuple(R.shape)}")
-    B, T, _ = R.shape
-    Tout = int(Tout)
-    if B < 1 or B > GL_MAX_B or T < 2 or T > GL_MAX_T or Tout < 1 or Tout > GL_MAX_T:
-        raise L.SaHipError(f"pv_synth_map: [B, T] = [{B}, {T}], Tout = {Tout} -- B in 1..{GL_MAX_B} (a grid extent), T "
-                           f"in 2..{GL_MAX_T}, Tout in 1..{GL_MAX_T}")
+    B, T, Tout = _pv_dims("pv_synth_map", R, Tout)
     _ct_tables(rho_q, Q, B, T)
     if M is not None:
         _pv_in(M, "M", shape=(B, T, 201))
-    lib = L.load()
-    Cx = torch.empty(B, Tout, 201, dtype=torch.complex64, device=R.device)
-    phase = torch.empty(B, Tout, 201, dtype=torch.float64, device=R.device) if return_phase else None
-    ws = torch.empty(lib.sa_pv_workspace_bytes(B, Tout) // 8, dtype=torch.float64, device=R.device)
-    L.check(lib.sa_pv_synth_map(_f(R), _f(M), _f(rho_q), _f(Q), B, T, Tout, _f(Cx), _f(phase), _f(ws), L.stream()),
-            "sa_pv_synth_map")
-    return (Cx, phase) if return_phase else Cx
+    return _pv_launch("sa_pv_synth_map", R, M, (rho_q, Q), B, T, Tout, return_phase)
 
 
 def pitch_resample_map(y, rho_q, Q, n_valid, Nout):

@@ -27,12 +27,13 @@ baseline, 0 a monotone voice: sa_pitch_contour -> [sa_env_warp_frames] -> sa_pv_
 
 The track: with ``f0_method="viterbi"`` the F0 of every path above is a Viterbi decode through each
 frame's d' dips (sa_f0_candidates -> sa_f0_viterbi on sa_yin_f0's d') instead of the first dip under the threshold."""
+import collections
 import math
 
 import torch
 
 from . import _lib as L
-from . import vocoder
+from . import ops, vocoder
 from .features import HOP
 
 SAMPLE_RATE, W, TAU_MIN, TAU_MAX = 16000, 400, 40, 266
@@ -47,14 +48,60 @@ F0_METHODS = ("yin", "viterbi")              # first dip under the threshold; a 
 F0_COSTS = ("voicing_cost", "switch_cost", "jump_cost", "lag_bias")
 F0_COST_LOW, F0_COST_HIGH = 0.0, 4.0         # what sa_f0_viterbi takes
 
+# one definition per option: its flag, its kind ("real", "count", "choice" or "bool"), its bounds (the constants above,
+# which the classes' *_settings check against too) or choices, and what the command line says of a value outside
+# them; fmt: how the refused value is shown
+Option = collections.namedtuple("Option", "flag kind low high text fmt", defaults=("{}",))
+OPTIONS = {
+    "formant_ratio": Option("--formant_ratio", "real", BETA_LOW, BETA_HIGH, f"a factor between {BETA_LOW:g} and "
+                            f"{BETA_HIGH:g} by which the formants are scaled"),
+    "preserve_formants": Option("--preserve_formants", "bool", None, None, "true or false"),
+    "lifter": Option("--lifter", "count", 1, LIFTER_MAX, f"a count of cepstral coefficients, 1 to {LIFTER_MAX}"),
+    "phase": Option("--phase", "choice", PHASES, None, "griffin_lim (phases reconstructed by Griffin-Lim, the default) "
+                    "or vocoder (the input's own phases carried through the stretch)"),
+    "contour_scale": Option("--contour_scale", "real", CONTOUR_LOW, CONTOUR_HIGH, f"a factor between {CONTOUR_LOW:g} "
+                            f"(a monotone voice) and {CONTOUR_HIGH:g} by which the F0 contour's excursions are scaled"),
+    "contour_smooth": Option("--contour_smooth", "count", 0, SMOOTH_MAX, f"a half-width in frames, 0 to {SMOOTH_MAX}"),
+    "f0_method": Option("--f0_method", "choice", F0_METHODS, None, "yin (the first dip of d' under the threshold, the "
+                        "default) or viterbi (a path decoded through every frame's dips)"),
+    "target_hz": Option("--pitch_target_hz", "real", TARGET_LOW, TARGET_HIGH, f"a target between {TARGET_LOW:g} and "
+                        f"{TARGET_HIGH:g} Hz, the range the F0 tracker covers", "{:g}"),
+}
 
-def f0_track(wav, threshold=0.15, method="yin", lens=None, **costs):
+
+def gpu_only(who, t):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.SaHipError(f"{who} runs on the GPU only (no CPU fallback)")
+
+
+def n_valid(lens, N, device):
+    """round(lens N) in 0..N per row, fp64 on the device: the samples that count (the kernels take them as int32)"""
+    return torch.round(lens.to(device).double() * N).clamp(0, N)
+
+
+def padded_stft(wavs):
+    """wavs [B, N] -> (wp, R): wavs zero-padded to the next multiple of the hop, contiguous, and vocoder.stft of it"""
+    N = wavs.shape[1]
+    Np = HOP * -(-N // HOP)
+    wp = (torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs).contiguous()
+    return wp, vocoder.stft(wp)
+
+
+def resynthesis(gl, R, ratio, Tout, S):
+    """the waveform of magnitudes S [B, Tout, 201]: Griffin-Lim (``gl``) from random phases, or without one R's own
+    phases carried through the stretch at ``ratio`` (pv_synth; S None: the plain stretch of |R|) and one inversion"""
+    if gl is not None:
+        return gl(S)
+    w, tw, _ = vocoder.tables(R.device)
+    return ops.gl_istft(ops.pv_synth(R, ratio, Tout, S), w, tw)
+
+
+def f0_track(wav, threshold=0.15, method="yin", lens=None, N=None, **costs):
     """wav [B, N] (device, fp32) -> f0 [B, N // 160 + 1] in Hz, one value per Fbank frame, 0 where unvoiced.
     ``method="viterbi"`` decodes a path through every frame's d' dips instead of taking the first
     one under the threshold: sa_yin_f0's d' -> sa_f0_candidates -> sa_f0_viterbi.  ``lens`` [B] (relative lengths;
-    None: every frame counts) cuts the decode at the frames of round(lens N) samples, 0 beyond them; ``costs``:
-    voicing_cost, switch_cost, jump_cost, lag_bias of ops.f0_viterbi."""
-    from . import ops
+    None: every frame counts) cuts the decode at the frames of round(lens N) samples, 0 beyond them (N: the unpadded
+    width when wav is padded); ``costs``: voicing_cost, switch_cost, jump_cost, lag_bias of ops.f0_viterbi."""
     method, costs = f0_settings("f0_track", method, costs)
     if method == "yin":
         return ops.yin_f0(wav, threshold)
@@ -62,7 +109,8 @@ def f0_track(wav, threshold=0.15, method="yin", lens=None, **costs):
     if lens is None:
         lens = torch.ones(wav.shape[0], dtype=torch.float32, device=wav.device)
     tau, q = ops.f0_candidates(dprime)
-    return ops.f0_viterbi(dprime, tau, q, lens.to(wav.device, torch.float32).contiguous(), wav.shape[1], **costs)
+    return ops.f0_viterbi(dprime, tau, q, lens.to(wav.device, torch.float32).contiguous(),
+                          wav.shape[1] if N is None else N, **costs)
 
 
 def f0_settings(who, method, costs):
@@ -156,9 +204,7 @@ class PitchNormalizer:
 
     @torch.no_grad()
     def __call__(self, wavs, lens):
-        from . import ops
-        if not torch.is_tensor(wavs) or not wavs.is_cuda:
-            raise L.SaHipError("PitchNormalizer runs on the GPU only (no CPU fallback)")
+        gpu_only("PitchNormalizer", wavs)
         lens = lens.to(wavs.device, torch.float32).contiguous()
         if self.contour_scale is not None:
             return self.shift_contour(wavs, lens)
@@ -167,30 +213,22 @@ class PitchNormalizer:
         return self.shift(wavs, lens, self.last[0])
 
     def track(self, wavs, lens, N=None):
-        """the F0 track the ratios are formed from: sa_yin_f0, or with f0_method="viterbi" the decode over the frames
-        of round(lens N) samples (N: the unpadded width when wavs is padded)"""
-        from . import ops
-        if self.f0_method == "yin":
-            return ops.yin_f0(wavs, self.threshold)
-        _, dprime = ops.yin_f0(wavs, self.threshold, return_dprime=True)
-        tau, q = ops.f0_candidates(dprime)
-        return ops.f0_viterbi(dprime, tau, q, lens, wavs.shape[1] if N is None else N, **self.f0_costs)
+        """the F0 track the ratios are formed from: f0_track with the object's method, threshold and costs (N: the
+        unpadded width when wavs is padded)"""
+        return f0_track(wavs, self.threshold, self.f0_method, lens, N, **self.f0_costs)
 
     @torch.no_grad()
     def shift_contour(self, wavs, lens):
-        """the contour path: pad -> yin_f0 of the padded waveform -> pitch_contour -> STFT [->
-        |R| -> env_warp_frames at q[b, t] = rho[b, t] / beta] -> pv_synth_map -> one gl_istft -> pitch_resample_map.
+        """the contour path: pad -> STFT, yin_f0 of the padded waveform -> pitch_contour [-> |R| ->
+        env_warp_frames at q[b, t] = rho[b, t] / beta] -> pv_synth_map -> one gl_istft -> pitch_resample_map.
         ``last`` is (the row's mean ratio Q[T - 1] / ((T - 1) 2^17), mean f0, voiced frames)."""
-        from . import ops
         B, N = wavs.shape
-        Np = HOP * -(-N // HOP)
-        wp = (torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs).contiguous()
+        wp, R = padded_stft(wavs)
         f0 = self.track(wp, lens, N)
         rho_q, Q, Tq, mean, voiced = ops.pitch_contour(f0, lens, N, self.target_hz, self.contour_scale,
                                                        self.contour_smooth, self.r_min, self.r_max, self.min_voiced)
         T = f0.shape[1]
         self.last = ((Q[:, T - 1].double() / float((T - 1) * ops.CT_Q_ONE)).float(), mean, voiced)
-        R = vocoder.stft(wp)
         M = None
         if self.formant_ratio is not None:                   # on the input grid: the frame's own ratio is known there
             one = torch.ones(B, dtype=torch.float32, device=wavs.device)
@@ -200,22 +238,17 @@ class PitchNormalizer:
         Tout = int(Tq.max())                                 # the path's one synchronisation: T' is a shape
         w, tw, _ = vocoder.tables(wavs.device)
         y = ops.gl_istft(ops.pv_synth_map(R, rho_q, Q, Tout, M), w, tw)
-        n_valid = torch.round(lens.double() * N).clamp(0, N).to(torch.int32)
-        return ops.pitch_resample_map(y, rho_q, Q, n_valid, N)
+        return ops.pitch_resample_map(y, rho_q, Q, n_valid(lens, N, wavs.device).to(torch.int32), N)
 
     @torch.no_grad()
     def shift(self, wavs, lens, ratio):
         """the stretch, the phase reconstruction and the resampling with a given ratio (fp32 [B], device)"""
-        from . import ops
-        if not torch.is_tensor(wavs) or not wavs.is_cuda:
-            raise L.SaHipError("PitchNormalizer runs on the GPU only (no CPU fallback)")
-        B, N = wavs.shape
+        gpu_only("PitchNormalizer", wavs)
+        N = wavs.shape[1]
         host = ratio.detach().cpu().tolist()                 # the path's one synchronisation: T' is a shape
         if not all(R_LOW <= r <= R_HIGH for r in host):
             raise L.SaHipError(f"PitchNormalizer.shift: ratios in [{R_LOW}, {R_HIGH}] expected, got {host}")
-        Np = HOP * -(-N // HOP)
-        wp = torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs
-        R = vocoder.stft(wp.contiguous())
+        _, R = padded_stft(wavs)
         Tout = max(stretched_frames(R.shape[1], r) for r in host)
         S = None                                             # (the vocoder path forms the plain stretch itself)
         if self.gl is not None or self.formant_ratio is not None:
@@ -223,13 +256,8 @@ class PitchNormalizer:
         if self.formant_ratio is not None:                   # q_b = r_b / beta, formed on the device
             q = (ratio.float() / self.formant_ratio).contiguous()
             S = ops.env_warp(S, q, self.lifter, self.floor_rel, self.max_gain_db)
-        if self.gl is not None:
-            y = self.gl(S)
-        else:
-            w, tw, _ = vocoder.tables(wavs.device)
-            y = ops.gl_istft(ops.pv_synth(R, ratio, Tout, S), w, tw)
-        n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N).to(torch.int32)
-        return ops.pitch_resample(y, ratio, n_valid, N)
+        y = resynthesis(self.gl, R, ratio, Tout, S)
+        return ops.pitch_resample(y, ratio, n_valid(lens, N, wavs.device).to(torch.int32), N)
 
 
 class FormantShifter:
@@ -250,120 +278,90 @@ class FormantShifter:
 
     @torch.no_grad()
     def __call__(self, wavs, lens):
-        from . import ops
-        if not torch.is_tensor(wavs) or not wavs.is_cuda:
-            raise L.SaHipError("FormantShifter runs on the GPU only (no CPU fallback)")
+        gpu_only("FormantShifter", wavs)
         B, N = wavs.shape
-        Np = HOP * -(-N // HOP)
-        wp = torch.nn.functional.pad(wavs, (0, Np - N)) if Np != N else wavs
-        R = vocoder.stft(wp.contiguous())
+        _, R = padded_stft(wavs)
         one = torch.ones(B, dtype=torch.float32, device=wavs.device)
         S = ops.pitch_stretch_mag(R, one, R.shape[1])        # |R| exactly: the stretch at ratio 1
         S = ops.env_warp(S, one / self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db)
-        if self.gl is not None:
-            y = self.gl(S)[:, :N]
-        else:
-            w, tw, _ = vocoder.tables(wavs.device)
-            y = ops.gl_istft(ops.pv_synth(R, one, R.shape[1], S), w, tw)[:, :N]
-        n_valid = torch.round(lens.to(wavs.device).double() * N).clamp(0, N)
-        live = torch.arange(N, device=wavs.device)[None, :] < n_valid[:, None]
+        y = resynthesis(self.gl, R, one, R.shape[1], S)[:, :N]
+        # (the fp64 counts and a torch.where, on purpose: the other paths hand int32 counts to their resampling kernel)
+        live = torch.arange(N, device=wavs.device)[None, :] < n_valid(lens, N, wavs.device)[:, None]
         return torch.where(live, y, torch.zeros((), dtype=y.dtype, device=y.device)).contiguous()
+
+
+def given_options(keys, settings, block=None):
+    """the options ``keys`` as the top-level settings give them, else the recipe's block (if any) -> a dict, in the
+    order of ``keys``, of those that were given"""
+    block = block or {}
+    return {k: v for k in keys for v in (settings.get(k, block.get(k)),) if v is not None}
+
+
+def check_option(key, value):
+    """``value`` of the option ``key`` -> as the classes take it (a float where it is real), or the option's one line"""
+    o = OPTIONS[key]
+    if o.kind == "bool":
+        ok = isinstance(value, bool)
+    elif o.kind == "choice":
+        ok = isinstance(value, str) and value in o.low
+    elif o.kind == "count":
+        ok = not isinstance(value, bool) and isinstance(value, int) and o.low <= value <= o.high
+    else:
+        try:
+            real = float(value)
+        except (TypeError, ValueError):
+            real = float("nan")
+        # (--formant_ratio true has always read as 1; --contour_scale true is refused)
+        ok = o.low <= real <= o.high and not (isinstance(value, bool) and key != "formant_ratio")
+    if not ok:
+        raise SystemExit(f"{o.flag} {o.fmt.format(value)}: {o.text}")
+    return value if o.kind != "real" else real
 
 
 def check_formant_options(settings, block=None):
     """the envelope settings of a recipe's ``pitch_norm:`` block (if any) under the top-level overrides ->
     a dict of the keys that were given (preserve_formants, formant_ratio, lifter), each refused in one line"""
-    block = block or {}
-    given = {}
-    for key in ("preserve_formants", "formant_ratio", "lifter"):
-        value = settings.get(key, block.get(key))
-        if value is not None:
-            given[key] = value
-    if "preserve_formants" in given:
-        if not isinstance(given["preserve_formants"], bool):
-            raise SystemExit(f"--preserve_formants {given['preserve_formants']}: true or false")
-    if "formant_ratio" in given:
-        try:
-            beta = float(given["formant_ratio"])
-        except (TypeError, ValueError):
-            beta = float("nan")
-        if not BETA_LOW <= beta <= BETA_HIGH:
-            raise SystemExit(f"--formant_ratio {given['formant_ratio']}: a factor between {BETA_LOW:g} and "
-                             f"{BETA_HIGH:g} by which the formants are scaled")
-        given["formant_ratio"] = beta
-        if given.get("preserve_formants"):
-            raise SystemExit("--preserve_formants true and --formant_ratio exclude each other: preserving the "
-                             "formants is formant_ratio 1")
+    given = given_options(("preserve_formants", "formant_ratio", "lifter"), settings, block)
+    for key in ("preserve_formants", "formant_ratio"):
+        if key in given:
+            given[key] = check_option(key, given[key])
+    if "formant_ratio" in given and given.get("preserve_formants"):
+        raise SystemExit("--preserve_formants true and --formant_ratio exclude each other: preserving the "
+                         "formants is formant_ratio 1")
     if "lifter" in given:
-        n = given["lifter"]
-        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= LIFTER_MAX:
-            raise SystemExit(f"--lifter {n}: a count of cepstral coefficients, 1 to {LIFTER_MAX}")
+        check_option("lifter", given["lifter"])
     return given
 
 
 def check_phase_option(settings, block=None):
     """the ``phase`` of a recipe's ``pitch_norm:`` block (if any) under the top-level override -> a dict that carries
     the key only when it was given; anything but griffin_lim and vocoder is refused in one line"""
-    value = settings.get("phase", (block or {}).get("phase"))
-    if value is None:
-        return {}
-    if value not in PHASES:
-        raise SystemExit(f"--phase {value}: griffin_lim (phases reconstructed by Griffin-Lim, the default) or vocoder "
-                         "(the input's own phases carried through the stretch)")
-    return {"phase": value}
+    return {k: check_option(k, v) for k, v in given_options(("phase",), settings, block).items()}
 
 
 def check_f0_option(settings, block=None):
     """the ``f0_method`` of a recipe's ``pitch_norm:`` block (if any) under the top-level override -> a dict that
     carries the key only when it was given; anything but yin and viterbi is refused in one line"""
-    value = settings.get("f0_method", (block or {}).get("f0_method"))
-    if value is None:
-        return {}
-    if not isinstance(value, str) or value not in F0_METHODS:
-        raise SystemExit(f"--f0_method {value}: yin (the first dip of d' under the threshold, the default) or viterbi "
-                         "(a path decoded through every frame's dips)")
-    return {"f0_method": value}
+    return {k: check_option(k, v) for k, v in given_options(("f0_method",), settings, block).items()}
 
 
 def check_contour_options(settings, block=None):
     """``contour_scale`` and ``contour_smooth`` of a recipe's ``pitch_norm:`` block (if any) under the top-level
     overrides -> a dict that carries a key only when it was given; each is refused in one line when out of range or
     given without ``phase: vocoder``"""
-    block = block or {}
-    given = {}
-    for key in ("contour_scale", "contour_smooth"):
-        value = settings.get(key, block.get(key))
-        if value is not None:
-            given[key] = value
-    if not given:
-        return given
-    if settings.get("phase", block.get("phase")) != "vocoder":
+    given = given_options(("contour_scale", "contour_smooth"), settings, block)
+    if given and given_options(("phase",), settings, block).get("phase") != "vocoder":
         raise SystemExit(f"--{next(iter(given))} needs --phase vocoder: the contour is moved on the phase-vocoder path "
                          "only")
-    if "contour_scale" in given:
-        try:
-            gamma = float(given["contour_scale"])
-        except (TypeError, ValueError):
-            gamma = float("nan")
-        if isinstance(given["contour_scale"], bool) or not CONTOUR_LOW <= gamma <= CONTOUR_HIGH:
-            raise SystemExit(f"--contour_scale {given['contour_scale']}: a factor between {CONTOUR_LOW:g} (a monotone "
-                             f"voice) and {CONTOUR_HIGH:g} by which the F0 contour's excursions are scaled")
-        given["contour_scale"] = gamma
-    if "contour_smooth" in given:
-        s = given["contour_smooth"]
-        if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s <= SMOOTH_MAX:
-            raise SystemExit(f"--contour_smooth {s}: a half-width in frames, 0 to {SMOOTH_MAX}")
-        if "contour_scale" not in given:
-            raise SystemExit("--contour_smooth needs --contour_scale: there is no contour to smooth without it")
+    for key in given:
+        given[key] = check_option(key, given[key])
+    if "contour_smooth" in given and "contour_scale" not in given:
+        raise SystemExit("--contour_smooth needs --contour_scale: there is no contour to smooth without it")
     return given
 
 
 def check_pitch_target(value):
-    target = float(value)
-    if not TARGET_LOW <= target <= TARGET_HIGH:
-        raise SystemExit(f"--pitch_target_hz {target:g}: a target between {TARGET_LOW:g} and {TARGET_HIGH:g} Hz, "
-                         "the range the F0 tracker covers")
-    return target
+    return check_option("target_hz", float(value))
 
 
 def check_pitch_options(settings, run_opts, environ=None):

@@ -154,71 +154,75 @@ def invert_features(feats, normalizer, lens=None, frames=None, return_magnitude=
 
 
 ANON_MODEL_TYPES = ("convae", "fcae", "endtoend")
+# the two modes that re-synthesise the waveform they are given: their flag and what they write
+RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
+                 "formant_shift": ("--formant_ratio", "formant-shifted")}
+
+
+def anonymize_mode(settings):
+    """what anonymize.py runs: mcadams, pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough
+    or model"""
+    if any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")):
+        return "mcadams"
+    if settings.get("pitch_norm"):
+        return "pitch_norm"
+    if settings.get("formant_ratio") is not None:
+        return "formant_shift"
+    return "passthrough" if settings.get("passthrough") else "model"
 
 
 def check_anonymize_options(settings, run_opts, environ=None):
     """what anonymize.py refuses before anything touches a GPU, one line each"""
     import os
+    from . import mcadams, pitchnorm                        # (both import this module)
     environ = os.environ if environ is None else environ
-    mt = settings.get("model_type")
-    from .pitchnorm import check_formant_options, check_phase_option
-    formant = check_formant_options(settings)
-    phase = check_phase_option(settings)
-    shift_only = "formant_ratio" in formant and not settings.get("pitch_norm")
-    mcadams = any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max"))
-    if mcadams:                                             # (DESIGN section 17: no model, no checkpoint)
-        from .mcadams import check_mcadams_options
-        check_mcadams_options(settings)
-        for flag, given in (("--pitch_norm true", settings.get("pitch_norm")),
-                            ("--formant_ratio", "formant_ratio" in formant),
-                            ("--preserve_formants true", formant.get("preserve_formants")),
-                            ("--recon_ckpt", settings.get("recon_ckpt")),
-                            ("--passthrough true", settings.get("passthrough"))):
-            if given:
-                raise SystemExit(f"--mcadams and {flag} exclude each other: the McAdams transform runs no model, "
-                                 "no pitch change and no envelope warp")
-        shift_only = False
+    formant = pitchnorm.check_formant_options(settings)
+    phase = pitchnorm.check_phase_option(settings)
+    mode = anonymize_mode(settings)
+    given = {"--mcadams": mode == "mcadams", "--pitch_norm true": settings.get("pitch_norm"),
+             "--formant_ratio": "formant_ratio" in formant,
+             "--preserve_formants true": formant.get("preserve_formants"),
+             "--recon_ckpt": settings.get("recon_ckpt"), "--passthrough true": settings.get("passthrough")}
+
+    def exclude(text, *flags):
+        for flag in flags:
+            if given[flag]:
+                raise SystemExit(text.format(flag))
+
+    if mode == "mcadams":                                   # (DESIGN section 17: no model, no checkpoint)
+        mcadams.check_mcadams_options(settings)
+        exclude("--mcadams and {} exclude each other: the McAdams transform runs no model, no pitch change and no "
+                "envelope warp", "--pitch_norm true", "--formant_ratio", "--preserve_formants true", "--recon_ckpt",
+                "--passthrough true")
     if phase.get("phase") == "vocoder":                     # (DESIGN section 19: a real waveform's phases only)
-        for flag, given in (("--mcadams", mcadams), ("--passthrough true", settings.get("passthrough")),
-                            ("--recon_ckpt", settings.get("recon_ckpt"))):
-            if given:
-                raise SystemExit(f"--phase vocoder and {flag} exclude each other: there is no input phase to carry")
-        if not settings.get("pitch_norm") and not shift_only:
+        exclude("--phase vocoder and {} exclude each other: there is no input phase to carry", "--mcadams",
+                "--passthrough true", "--recon_ckpt")
+        if mode not in RESYNTH_MODES:
             raise SystemExit("--phase vocoder goes with --pitch_norm true or --formant_ratio: the paths that "
                              "re-synthesise a waveform they were given")
-    from .pitchnorm import check_contour_options
-    if check_contour_options(settings) and not settings.get("pitch_norm"):    # (DESIGN section 20)
+    if pitchnorm.check_contour_options(settings) and mode != "pitch_norm":    # (DESIGN section 20)
         raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
                          "pitch")
-    from .pitchnorm import check_f0_option
-    if check_f0_option(settings) and not settings.get("pitch_norm") and not settings.get("report_f0"):
+    if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0"):
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
-    if mt not in ANON_MODEL_TYPES and not settings.get("pitch_norm") and not shift_only and not mcadams:
-        raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
-    if formant.get("preserve_formants") and not settings.get("pitch_norm"):
+    if mode in ("passthrough", "model") and settings.get("model_type") not in ANON_MODEL_TYPES:
+        raise SystemExit(f"unknown model_type {settings.get('model_type')!r}: the anonymiser is one of convae, fcae "
+                         "and endtoend")
+    if formant.get("preserve_formants") and mode != "pitch_norm":
         raise SystemExit("--preserve_formants true goes with --pitch_norm true: it keeps the formants where the "
                          "pitch normalisation would move them")
-    if "lifter" in formant and not settings.get("pitch_norm") and not shift_only:
+    if "lifter" in formant and mode not in RESYNTH_MODES:
         raise SystemExit("--lifter goes with --formant_ratio or --pitch_norm true --preserve_formants true")
-    if mcadams:
-        pass
-    elif shift_only:
+    if mode in RESYNTH_MODES:
+        flag, written = RESYNTH_MODES[mode]
         if settings.get("passthrough"):
-            raise SystemExit("--formant_ratio and --passthrough true exclude each other: one writes the "
-                             "formant-shifted waveforms, the other the vocoded originals")
+            raise SystemExit(f"{flag} and --passthrough true exclude each other: one writes the {written} waveforms, "
+                             "the other the vocoded originals")
         if settings.get("recon_ckpt"):
-            raise SystemExit("--formant_ratio takes no --recon_ckpt: no anonymiser runs, the waveforms are "
-                             "formant-shifted")
-    elif settings.get("pitch_norm"):
-        if settings.get("passthrough"):
-            raise SystemExit("--pitch_norm true and --passthrough true exclude each other: one writes the "
-                             "pitch-normalised waveforms, the other the vocoded originals")
-        if settings.get("recon_ckpt"):
-            raise SystemExit("--pitch_norm true takes no --recon_ckpt: no anonymiser runs, the waveforms are "
-                             "pitch-normalised")
-        from .pitchnorm import check_pitch_target
-        check_pitch_target(settings.get("pitch_target_hz", 170.0))
-    elif not settings.get("passthrough") and not settings.get("recon_ckpt"):
+            raise SystemExit(f"{flag} takes no --recon_ckpt: no anonymiser runs, the waveforms are {written}")
+    if mode == "pitch_norm":
+        pitchnorm.check_pitch_target(settings.get("pitch_target_hz", 170.0))
+    if mode == "model" and not settings.get("recon_ckpt"):
         raise SystemExit("--recon_ckpt DIR is required without --passthrough true: a CKPT+* directory of "
                          "speechbrain_convae_train.py (model.ckpt, normalizer.ckpt)")
     if not settings.get("out_dir"):

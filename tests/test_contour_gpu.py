@@ -7,14 +7,12 @@ to the contour kernel are ones whose decisions tests/test_contour_cpu.py shows t
 the GPU's own R and magnitudes and keeps section 19's bars ((Tout + 8) 2^-50 turns for phi', 4 u S' for C), the warp
 keeps section 16's, the resampling section 15's ((taps + 4) u mass).  u = 2^-24."""
 import ctypes
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import contour_ref as Cr
 from tests import formant_ref as F
 from tests import phasevoc_ref as V
@@ -577,12 +575,8 @@ def test_preserve_formants_with_a_flat_contour():
 
 def _anonymize_child(tmp_path, name, extra):
     out = tmp_path / name
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "anonymize.py"),
-                        os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--out_dir", str(out),
-                        "--pitch_norm", "true", "--phase", "vocoder", "--synthetic", "4", "--report_f0", "true"]
-                       + extra, cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return out, json.loads(r.stdout.strip().splitlines()[-1])
+    return out, anon_cli.run_child(["--device", DEV, "--out_dir", str(out), "--pitch_norm", "true", "--phase", "vocoder",
+                                    "--synthetic", "4", "--report_f0", "true"] + extra)
 
 
 @gpu

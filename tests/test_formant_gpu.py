@@ -18,7 +18,6 @@ over the three resonance rows x 3 phase seeds on the CPU; two Griffin-Lim trajec
 ways, so the tests ask twice its figures."""
 import ctypes
 import errno
-import importlib.util
 import json
 import os
 import subprocess
@@ -27,6 +26,7 @@ import sys
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import formant_ref as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -262,12 +262,7 @@ def test_recipe_trains_one_epoch_with_preserved_formants(tmp_path):
 
 
 def _anonymize(capsys, argv):
-    spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--synthetic", "4",
-              "--seed", "3"] + argv)
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    return anon_cli.run(capsys, ["--device", DEV, "--synthetic", "4", "--seed", "3"] + argv)
 
 
 @gpu

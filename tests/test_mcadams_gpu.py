@@ -25,7 +25,6 @@ Left out: samples touched by a frame the restatement flags as near a decision (n
 tests/test_mcadams_cpu.py checks that), at most 1 %."""
 import ctypes
 import errno
-import importlib.util
 import json
 import os
 import subprocess
@@ -35,6 +34,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import formant_ref as FR
 from tests import mcadams_ref as M
 
@@ -261,11 +261,7 @@ def test_a_range_draws_one_coefficient_per_utterance():
 
 
 def _anonymize(capsys, argv):
-    spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--synthetic", "4"] + argv)
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    return anon_cli.run(capsys, ["--device", DEV, "--synthetic", "4"] + argv)
 
 
 @gpu

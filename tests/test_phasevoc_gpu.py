@@ -13,15 +13,13 @@ waveform would test the STFT's rounding, not this kernel.  u = 2^-24.  The bars,
          magnitudes are, bit for bit, those of sa_pitch_stretch_mag (whose own bar tests/test_pitchnorm_gpu.py holds)
   r = 1  |C - R| <= 4 u |R|: |R| by one fp32 fma and square root, one rounding of the product, the telescoped phase"""
 import ctypes
-import json
 import math
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import formant_ref as F
 from tests import phasevoc_ref as V
 from tests import pitch_ref as P
@@ -331,12 +329,8 @@ def test_formant_shifter_with_the_vocoder_moves_the_envelope():
 
 def _anonymize_child(tmp_path, name, extra):
     out = tmp_path / name
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "anonymize.py"),
-                        os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--out_dir", str(out),
-                        "--pitch_norm", "true", "--synthetic", "4", "--report_f0", "true", "--report_stoi", "true"]
-                       + extra, cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return out, json.loads(r.stdout.strip().splitlines()[-1])
+    return out, anon_cli.run_child(["--device", DEV, "--out_dir", str(out), "--pitch_norm", "true", "--synthetic", "4",
+                                    "--report_f0", "true", "--report_stoi", "true"] + extra)
 
 
 @gpu

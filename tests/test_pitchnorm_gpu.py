@@ -13,6 +13,7 @@ import os
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import pitch_ref as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -215,12 +216,7 @@ def test_recipe_main_trains_one_epoch(tmp_path, capsys):
 
 
 def _anonymize(capsys, argv):
-    spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--synthetic", "4",
-              "--seed", "3"] + argv)
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    return anon_cli.run(capsys, ["--device", DEV, "--synthetic", "4", "--seed", "3"] + argv)
 
 
 @gpu

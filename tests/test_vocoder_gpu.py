@@ -18,16 +18,14 @@ seeds 0..7 -- the scale on which two trajectories of this non-convex iteration d
 the signals below (tools/vocoder_delta.py prints them): DELTA_TRUE for true STFT magnitudes, DELTA_MEL for the
 feature round trip's mean |dB| error.  See the constants for the figures.  The GPU's signal also tracks the
 restatement's directly (TRACK_MEASURED), which is asserted with a stated margin."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from speech_anonymization_amd import vocoder
+from tests import anon_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -342,13 +340,8 @@ def test_feature_round_trip(loop_case):
 # the command line
 # ---------------------------------------------------------------------------------------------------
 def _anonymize(out, extra):
-    cmd = [sys.executable, os.path.join(ROOT, "anonymize.py"), os.path.join(ROOT, "speechbrain_configs", "convae.yaml"),
-           "--device", DEV, "--model_type", "fcae", "--out_dir", str(out), "--synthetic", "4", "--n_iter", "8",
-           "--seed", "3"] + extra
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=ROOT)
-    print(r.stdout[-2000:], r.stderr[-3000:])
-    assert r.returncode == 0
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return anon_cli.run_child(["--device", DEV, "--model_type", "fcae", "--out_dir", str(out), "--synthetic", "4",
+                               "--n_iter", "8", "--seed", "3"] + extra, timeout=180)
 
 
 def _check_outputs(out, res):

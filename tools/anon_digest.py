@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""SHA-256 digests of what the waveform anonymisers compute, for comparing two commits bit for bit on one GPU:
+
+    python tools/anon_digest.py [--device cuda:0] [--out FILE] [--each]
+
+Every output tensor (the waveforms and ``last``) of PitchNormalizer over phase x formants x f0_method x contour, of
+FormantShifter in both phases and of McAdams with a fixed coefficient and with a range, each on
+data.synthetic_gender_dataset(6, 3) and on one batch of width 16037 (no multiple of the hop) with lens (1.0, 0.73,
+0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of six anonymize.py modes.
+Prints one JSON object with one digest per transform and input (over the digests of its tensors, batch by batch) and
+one per mode (over its JSON line and its WAV files by name); ``--each`` prints every item's own digest instead, to find
+what differs.  profiles/anon_refactor_digest.json is its output."""
+import contextlib
+import hashlib
+import importlib.util
+import io
+import itertools
+import json
+import os
+import sys
+import tempfile
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import speech_anonymization_amd as pkg  # noqa: E402,F401  (registers the package name)
+from speech_anonymization_amd import data, mcadams, pitchnorm  # noqa: E402
+
+MODES = {"passthrough": ["--passthrough", "true"],
+         "pitch_norm": ["--pitch_norm", "true"],
+         "pitch_norm_contour_viterbi": ["--pitch_norm", "true", "--phase", "vocoder", "--contour_scale", "0.5",
+                                        "--f0_method", "viterbi"],
+         "formant_shift": ["--formant_ratio", "1.15"],
+         "mcadams": ["--mcadams", "0.8"],
+         "mcadams_range": ["--mcadams_min", "0.5", "--mcadams_max", "0.9"]}
+COMMON = ["--synthetic", "3", "--batch_size", "3", "--n_iter", "2", "--report_f0", "true", "--report_stoi", "true"]
+
+
+def sha(t):
+    t = t.detach().cpu().contiguous()
+    head = f"{t.dtype}{tuple(t.shape)}".encode()
+    return hashlib.sha256(head + t.view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def inputs():
+    """name -> list of (wavs, lens) on the host"""
+    odd = next(iter(data.synthetic_gender_dataset(3, 3, n_samples=16037, seed=7))).sig[0]
+    return {"synthetic_6_3": [b.sig for b in data.synthetic_gender_dataset(6, 3)],
+            "width_16037": [(odd, torch.tensor([1.0, 0.73, 0.5]))]}
+
+
+def transforms():
+    """name -> a function that makes the transform anew (each owns a generator)"""
+    out = {}
+    formants = {"moved": {}, "preserved": {"preserve_formants": True}, "ratio_1.15": {"formant_ratio": 1.15}}
+    contours = {"off": {}, "0.5_smooth0": {"contour_scale": 0.5, "contour_smooth": 0},
+                "0.5_smooth2": {"contour_scale": 0.5, "contour_smooth": 2}}
+    for phase, (fn, fo), method, (cn, co) in itertools.product(pitchnorm.PHASES, formants.items(),
+                                                               pitchnorm.F0_METHODS, contours.items()):
+        if co and phase != "vocoder":
+            continue
+        kw = dict(fo, **co, phase=phase, f0_method=method)
+        out[f"PitchNormalizer/{phase}/{fn}/{method}/contour_{cn}"] = lambda kw=kw: pitchnorm.PitchNormalizer(**kw)
+    for phase in pitchnorm.PHASES:
+        out[f"FormantShifter/{phase}"] = lambda phase=phase: pitchnorm.FormantShifter(1.15, phase=phase)
+    out["McAdams/alpha_0.8"] = lambda: mcadams.McAdams(alpha=0.8)
+    out["McAdams/range_0.5_0.9"] = lambda: mcadams.McAdams(alpha_range=(0.5, 0.9))
+    return out
+
+
+def anonymize_modes(device, res):
+    spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    for name, argv in MODES.items():
+        with tempfile.TemporaryDirectory() as out:
+            text = io.StringIO()
+            with contextlib.redirect_stdout(text):
+                mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", device, "--out_dir",
+                          out] + COMMON + argv)
+            line = json.loads(text.getvalue().strip().splitlines()[-1])
+            line["out_dir"] = name
+            res[f"anonymize/{name}/json"] = hashlib.sha256(json.dumps(line).encode()).hexdigest()
+            for wav in sorted(os.listdir(out)):
+                with open(os.path.join(out, wav), "rb") as f:
+                    res[f"anonymize/{name}/{wav}"] = hashlib.sha256(f.read()).hexdigest()
+
+
+def main(argv):
+    device = argv[argv.index("--device") + 1] if "--device" in argv else "cuda:0"
+    torch.cuda.set_device(torch.device(device))
+    res = {}
+    for (tn, make), (name, batches) in itertools.product(transforms().items(), inputs().items()):
+        tr = make()
+        for k, (wavs, lens) in enumerate(batches):
+            out = tr(wavs.to(device).contiguous(), lens)
+            res[f"{tn}/{name}/{k}/out"] = sha(out)
+            for j, t in enumerate(getattr(tr, "last", None) or ()):
+                res[f"{tn}/{name}/{k}/last{j}"] = sha(t)
+    anonymize_modes(device, res)
+    if "--each" not in argv:                                 # one digest per transform and input, one per mode
+        groups = {}
+        for key in sorted(res):
+            head = "/".join(key.split("/")[:2] if key.startswith("anonymize/") else key.split("/")[:-2])
+            groups.setdefault(head, hashlib.sha256()).update(f"{key}={res[key]}\n".encode())
+        res = {head: h.hexdigest() for head, h in groups.items()}
+    text = json.dumps(res, indent=1, sort_keys=True) + "\n"
+    if "--out" in argv:
+        with open(argv[argv.index("--out") + 1], "w") as f:
+            f.write(text)
+    else:
+        sys.stdout.write(text)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

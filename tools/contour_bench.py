@@ -181,19 +181,17 @@ def main():
     batch.sig = (wav.cpu(), lens_cpu)
     gamma, s = 0.0, 2
 
-    Np = HOP * -(-N // HOP)
-    wp = torch.nn.functional.pad(wav, (0, Np - N)).contiguous()
+    wp, R = pitchnorm.padded_stft(wav)
     f0 = ops.yin_f0(wp)
     args = (f0, lens, N, 170.0, gamma, s, 0.5, 2.0, 5)
     rho_q, Q, Tq, mean, voiced = ops.pitch_contour(*args)
     t_rho, t_Q, t_Tq = torch_contour(*args)
     differ = int((t_rho != rho_q).sum())
-    R = vocoder.stft(wp)
     T, Tout = R.shape[1], int(Tq.max())
     one = torch.ones(B, device=dev)
     mag = ops.pitch_stretch_mag(R, one, T)
     q = (rho_q.float() / 65536.0).contiguous()
-    n_valid = torch.round(lens.double() * N).clamp(0, N).to(torch.int32)
+    n_valid = pitchnorm.n_valid(lens, N, dev).to(torch.int32)
     C = ops.pv_synth_map(R, rho_q, Q, Tout)
     d_synth = float((C - torch_synth_map(R, rho_q, Q, Tout)).abs().max() / mag.max())
     M = ops.env_warp_frames(mag, q)

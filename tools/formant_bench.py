@@ -75,14 +75,13 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, ops, pitchnorm, vocoder
+    from speech_anonymization_amd import data, ops, pitchnorm
     B, N = a.B, int(a.seconds * SR)
     wav_cpu, lens_cpu = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N))).sig
     wav, lens = wav_cpu.to(dev), lens_cpu.to(dev)
 
     ratio = ops.pitch_ratio(ops.yin_f0(wav), lens, N)[0]
-    Np = HOP * -(-N // HOP)
-    R = vocoder.stft(torch.nn.functional.pad(wav, (0, Np - N)).contiguous())
+    R = pitchnorm.padded_stft(wav)[1]
     Tout = max(pitchnorm.stretched_frames(R.shape[1], r) for r in ratio.cpu().tolist())
     S = ops.pitch_stretch_mag(R, ratio, Tout)
     n_c, floor_rel, limit = 30, 1e-4, 40.0 * ops.LN10_OVER_20

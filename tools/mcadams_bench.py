@@ -65,7 +65,7 @@ def main():
     wav_cpu, lens_cpu = batch.sig
     wav, lens = wav_cpu.to(dev), lens_cpu.to(dev)
     alpha = torch.full((B,), a.alpha, device=dev)
-    nv = torch.round(lens.double() * N).to(torch.int32)
+    nv = pitchnorm.n_valid(lens, N, dev).to(torch.int32)
     T = ops.mcadams_frames(N)
 
     out_gpu, gain, status = ops.mcadams(wav, alpha, nv, True, return_status=True)

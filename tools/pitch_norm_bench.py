@@ -100,14 +100,12 @@ def main():
     norm = pitchnorm.PitchNormalizer()
     f0 = ops.yin_f0(wav)
     ratio, mean, voiced = ops.pitch_ratio(f0, lens, N)
-    Np = HOP * -(-N // HOP)
-    wp = torch.nn.functional.pad(wav, (0, Np - N)).contiguous()
-    R = vocoder.stft(wp)
+    wp, R = pitchnorm.padded_stft(wav)
     Tout = max(pitchnorm.stretched_frames(R.shape[1], r) for r in ratio.cpu().tolist())
     S = ops.pitch_stretch_mag(R, ratio, Tout)
     phi = norm.gl.draw_phase(S.shape).to(dev)
     y = norm.gl(S, phase=phi)
-    nv = torch.round(lens.double() * N).to(torch.int32)
+    nv = pitchnorm.n_valid(lens, N, dev).to(torch.int32)
     out.update(ratio_min=round(float(ratio.min()), 4), ratio_max=round(float(ratio.max()), 4), Tout=Tout)
     for name, fn in (("stage_yin_ms", lambda: ops.yin_f0(wav)),
                      ("stage_ratio_ms", lambda: ops.pitch_ratio(f0, lens, N)),
