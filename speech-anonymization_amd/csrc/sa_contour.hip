@@ -8,7 +8,7 @@
 // The time map is in integers so that no order of summation can change a bit of it.  Plain HIP, no atomics, fixed
 // summation orders, the same bits on every run.
 #include "sa_common.h"
-#include "sa_pitch_stretch.h"
+#include "sa_pitch_shared.h"
 #include "sa_contour_map.h"
 #include <errno.h>
 
@@ -16,21 +16,16 @@
 #define CT_SMOOTH_MAX 8
 #define CT_HALO CT_SMOOTH_MAX            // f^ a pass needs on either side of its frames
 #define CT_FLOOR_HZ 60.0                 // YIN's lowest
-#define CT_HOP 160
-#define CT_MAX_N (1 << 30)
-#define CTR_TILE 256                     // outputs per workgroup of sa_pitch_resample_map
-#define CTR_HALF 16.0                    // filter half-width in periods of the cut-off
-#define CTR_SPAN (2 * CTR_TILE + 2 * 32 + 2)
 
 extern "C" int sa_contour_dim(int which) {
   switch (which) {
     case 0: return CT_W;
     case 1: return CT_SMOOTH_MAX;
-    case 2: return CT_HOP;
+    case 2: return PN_HOP;
     case 3: return 16;                   // fraction bits of rho_q
     case 4: return CT_QBITS;             // fraction bits of Q
-    case 5: return CTR_TILE;
-    case 6: return CTR_SPAN;
+    case 5: return RS_TILE;
+    case 6: return RS_SPAN;
     default: return -EINVAL;
   }
 }
@@ -76,7 +71,7 @@ __device__ static inline double ct_fill(const float* __restrict__ f0, const long
 }
 
 // grid (B): one workgroup of 256 threads per row, T walked in passes of 256 frames; no workgroup waits on another.
-//   statistics  exactly sa_pitch_ratio's: strided fp64 sums, butterfly, the four waves in order
+//   statistics  sa_pitch_ratio's, from the same text (pn_counted_frames and pn_voiced_mean, sa_pitch_shared.h)
 //   pass A      l[t] by a max-scan of the voiced indices, left to right, with a carry between the passes
 //   pass B      n[t] by a min-scan, right to left; (l, n) are kept in the words of Q, which nothing else needs yet
 //   pass C      f^ of the tile and its halo into LDS, the triangle, the ratio, rho_q
@@ -88,8 +83,6 @@ __global__ __launch_bounds__(CT_W) void sa_pitch_contour_kernel(const float* __r
                                                                 double r_max, int min_voiced, int* rho_q,
                                                                 long long* Qg, int* __restrict__ Tq,
                                                                 float* __restrict__ mean, int* __restrict__ voiced) {
-  __shared__ double part[4];
-  __shared__ int cnt[4];
   __shared__ double stat[2];
   __shared__ int shi[4];
   __shared__ long long shl[4];
@@ -99,39 +92,14 @@ __global__ __launch_bounds__(CT_W) void sa_pitch_contour_kernel(const float* __r
   int* rq = rho_q + (size_t)b * T;
   long long* Q = Qg + (size_t)b * T;
 
-  double nb = rint((double)lens[b] * (double)N);
-  nb = nb >= 0.0 ? (nb <= (double)N ? nb : (double)N) : 0.0;           // (NaN -> 0)
-  int F = (int)nb / CT_HOP + 1;
-  if (F > T) F = T;
-  double acc = 0.0;
-  int n = 0;
-  for (int t = tid; t < F; t += CT_W) {
-    const float v = f0[t];
-    if (v > 0.0f) {
-      acc += (double)v;
-      ++n;
-    }
-  }
-  acc = sa_wave_sum_d(acc);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((tid & 63) == 0) {
-    part[tid >> 6] = acc;
-    cnt[tid >> 6] = n;
-  }
-  __syncthreads();
+  const int F = pn_counted_frames(lens[b], N, T);
+  int v0;
+  const double m0 = pn_voiced_mean(f0, F, &v0);               // (thread 0's)
   if (tid == 0) {
-    double s = 0.0;
-    int v = 0;
-    for (int w = 0; w < 4; ++w) {
-      s += part[w];
-      v += cnt[w];
-    }
-    const double m = v > 0 ? s / (double)v : 0.0;
-    stat[0] = m;
-    stat[1] = (v >= min_voiced && m > 0.0) ? 1.0 : 0.0;
-    mean[b] = (float)m;
-    voiced[b] = v;
+    stat[0] = m0;
+    stat[1] = (v0 >= min_voiced && m0 > 0.0) ? 1.0 : 0.0;
+    mean[b] = (float)m0;
+    voiced[b] = v0;
   }
   __syncthreads();
   const double m = stat[0];
@@ -202,8 +170,8 @@ __global__ __launch_bounds__(CT_W) void sa_pitch_contour_kernel(const float* __r
 extern "C" int sa_pitch_contour(const float* f0, const float* lens, int B, int T, int N, float target, float gamma,
                                 int smooth, float r_min, float r_max, int min_voiced, int* rho_q, long long* Q,
                                 int* Tq, float* mean, int* voiced, void* stream) {
-  if (!f0 || !lens || !rho_q || !Q || !Tq || !mean || !voiced || B < 1 || B > PN_MAX_B || T < 2 || T > PN_MAX_T ||
-      N < 1 || N > CT_MAX_N || !(target > 0.0f) || !(gamma >= 0.0f) || !(gamma <= 2.0f) || smooth < 0 ||
+  if (!f0 || !lens || !rho_q || !Q || !Tq || !mean || !voiced || !pn_rows_ok(B) || !pn_frames_ok(T, 2) ||
+      !pn_samples_ok(N) || !(target > 0.0f) || !(gamma >= 0.0f) || !(gamma <= 2.0f) || smooth < 0 ||
       smooth > CT_SMOOTH_MAX || !(r_min >= 0.5f) || !(r_max <= 2.0f) || !(r_min <= r_max))
     return -EINVAL;
   hipLaunchKernelGGL(sa_pitch_contour_kernel, dim3(B), dim3(CT_W), 0, (hipStream_t)stream, f0, lens, T, N,
@@ -218,29 +186,29 @@ extern "C" int sa_pitch_contour(const float* f0, const float* lens, int B, int T
 // ip + fr, and the filter is section 15's at the local ratio r_loc = w[t] / 2^17 <= 2: c = min(1, 1 / r_loc),
 // H = 16 / c <= 32, at most 64 taps.  Row b's input ends at (T'_b - 1) 160 samples, at most Nin.  The workgroup
 // stages the span [ip(n0) - 32, ip(n0) - 32 + 578): the positions of a tile advance by at most 2 per sample, so every
-// tap of the tile lies inside (a tap that does not -- a table no sa_pitch_contour wrote -- is left out).  A thread
-// forms each weight in fp64 and rounds it once, and accumulates in fp32 in the order of i.
+// tap of the tile lies inside (a tap that does not -- a table no sa_pitch_contour wrote -- is left out).  The taps
+// are sa_pitch_resample's loop (pn_rs_taps, sa_pitch_shared.h) at the position ip + fr and the ratio r_loc.
 __device__ static inline long long ctr_position(const int* __restrict__ rq, const long long* __restrict__ Q, int T,
                                                 int n, long long* w) {
-  const int t = min(n / CT_HOP, T - 2);
+  const int t = min(n / PN_HOP, T - 2);
   *w = ct_w(rq, t);
   const long long q = min(max(Q[t], 0LL), (long long)t << 18);
-  return (long long)CT_HOP * q + *w * (long long)(n - CT_HOP * t);
+  return (long long)PN_HOP * q + *w * (long long)(n - PN_HOP * t);
 }
 
-__global__ __launch_bounds__(CTR_TILE) void sa_pitch_resample_map_kernel(const float* __restrict__ y,
-                                                                         const int* __restrict__ rho_q,
-                                                                         const long long* __restrict__ Qg,
-                                                                         const int* __restrict__ n_valid, int Nin,
-                                                                         int Nout, int T, float* __restrict__ out) {
-  __shared__ float ys[CTR_SPAN];
-  const int tid = threadIdx.x, b = blockIdx.y, n0 = blockIdx.x * CTR_TILE, n = n0 + tid;
+__global__ __launch_bounds__(RS_TILE) void sa_pitch_resample_map_kernel(const float* __restrict__ y,
+                                                                        const int* __restrict__ rho_q,
+                                                                        const long long* __restrict__ Qg,
+                                                                        const int* __restrict__ n_valid, int Nin,
+                                                                        int Nout, int T, float* __restrict__ out) {
+  __shared__ float ys[RS_SPAN];
+  const int tid = threadIdx.x, b = blockIdx.y, n0 = blockIdx.x * RS_TILE, n = n0 + tid;
   const int* rq = rho_q + (size_t)b * T;
   const long long* Q = Qg + (size_t)b * T;
-  const long long vin = min((long long)Nin, (long long)CT_HOP * (long long)(ct_frames(Q, T) - 1));
+  const long long vin = min((long long)Nin, (long long)PN_HOP * (long long)(ct_frames(Q, T) - 1));
   long long w;
   const long long span0 = (ctr_position(rq, Q, T, n0, &w) >> CT_QBITS) - 32;
-  for (int i = tid; i < CTR_SPAN; i += CTR_TILE) {
+  for (int i = tid; i < RS_SPAN; i += RS_TILE) {
     const long long s = span0 + i;
     ys[i] = (s >= 0 && s < vin) ? y[(size_t)b * Nin + s] : 0.0f;
   }
@@ -251,32 +219,17 @@ __global__ __launch_bounds__(CTR_TILE) void sa_pitch_resample_map_kernel(const f
     const long long Z = ctr_position(rq, Q, T, n, &w);
     const long long ip = Z >> CT_QBITS;
     const double fr = (double)(Z & (CT_QONE - 1)) * (1.0 / (double)CT_QONE);
-    const double r = (double)w * (1.0 / (double)CT_QONE);
-    const double c = r > 1.0 ? 1.0 / r : 1.0, H = CTR_HALF / c;
-    const double pos = (double)ip + fr;
-    const long long lo = (long long)floor(pos - H) + 1;
-    const double invH = 1.0 / H;
-    for (int q = 0; q < 64; ++q) {
-      const long long i = lo + q;
-      const double u = (double)(ip - i) + fr;
-      const long long idx = i - span0;
-      if (!(u > -H) || idx >= CTR_SPAN) break;
-      if (idx < 0) continue;
-      const double cu = c * u;
-      const double snc = cu == 0.0 ? 1.0 : sinpi(cu) / (3.14159265358979323846 * cu);
-      const float h = (float)(c * snc * (0.5 + 0.5 * cospi(u * invH)));
-      acc = fmaf(ys[idx], h, acc);
-    }
+    acc = pn_rs_taps<true>(ys, span0, (double)ip + fr, (double)w * (1.0 / (double)CT_QONE));
   }
   out[(size_t)b * Nout + n] = acc;
 }
 
 extern "C" int sa_pitch_resample_map(const float* y, const int* rho_q, const long long* Q, const int* n_valid, int B,
                                      int Nin, int Nout, int T, float* out, void* stream) {
-  if (!y || !rho_q || !Q || !n_valid || !out || B < 1 || B > PN_MAX_B || Nin < 1 || Nin > CT_MAX_N || Nout < 1 ||
-      Nout > CT_MAX_N / 2 || T < 2 || T > PN_MAX_T)
+  if (!y || !rho_q || !Q || !n_valid || !out || !pn_rows_ok(B) || !pn_samples_ok(Nin) || Nout < 1 ||
+      Nout > PN_MAX_N / 2 || !pn_frames_ok(T, 2))
     return -EINVAL;
-  hipLaunchKernelGGL(sa_pitch_resample_map_kernel, dim3(sa_div_up(Nout, CTR_TILE), B), dim3(CTR_TILE), 0,
+  hipLaunchKernelGGL(sa_pitch_resample_map_kernel, dim3(sa_div_up(Nout, RS_TILE), B), dim3(RS_TILE), 0,
                      (hipStream_t)stream, y, rho_q, Q, n_valid, Nin, Nout, T, out);
   return -(int)hipGetLastError();
 }

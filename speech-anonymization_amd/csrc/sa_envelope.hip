@@ -40,6 +40,16 @@ __device__ static inline float env_q(float q) {            // a warp factor no k
   return q >= 0.25f && q <= 4.0f ? q : (q > 4.0f ? 4.0f : (q < 0.25f ? 0.25f : 1.0f));
 }
 
+// The store of stage (c) for one frame and bin: E(w_k) and E(theta_k) from the sums Ew and Et and the frame's c_0,
+// the clamped gain, out = s exp(g) (at q == 1 a copy of s) and the optional env.
+__device__ static inline void env_store(float Ew, float Et, float c0, float max_gain_ln, float q, float s, size_t o,
+                                        float* __restrict__ out, float* __restrict__ env) {
+  const float ew = fmaf(2.0f, Ew, c0), et = fmaf(2.0f, Et, c0);
+  const float g = fminf(fmaxf(et - ew, -max_gain_ln), max_gain_ln);
+  out[o] = q == 1.0f ? s : s * expf(g);
+  if (env) env[o] = ew;
+}
+
 // grid (tiles of 8 frames, B), 4 waves.  The tile's 8 x 201 magnitudes are contiguous in memory and are staged as
 // they lie.
 //   (a) wave w takes the frames 2 w and 2 w + 1 and finds each frame's maximum by butterfly; then thread k forms L
@@ -176,16 +186,10 @@ __global__ __launch_bounds__(ENV_THREADS) void sa_env_warp_kernel(const float* _
       w0 = w1, w1 = w2;
     }
 #pragma unroll
-    for (int f = 0; f < ENV_G; ++f) {
-      if (f < nf) {
-        const float ew = fmaf(2.0f, Ew[f], cep[f]), et = fmaf(2.0f, Et[f], cep[f]);
-        const float g = fminf(fmaxf(et - ew, -max_gain_ln), max_gain_ln);
-        const float s = Ss[f * ENV_NBIN + k];
-        const size_t o = base + (size_t)f * ENV_NBIN + k;
-        out[o] = qf[f] == 1.0f ? s : s * expf(g);
-        if (env) env[o] = ew;
-      }
-    }
+    for (int f = 0; f < ENV_G; ++f)
+      if (f < nf)
+        env_store(Ew[f], Et[f], cep[f], max_gain_ln, qf[f], Ss[f * ENV_NBIN + k], base + (size_t)f * ENV_NBIN + k,
+                  out, env);
     return;
   }
   const float q = env_q(qrow[b]);
@@ -213,23 +217,21 @@ __global__ __launch_bounds__(ENV_THREADS) void sa_env_warp_kernel(const float* _
     Et[2 * f] = Et2[f].x, Et[2 * f + 1] = Et2[f].y;
   }
 #pragma unroll
-  for (int f = 0; f < ENV_G; ++f) {
-    if (f < nf) {
-      const float ew = fmaf(2.0f, Ew[f], cep[f]), et = fmaf(2.0f, Et[f], cep[f]);
-      const float g = fminf(fmaxf(et - ew, -max_gain_ln), max_gain_ln);
-      const float s = Ss[f * ENV_NBIN + k];
-      const size_t o = base + (size_t)f * ENV_NBIN + k;
-      out[o] = q == 1.0f ? s : s * expf(g);
-      if (env) env[o] = ew;
-    }
-  }
+  for (int f = 0; f < ENV_G; ++f)
+    if (f < nf)
+      env_store(Ew[f], Et[f], cep[f], max_gain_ln, q, Ss[f * ENV_NBIN + k], base + (size_t)f * ENV_NBIN + k, out,
+                env);
+}
+
+static inline bool env_args_ok(const float* S, const float* q, int B, int T, int n_c, float floor_rel,
+                               float max_gain_ln, const float* out) {
+  return S && q && out && B >= 1 && B <= ENV_MAX_B && T >= 1 && T <= ENV_MAX_T && n_c >= 1 && n_c <= ENV_NC_MAX &&
+         floor_rel > 0.0f && floor_rel < 1.0f && max_gain_ln > 0.0f;          // (a NaN fails its comparison)
 }
 
 extern "C" int sa_env_warp(const float* S, const float* q, int B, int T, int n_c, float floor_rel, float max_gain_ln,
                            float* out, float* env, void* stream) {
-  if (!S || !q || !out || B < 1 || B > ENV_MAX_B || T < 1 || T > ENV_MAX_T || n_c < 1 || n_c > ENV_NC_MAX ||
-      !(floor_rel > 0.0f) || !(floor_rel < 1.0f) || !(max_gain_ln > 0.0f))
-    return -EINVAL;
+  if (!env_args_ok(S, q, B, T, n_c, floor_rel, max_gain_ln, out)) return -EINVAL;
   hipLaunchKernelGGL(sa_env_warp_kernel<false>, dim3(sa_div_up(T, ENV_G), B), dim3(ENV_THREADS), 0,
                      (hipStream_t)stream, S, q, T, n_c, floor_rel, max_gain_ln, out, env);
   return -(int)hipGetLastError();
@@ -237,9 +239,7 @@ extern "C" int sa_env_warp(const float* S, const float* q, int B, int T, int n_c
 
 extern "C" int sa_env_warp_frames(const float* S, const float* q, int B, int T, int n_c, float floor_rel,
                                   float max_gain_ln, float* out, float* env, void* stream) {
-  if (!S || !q || !out || B < 1 || B > ENV_MAX_B || T < 1 || T > ENV_MAX_T || n_c < 1 || n_c > ENV_NC_MAX ||
-      !(floor_rel > 0.0f) || !(floor_rel < 1.0f) || !(max_gain_ln > 0.0f))
-    return -EINVAL;
+  if (!env_args_ok(S, q, B, T, n_c, floor_rel, max_gain_ln, out)) return -EINVAL;
   hipLaunchKernelGGL(sa_env_warp_kernel<true>, dim3(sa_div_up(T, ENV_G), B), dim3(ENV_THREADS), 0,
                      (hipStream_t)stream, S, q, T, n_c, floor_rel, max_gain_ln, out, env);
   return -(int)hipGetLastError();

@@ -5,16 +5,12 @@
 // Costs are Q16 integers and every path sum an int64: no floating point decides anything after the candidates'
 // costs are rounded.  Plain HIP C++, no atomics, the same bits on every run.
 #include "sa_common.h"
-#include "sa_pitch_stretch.h"
+#include "sa_pitch_shared.h"
 #include <errno.h>
 #include <limits.h>
 #include <math.h>
 
-#define FV_SR 16000
-#define FV_HOP 160
-#define FV_TMIN 40                       // sa_yin_dim(3)
-#define FV_TMAX 266                      // sa_yin_dim(4)
-#define FV_ROW (FV_TMAX + 1)             // d' values per frame
+#define FV_ROW (PN_TMAX + 1)             // d' values per frame
 #define FV_K 8                           // candidates per frame
 #define FV_S (FV_K + 1)                  // states: the candidates, then unvoiced
 #define FV_G 8                           // frames per workgroup of sa_f0_candidates, one wave each
@@ -22,7 +18,6 @@
 #define FV_CHUNK 256                     // frames per staged chunk of sa_f0_viterbi
 #define FV_FRAC 16
 #define FV_ONE (1 << FV_FRAC)
-#define FV_MAX_N (1 << 30)
 #define FV_INF (1LL << 62)
 
 extern "C" int sa_f0v_dim(int which) {
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(FV_G * SA_WAVE) void sa_f0_candidates_kernel(const 
   for (int k = 0; k < FV_LAGS; ++k) {
     const int tau = FV_LAGS * lane + 1 + k;
     key[k] = INT_MAX;
-    if (tau >= FV_TMIN && tau < FV_TMAX) {
+    if (tau >= PN_TMIN && tau < PN_TMAX) {
       const float c = dp[f][tau];
       if (c <= dp[f][tau - 1] && c < dp[f][tau + 1]) {
         const int q = (int)rintf(fminf(fmaxf(c, 0.0f), 1.0f) * (float)FV_ONE);
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(FV_G * SA_WAVE) void sa_f0_candidates_kernel(const 
 }
 
 extern "C" int sa_f0_candidates(const float* dprime, int B, int T, int* cand_tau, int* cand_q, void* stream) {
-  if (!dprime || !cand_tau || !cand_q || B < 1 || B > PN_MAX_B || T < 1 || T > PN_MAX_T) return -EINVAL;
+  if (!dprime || !cand_tau || !cand_q || !pn_rows_ok(B) || !pn_frames_ok(T, 1)) return -EINVAL;
   hipLaunchKernelGGL(sa_f0_candidates_kernel, dim3(sa_div_up(T, FV_G), B), dim3(FV_G * SA_WAVE), 0,
                      (hipStream_t)stream, dprime, T, cand_tau, cand_q);
   return -(int)hipGetLastError();
@@ -116,12 +111,8 @@ extern "C" int sa_f0_candidates(const float* dprime, int B, int T, int* cand_tau
 // strictly cheaper than the ones before it -- ties go to the smaller index.  psi collects in LDS and leaves for the
 // caller's workspace once per chunk.  Backward, chunk by chunk from the end: psi comes back to LDS, the wave follows it
 // (every lane the same walk: broadcast reads), and the lanes write path and f0 of the chunk's frames in parallel.
-__device__ static inline int fv_frames(float len, int N, int T) {
-  double nb = rint((double)len * (double)N);
-  nb = nb >= 0.0 ? (nb <= (double)N ? nb : (double)N) : 0.0;           // (NaN -> 0)
-  const int F = (int)nb / FV_HOP + 1;
-  return F > T ? T : F;
-}
+// The frames that count are sa_pitch_ratio's and the refinement of a chosen lag is sa_yin_f0's: one text each,
+// sa_pitch_shared.h.
 
 // lane a's value in every lane; a is the same in all lanes (an unrolled loop's counter), so this is a scalar read of
 // the register, not a trip through LDS
@@ -132,7 +123,7 @@ __device__ static inline long long fv_from(long long v, int a) {
   return ((long long)hi << 32) | (long long)lo;
 }
 
-__device__ static inline int fv_lag(int tau) { return tau < 0 ? -1 : min(max(tau, FV_TMIN), FV_TMAX - 1); }
+__device__ static inline int fv_lag(int tau) { return tau < 0 ? -1 : min(max(tau, PN_TMIN), PN_TMAX - 1); }
 
 __global__ __launch_bounds__(SA_WAVE) void sa_f0_viterbi_kernel(const float* __restrict__ dprime,
                                                                 const int* __restrict__ cand_tau,
@@ -148,11 +139,11 @@ __global__ __launch_bounds__(SA_WAVE) void sa_f0_viterbi_kernel(const float* __r
   __shared__ unsigned char c_psi[FV_CHUNK * FV_S];
   __shared__ int c_path[FV_CHUNK];
   const int lane = threadIdx.x, b = blockIdx.x;
-  const int F = fv_frames(lens[b], N, T);
+  const int F = pn_counted_frames(lens[b], N, T);
   const size_t row = (size_t)b * T;
   for (int i = lane; i < FV_ROW; i += SA_WAVE) lgt[i] = log_q[i];
   __syncthreads();
-  const long long lg_min = lgt[FV_TMIN];
+  const long long lg_min = lgt[PN_TMIN];
 
   long long delta = FV_INF;              // lanes past the states stay absent
   int lg_prev = 0;
@@ -231,12 +222,9 @@ __global__ __launch_bounds__(SA_WAVE) void sa_f0_viterbi_kernel(const float* __r
       float hz = 0.0f;
       if (p >= 0) {
         const int tau = fv_lag(cand_tau[(row + t) * FV_K + p]);
-        if (tau >= 0) {                  // sa_yin_f0's refinement, term for term
+        if (tau >= 0) {
           const float* d = dprime + (row + t) * FV_ROW;
-          const double a = d[tau - 1], c = d[tau], e = d[tau + 1];
-          const double den = a - 2.0 * c + e;
-          const double off = den > 0.0 ? 0.5 * (a - e) / den : 0.0;
-          hz = (float)((double)FV_SR / ((double)tau + off));
+          hz = pn_refined_hz(tau, d[tau - 1], d[tau], d[tau + 1]);
         }
       }
       path[row + t] = p;
@@ -261,8 +249,8 @@ extern "C" int sa_f0_viterbi(const float* dprime, const int* cand_tau, const int
                              float jump_cost, float lag_bias, unsigned char* psi, int* path, float* f0,
                              void* stream) {
   long long vq, sq, jq, bq;
-  if (!dprime || !cand_tau || !cand_q || !lens || !log_q || !psi || !path || !f0 || B < 1 || B > PN_MAX_B || T < 1 ||
-      T > PN_MAX_T || N < 1 || N > FV_MAX_N || !fv_weight(voicing_cost, &vq) || !fv_weight(switch_cost, &sq) ||
+  if (!dprime || !cand_tau || !cand_q || !lens || !log_q || !psi || !path || !f0 || !pn_rows_ok(B) ||
+      !pn_frames_ok(T, 1) || !pn_samples_ok(N) || !fv_weight(voicing_cost, &vq) || !fv_weight(switch_cost, &sq) ||
       !fv_weight(jump_cost, &jq) || !fv_weight(lag_bias, &bq))
     return -EINVAL;
   hipLaunchKernelGGL(sa_f0_viterbi_kernel, dim3(B), dim3(SA_WAVE), 0, (hipStream_t)stream, dprime, cand_tau, cand_q,

@@ -14,7 +14,7 @@
 // sa_pv_synth_map is the same three launches with the stretch positions of a time map in place
 // of a ratio's (MAP == true: sa_contour_map.h) and the magnitudes given on the input grid: one kernel text.
 #include "sa_common.h"
-#include "sa_pitch_stretch.h"
+#include "sa_pitch_shared.h"
 #include "sa_contour_map.h"
 #include <errno.h>
 

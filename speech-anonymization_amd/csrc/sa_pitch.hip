@@ -6,34 +6,26 @@
 //   sa_pitch_resample     windowed-sinc read of the re-synthesised waveform at n r_b (duration back, pitch times r_b)
 // Plain fp32 FMAs (positions and filter weights in fp64), no atomics, the same bits on every run.
 #include "sa_common.h"
-#include "sa_pitch_stretch.h"
+#include "sa_pitch_shared.h"
 #include <errno.h>
 #include <limits.h>
 
-#define YIN_SR 16000
-#define YIN_HOP 160
 #define YIN_W 400                        // terms of a difference sum
-#define YIN_TMIN 40                      // 400 Hz
-#define YIN_TMAX 266                     // 60 Hz
-#define YIN_L (YIN_W + YIN_TMAX)         // samples a frame reads; frame t starts at 160 t - L / 2
+#define YIN_L (YIN_W + PN_TMAX)          // samples a frame reads; frame t starts at 160 t - L / 2
 #define YIN_G 8                          // frames per workgroup, one wave each
 #define YIN_K 5                          // consecutive lags per lane (odd: the lanes' LDS reads hit 64 banks)
 #define YIN_THREADS (YIN_G * SA_WAVE)
 #define YIN_LAGS (YIN_K * SA_WAVE)       // 320 lag slots, 1..266 of them used
-#define YIN_XS ((YIN_G - 1) * YIN_HOP + YIN_W + YIN_LAGS + YIN_K + 3)   // 1848: what the idle slots read too
+#define YIN_XS ((YIN_G - 1) * PN_HOP + YIN_W + YIN_LAGS + YIN_K + 3)   // 1848: what the idle slots read too
 #define YIN_DP (YIN_LAGS + 2)            // d' slots per frame in LDS
-#define PN_MAX_N (1 << 30)
-#define RS_TILE 256                      // outputs per workgroup of sa_pitch_resample
-#define RS_HALF 16.0                     // filter half-width in periods of the cut-off
-#define RS_SPAN (2 * RS_TILE + 2 * 32 + 2)
 
 extern "C" int sa_yin_dim(int which) {
   switch (which) {
-    case 0: return YIN_SR;
-    case 1: return YIN_HOP;
+    case 0: return PN_SR;
+    case 1: return PN_HOP;
     case 2: return YIN_W;
-    case 3: return YIN_TMIN;
-    case 4: return YIN_TMAX;
+    case 3: return PN_TMIN;
+    case 4: return PN_TMAX;
     case 5: return YIN_L;
     case 6: return YIN_G;
     case 7: return RS_TILE;
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(YIN_THREADS) void sa_yin_f0_kernel(const float* __r
   __shared__ float dp[YIN_G][YIN_DP];
   const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * YIN_G;
   const int f = tid >> 6, lane = tid & 63, t = t0 + f;
-  const long long s0 = (long long)t0 * YIN_HOP - YIN_L / 2;
+  const long long s0 = (long long)t0 * PN_HOP - YIN_L / 2;
   for (int i = tid; i < YIN_XS; i += YIN_THREADS) {
     const long long n = s0 + i;
     xs[i] = (n >= 0 && n < N) ? wav[(size_t)b * N + n] : 0.0f;
@@ -64,7 +56,7 @@ __global__ __launch_bounds__(YIN_THREADS) void sa_yin_f0_kernel(const float* __r
   __syncthreads();
 
   const int tau0 = YIN_K * lane + 1;
-  const float* x = xs + f * YIN_HOP;
+  const float* x = xs + f * PN_HOP;
   float d[YIN_K], w[2 * YIN_K - 1];
 #pragma unroll
   for (int k = 0; k < YIN_K; ++k) d[k] = 0.0f;
@@ -114,76 +106,43 @@ __global__ __launch_bounds__(YIN_THREADS) void sa_yin_f0_kernel(const float* __r
   for (int k = YIN_K - 1; k >= 0; --k) {
     const int tau = tau0 + k;
     const float c = dp[f][tau];
-    if (tau >= YIN_TMIN && tau < YIN_TMAX && c < thr && c <= dp[f][tau - 1] && c < dp[f][tau + 1]) pick = tau;
+    if (tau >= PN_TMIN && tau < PN_TMAX && c < thr && c <= dp[f][tau - 1] && c < dp[f][tau + 1]) pick = tau;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pick = min(pick, __shfl_xor(pick, o, 64));
 
   if (t >= T) return;
   if (dprime) {
-    float* out = dprime + ((size_t)b * T + t) * (YIN_TMAX + 1);
-    for (int i = lane; i <= YIN_TMAX; i += 64) out[i] = dp[f][i];
+    float* out = dprime + ((size_t)b * T + t) * (PN_TMAX + 1);
+    for (int i = lane; i <= PN_TMAX; i += 64) out[i] = dp[f][i];
   }
   if (lane == 0) {
     float hz = 0.0f;
-    if (pick != INT_MAX) {
-      const double a = dp[f][pick - 1], c = dp[f][pick], e = dp[f][pick + 1];
-      const double den = a - 2.0 * c + e;
-      const double off = den > 0.0 ? 0.5 * (a - e) / den : 0.0;
-      hz = (float)((double)YIN_SR / ((double)pick + off));
-    }
+    if (pick != INT_MAX) hz = pn_refined_hz(pick, dp[f][pick - 1], dp[f][pick], dp[f][pick + 1]);
     f0[(size_t)b * T + t] = hz;
   }
 }
 
 extern "C" int sa_yin_f0(const float* wav, int B, int N, float threshold, float* f0, float* dprime, void* stream) {
-  if (!wav || !f0 || B < 1 || B > PN_MAX_B || N < 1 || N > PN_MAX_N) return -EINVAL;
-  const int T = N / YIN_HOP + 1;
+  if (!wav || !f0 || !pn_rows_ok(B) || !pn_samples_ok(N)) return -EINVAL;
+  const int T = N / PN_HOP + 1;
   hipLaunchKernelGGL(sa_yin_f0_kernel, dim3(sa_div_up(T, YIN_G), B), dim3(YIN_THREADS), 0, (hipStream_t)stream, wav,
                      N, T, threshold, f0, dprime);
   return -(int)hipGetLastError();
 }
 
 // ---- ratio -------------------------------------------------------------------------------------------
-// grid (B): one workgroup per row.  The first F_b = round(lens_b N) / 160 + 1 frames count.  Every thread adds
-// its strided voiced frames in fp64, the wave adds its lanes by butterfly, thread 0 adds the 4 waves in order.
+// grid (B): one workgroup per row.  The first F_b = round(lens_b N) / 160 + 1 frames count; their voiced mean is
+// pn_voiced_mean's (sa_pitch_shared.h: sa_pitch_contour writes the same bits).
 __global__ __launch_bounds__(256) void sa_pitch_ratio_kernel(const float* __restrict__ f0,
                                                              const float* __restrict__ lens, int T, int N,
                                                              double target, double r_min, double r_max,
                                                              int min_voiced, float* __restrict__ ratio,
                                                              float* __restrict__ mean, int* __restrict__ voiced) {
-  __shared__ double part[4];
-  __shared__ int cnt[4];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  double nb = rint((double)lens[b] * (double)N);
-  nb = nb >= 0.0 ? (nb <= (double)N ? nb : (double)N) : 0.0;           // (NaN -> 0)
-  int F = (int)nb / YIN_HOP + 1;
-  if (F > T) F = T;
-  double acc = 0.0;
-  int n = 0;
-  for (int t = tid; t < F; t += 256) {
-    const float v = f0[(size_t)b * T + t];
-    if (v > 0.0f) {
-      acc += (double)v;
-      ++n;
-    }
-  }
-  acc = sa_wave_sum_d(acc);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((tid & 63) == 0) {
-    part[tid >> 6] = acc;
-    cnt[tid >> 6] = n;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    int v = 0;
-    for (int w = 0; w < 4; ++w) {
-      s += part[w];
-      v += cnt[w];
-    }
-    const double m = v > 0 ? s / (double)v : 0.0;
+  const int b = blockIdx.x;
+  int v;
+  const double m = pn_voiced_mean(f0 + (size_t)b * T, pn_counted_frames(lens[b], N, T), &v);
+  if (threadIdx.x == 0) {
     double r = 1.0;
     if (v >= min_voiced && m > 0.0) r = fmin(fmax(target / m, r_min), r_max);
     ratio[b] = (float)r;
@@ -194,8 +153,8 @@ __global__ __launch_bounds__(256) void sa_pitch_ratio_kernel(const float* __rest
 
 extern "C" int sa_pitch_ratio(const float* f0, const float* lens, int B, int T, int N, float target, float r_min,
                               float r_max, int min_voiced, float* ratio, float* mean, int* voiced, void* stream) {
-  if (!f0 || !lens || !ratio || !mean || !voiced || B < 1 || B > PN_MAX_B || T < 1 || T > PN_MAX_T || N < 1 ||
-      N > PN_MAX_N || !(target > 0.0f) || !(r_min >= 0.5f) || !(r_max <= 2.0f) || !(r_min <= r_max))
+  if (!f0 || !lens || !ratio || !mean || !voiced || !pn_rows_ok(B) || !pn_frames_ok(T, 1) || !pn_samples_ok(N) ||
+      !(target > 0.0f) || !(r_min >= 0.5f) || !(r_max <= 2.0f) || !(r_min <= r_max))
     return -EINVAL;
   hipLaunchKernelGGL(sa_pitch_ratio_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, f0, lens, T, N,
                      (double)target, (double)r_min, (double)r_max, min_voiced, ratio, mean, voiced);
@@ -224,8 +183,7 @@ __global__ __launch_bounds__(256) void sa_pitch_stretch_mag_kernel(const float2*
 
 extern "C" int sa_pitch_stretch_mag(const void* R, const float* ratio, int B, int T, int Tout, float* S,
                                     void* stream) {
-  if (!R || !ratio || !S || B < 1 || B > PN_MAX_B || T < 2 || T > PN_MAX_T || Tout < 1 || Tout > PN_MAX_T)
-    return -EINVAL;
+  if (!R || !ratio || !S || !pn_rows_ok(B) || !pn_frames_ok(T, 2) || !pn_frames_ok(Tout, 1)) return -EINVAL;
   hipLaunchKernelGGL(sa_pitch_stretch_mag_kernel, dim3(sa_div_up(Tout * PN_NBIN, 256), B), dim3(256), 0,
                      (hipStream_t)stream, (const float2*)R, ratio, T, Tout, S);
   return -(int)hipGetLastError();
@@ -236,7 +194,8 @@ extern "C" int sa_pitch_stretch_mag(const void* R, const float* ratio, int B, in
 // |u| < H, c = min(1, 1 / r), H = 16 / c: at most 64 taps.  Row b's input ends at 160 ceil(ceil(Nout / 160) r_b)
 // samples (the stretched frame count of a waveform of Nout samples), at most Nin.  The workgroup stages the
 // input span of its tile (at most 2 256 + 64 + 2 samples, zeros outside the row's input); a thread forms each
-// weight in fp64 and rounds it once, and accumulates in fp32 in the order of i.
+// weight in fp64 and rounds it once, and accumulates in fp32 in the order of i (pn_rs_taps, sa_pitch_shared.h:
+// sa_pitch_resample_map runs the same loop).
 __global__ __launch_bounds__(RS_TILE) void sa_pitch_resample_kernel(const float* __restrict__ y,
                                                                     const float* __restrict__ ratio,
                                                                     const int* __restrict__ n_valid, int Nin,
@@ -244,8 +203,9 @@ __global__ __launch_bounds__(RS_TILE) void sa_pitch_resample_kernel(const float*
   __shared__ float ys[RS_SPAN];
   const int tid = threadIdx.x, b = blockIdx.y, n0 = blockIdx.x * RS_TILE, n = n0 + tid;
   const double r = (double)pn_ratio(ratio[b]);
-  const double c = r > 1.0 ? 1.0 / r : 1.0, H = RS_HALF / c;
-  const long long vin = min((long long)Nin, 160LL * (long long)ceil((double)((Nout + YIN_HOP - 1) / YIN_HOP) * r));
+  double H;
+  pn_rs_cutoff(r, &H);
+  const long long vin = min((long long)Nin, 160LL * (long long)ceil((double)((Nout + PN_HOP - 1) / PN_HOP) * r));
   const long long span0 = (long long)floor((double)n0 * r - H) + 1;
   for (int i = tid; i < RS_SPAN; i += RS_TILE) {
     const long long s = span0 + i;
@@ -253,29 +213,12 @@ __global__ __launch_bounds__(RS_TILE) void sa_pitch_resample_kernel(const float*
   }
   __syncthreads();
   if (n >= Nout) return;
-  float acc = 0.0f;
-  if (n < n_valid[b]) {
-    const double pos = (double)n * r;
-    const long long lo = (long long)floor(pos - H) + 1;
-    const double invH = 1.0 / H;
-    for (int q = 0; q < 64; ++q) {
-      const long long i = lo + q;
-      const double u = pos - (double)i;
-      const int idx = (int)(i - span0);
-      if (!(u > -H) || idx < 0 || idx >= RS_SPAN) break;
-      const double cu = c * u;
-      const double snc = cu == 0.0 ? 1.0 : sinpi(cu) / (3.14159265358979323846 * cu);
-      const float h = (float)(c * snc * (0.5 + 0.5 * cospi(u * invH)));
-      acc = fmaf(ys[idx], h, acc);
-    }
-  }
-  out[(size_t)b * Nout + n] = acc;
+  out[(size_t)b * Nout + n] = n < n_valid[b] ? pn_rs_taps<false>(ys, span0, (double)n * r, r) : 0.0f;
 }
 
 extern "C" int sa_pitch_resample(const float* y, const float* ratio, const int* n_valid, int B, int Nin, int Nout,
                                  float* out, void* stream) {
-  if (!y || !ratio || !n_valid || !out || B < 1 || B > PN_MAX_B || Nin < 1 || Nin > PN_MAX_N || Nout < 1 ||
-      Nout > PN_MAX_N / 2)
+  if (!y || !ratio || !n_valid || !out || !pn_rows_ok(B) || !pn_samples_ok(Nin) || Nout < 1 || Nout > PN_MAX_N / 2)
     return -EINVAL;
   hipLaunchKernelGGL(sa_pitch_resample_kernel, dim3(sa_div_up(Nout, RS_TILE), B), dim3(RS_TILE), 0,
                      (hipStream_t)stream, y, ratio, n_valid, Nin, Nout, out);

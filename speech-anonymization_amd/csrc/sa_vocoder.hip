@@ -30,6 +30,10 @@
 
 extern "C" int sa_gl_tile(void) { return GL_G; }
 
+static inline bool gl_shape_ok(int B, int T, int least) {    // rows, and frames (at least `least` of them)
+  return B >= 1 && B <= GL_MAX_B && T >= least && T <= GL_MAX_T;
+}
+
 // ---- Mel -> linear magnitude ---------------------------------------------------------------------------
 // grid (tiles of 16 frames, B).  The tile's powers p[m][f] are formed once (the affine in fp64, so the exponent's
 // argument is rounded once) and held in LDS; thread k < 201 then runs the 80-term dot product of every frame with
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(MM_THREADS) void sa_mel_to_mag_kernel(const float* 
 
 extern "C" int sa_mel_to_mag(const float* x, const float* mean, const float* stdv, const float* M, int B, int T,
                              int Tf, float* S, void* stream) {
-  if (!x || !mean || !stdv || !M || !S || B < 1 || B > GL_MAX_B || T < 1 || T > GL_MAX_T || T > Tf) return -EINVAL;
+  if (!x || !mean || !stdv || !M || !S || !gl_shape_ok(B, T, 1) || T > Tf) return -EINVAL;
   hipLaunchKernelGGL(sa_mel_to_mag_kernel, dim3(sa_div_up(T, MM_FRAMES), B), dim3(MM_THREADS), 0,
                      (hipStream_t)stream, x, mean, stdv, M, T, Tf, S);
   return -(int)hipGetLastError();
@@ -88,6 +92,24 @@ extern "C" int sa_mel_to_mag(const float* x, const float* mean, const float* std
 //   2. thread q <= 100: the four sums per frame over k, then x[q], x[200 + q], x[400 - q], x[200 - q], each times
 //      w / 400, into xs[f][j]
 //   3. every sample of the tile: the sum of its 2 or 3 frames' xs over the sum of their w^2
+// One k of step 2: the ten frames' staged pairs of row k times the twiddles at idx = (k tid) mod 400, added to the
+// cosine sums cs and the sine sums sn (the even k's or the odd k's); idx steps on to the next k.
+__device__ static inline void gl_istft_step(const float* coef_k, const float* tcos, const float* tsin, int tid,
+                                            int& idx, float (&cs)[GL_F], float (&sn)[GL_F]) {
+  const float c = tcos[idx], s = tsin[idx];
+  const float4* row = reinterpret_cast<const float4*>(coef_k);
+#pragma unroll
+  for (int v = 0; v < GL_F / 2; ++v) {
+    const float4 a = row[v];
+    cs[2 * v] = fmaf(a.x, c, cs[2 * v]);
+    sn[2 * v] = fmaf(a.y, s, sn[2 * v]);
+    cs[2 * v + 1] = fmaf(a.z, c, cs[2 * v + 1]);
+    sn[2 * v + 1] = fmaf(a.w, s, sn[2 * v + 1]);
+  }
+  idx += tid;
+  if (idx >= GL_NFFT) idx -= GL_NFFT;
+}
+
 __global__ __launch_bounds__(GL_THREADS) void sa_gl_istft_kernel(const float2* __restrict__ C,
                                                                  const float* __restrict__ win,
                                                                  const float* __restrict__ tw, int T,
@@ -120,34 +142,8 @@ __global__ __launch_bounds__(GL_THREADS) void sa_gl_istft_kernel(const float2* _
     int idx = 0;                                   // (k tid) mod 400
 #pragma unroll 1
     for (int k = 0; k < GL_NBIN; k += 2) {
-      {
-        const float c = tcos[idx], s = tsin[idx];
-        const float4* row = reinterpret_cast<const float4*>(coef[k]);
-#pragma unroll
-        for (int v = 0; v < GL_F / 2; ++v) {
-          const float4 a = row[v];
-          ce[2 * v] = fmaf(a.x, c, ce[2 * v]);
-          se[2 * v] = fmaf(a.y, s, se[2 * v]);
-          ce[2 * v + 1] = fmaf(a.z, c, ce[2 * v + 1]);
-          se[2 * v + 1] = fmaf(a.w, s, se[2 * v + 1]);
-        }
-        idx += tid;
-        if (idx >= GL_NFFT) idx -= GL_NFFT;
-      }
-      if (k + 1 < GL_NBIN) {
-        const float c = tcos[idx], s = tsin[idx];
-        const float4* row = reinterpret_cast<const float4*>(coef[k + 1]);
-#pragma unroll
-        for (int v = 0; v < GL_F / 2; ++v) {
-          const float4 a = row[v];
-          co[2 * v] = fmaf(a.x, c, co[2 * v]);
-          so[2 * v] = fmaf(a.y, s, so[2 * v]);
-          co[2 * v + 1] = fmaf(a.z, c, co[2 * v + 1]);
-          so[2 * v + 1] = fmaf(a.w, s, so[2 * v + 1]);
-        }
-        idx += tid;
-        if (idx >= GL_NFFT) idx -= GL_NFFT;
-      }
+      gl_istft_step(coef[k], tcos, tsin, tid, idx, ce, se);
+      if (k + 1 < GL_NBIN) gl_istft_step(coef[k + 1], tcos, tsin, tid, idx, co, so);
     }
     const float inv = 1.0f / GL_NFFT;
     const bool twin = tid > 0 && tid < 100;        // 400 - q and 200 - q are further samples
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(GL_THREADS) void sa_gl_istft_kernel(const float2* _
 
 extern "C" int sa_gl_istft(const void* C, const float* window, const float* twiddle, int B, int T, float* y,
                            void* stream) {
-  if (!C || !window || !twiddle || !y || B < 1 || B > GL_MAX_B || T < 2 || T > GL_MAX_T) return -EINVAL;
+  if (!C || !window || !twiddle || !y || !gl_shape_ok(B, T, 2)) return -EINVAL;
   hipLaunchKernelGGL(sa_gl_istft_kernel, dim3(sa_div_up(T, GL_G), B), dim3(GL_THREADS), 0, (hipStream_t)stream,
                      (const float2*)C, window, twiddle, T, y);
   return -(int)hipGetLastError();
@@ -195,6 +191,28 @@ extern "C" int sa_gl_istft(const void* C, const float* window, const float* twid
 //   2. thread q <= 100: the four sums per frame over j, then R[q] and R[200 - q]
 //   3. the update of those bins, in fp64 from the fp32 R, Tprev, S and m (201 of them per frame against the
 //      transform's 400 x 201 FMAs): A = R - m Tprev; C' = S A / (|A| + 1e-16), rounded once; stores C' and R
+// One j of step 2: the eight frames' staged samples of row j times the twiddles at idx = (tid j) mod 400, added to the
+// cosine sums cs and the sine sums sn (the even j's or the odd j's); idx steps on to the next j.
+__device__ static inline void gl_project_step(const float* z_j, const float* tcos, const float* tsin, int tid,
+                                              int& idx, float (&cs)[GL_G], float (&sn)[GL_G]) {
+  const float c = tcos[idx], s = tsin[idx];
+  const float4* row = reinterpret_cast<const float4*>(z_j);
+#pragma unroll
+  for (int v = 0; v < GL_G / 4; ++v) {
+    const float4 a = row[v];
+    cs[4 * v] = fmaf(a.x, c, cs[4 * v]);
+    sn[4 * v] = fmaf(a.x, s, sn[4 * v]);
+    cs[4 * v + 1] = fmaf(a.y, c, cs[4 * v + 1]);
+    sn[4 * v + 1] = fmaf(a.y, s, sn[4 * v + 1]);
+    cs[4 * v + 2] = fmaf(a.z, c, cs[4 * v + 2]);
+    sn[4 * v + 2] = fmaf(a.z, s, sn[4 * v + 2]);
+    cs[4 * v + 3] = fmaf(a.w, c, cs[4 * v + 3]);
+    sn[4 * v + 3] = fmaf(a.w, s, sn[4 * v + 3]);
+  }
+  idx += tid;
+  if (idx >= GL_NFFT) idx -= GL_NFFT;
+}
+
 __global__ __launch_bounds__(GL_THREADS) void sa_gl_project_kernel(const float* __restrict__ y,
                                                                    const float* __restrict__ S,
                                                                    const float2* __restrict__ Tprev, float mom,
@@ -226,42 +244,8 @@ __global__ __launch_bounds__(GL_THREADS) void sa_gl_project_kernel(const float* 
   int idx = 0;                                     // (tid j) mod 400
 #pragma unroll 1
   for (int j = 0; j < GL_NFFT; j += 2) {
-    {
-      const float c = tcos[idx], s = tsin[idx];
-      const float4* row = reinterpret_cast<const float4*>(z[j]);
-#pragma unroll
-      for (int v = 0; v < GL_G / 4; ++v) {
-        const float4 a = row[v];
-        ce[4 * v] = fmaf(a.x, c, ce[4 * v]);
-        se[4 * v] = fmaf(a.x, s, se[4 * v]);
-        ce[4 * v + 1] = fmaf(a.y, c, ce[4 * v + 1]);
-        se[4 * v + 1] = fmaf(a.y, s, se[4 * v + 1]);
-        ce[4 * v + 2] = fmaf(a.z, c, ce[4 * v + 2]);
-        se[4 * v + 2] = fmaf(a.z, s, se[4 * v + 2]);
-        ce[4 * v + 3] = fmaf(a.w, c, ce[4 * v + 3]);
-        se[4 * v + 3] = fmaf(a.w, s, se[4 * v + 3]);
-      }
-      idx += tid;
-      if (idx >= GL_NFFT) idx -= GL_NFFT;
-    }
-    {
-      const float c = tcos[idx], s = tsin[idx];
-      const float4* row = reinterpret_cast<const float4*>(z[j + 1]);
-#pragma unroll
-      for (int v = 0; v < GL_G / 4; ++v) {
-        const float4 a = row[v];
-        co[4 * v] = fmaf(a.x, c, co[4 * v]);
-        so[4 * v] = fmaf(a.x, s, so[4 * v]);
-        co[4 * v + 1] = fmaf(a.y, c, co[4 * v + 1]);
-        so[4 * v + 1] = fmaf(a.y, s, so[4 * v + 1]);
-        co[4 * v + 2] = fmaf(a.z, c, co[4 * v + 2]);
-        so[4 * v + 2] = fmaf(a.z, s, so[4 * v + 2]);
-        co[4 * v + 3] = fmaf(a.w, c, co[4 * v + 3]);
-        so[4 * v + 3] = fmaf(a.w, s, so[4 * v + 3]);
-      }
-      idx += tid;
-      if (idx >= GL_NFFT) idx -= GL_NFFT;
-    }
+    gl_project_step(z[j], tcos, tsin, tid, idx, ce, se);
+    gl_project_step(z[j + 1], tcos, tsin, tid, idx, co, so);
   }
 
   const double m = (double)mom;
@@ -287,8 +271,7 @@ __global__ __launch_bounds__(GL_THREADS) void sa_gl_project_kernel(const float* 
 extern "C" int sa_gl_project(const float* y, const float* S, const void* Tprev, float momentum_ratio,
                              const float* window, const float* twiddle, int B, int T, void* C_new, void* R,
                              void* stream) {
-  if (!y || !S || !Tprev || !window || !twiddle || !C_new || !R || B < 1 || B > GL_MAX_B || T < 2 || T > GL_MAX_T)
-    return -EINVAL;
+  if (!y || !S || !Tprev || !window || !twiddle || !C_new || !R || !gl_shape_ok(B, T, 2)) return -EINVAL;
   hipLaunchKernelGGL(sa_gl_project_kernel, dim3(sa_div_up(T, GL_G), B), dim3(GL_THREADS), 0, (hipStream_t)stream,
                      y, S, (const float2*)Tprev, momentum_ratio, window, twiddle, T, (float2*)C_new, (float2*)R);
   return -(int)hipGetLastError();

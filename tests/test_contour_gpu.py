@@ -97,6 +97,8 @@ def test_contour_against_the_restatement(shape, call):
     assert torch.equal(Q, own_Q) and torch.equal(Tq, own_Tq) and torch.equal(Tq, ref.Tq)
     m = mean.cpu().double()
     assert bool(((m - ref.mean).abs() <= 2 * U * ref.mean).all())            # sa_pitch_ratio's bar
+    _, r_mean, r_voiced = ops.pitch_ratio(f0.to(DEV), lens.to(DEV), N, 170.0, min_voiced=min_voiced)
+    assert torch.equal(r_mean, mean) and torch.equal(r_voiced, voiced)       # one text: sa_pitch_ratio's bits
     assert bool((rho_q[~ref.moved] == Cr.RHO_ONE).all())
     if shape == "passes":
         assert ref.moved.tolist() == [True, True, False, False, True, True, True, True]
