@@ -5,6 +5,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
+        [--report_prosody true [--prosody_max_lag K]]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
 normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
@@ -45,14 +46,24 @@ utterances' ``ratio`` is the mean ratio of the row, and with ``--report_f0 true`
 
 ``--f0_method viterbi`` tracks F0 with a Viterbi decode through every frame's d' dips (speech_anonymization_amd.
 pitchnorm.f0_track) instead of first-dip YIN (``yin``, the default).  With ``--pitch_norm true`` it
-steers the normaliser; with ``--report_f0 true``, in any mode, the report is measured with it.  Without either it is
-refused: nothing tracks F0.  The JSON line carries ``"f0_method"`` only when the option is given.
+steers the normaliser; with ``--report_f0 true`` or ``--report_prosody true``, in any mode, the report is measured
+with it.  Without any of them it is refused: nothing tracks F0.  The JSON line carries ``"f0_method"`` only when the
+option is given.
 
 ``--report_stoi true`` adds, in any mode, the intelligibility of every waveform written against the waveform it was
 made from (speech_anonymization_amd.ops.stoi): per utterance ``stoi``, ``estoi`` (both null when the
 utterance has fewer than 30 frames within 40 dB of its loudest) and ``stoi_segments``, and ``stoi_mean`` and
 ``estoi_mean`` over the scored utterances in the final object.  The two are compared over their common width, up to
 the smaller of their sample counts.
+
+``--report_prosody true [--prosody_max_lag K]`` adds, in any mode, how much of the input's intonation is found in
+every waveform written (speech_anonymization_amd.ops.f0_compare): both are tracked with
+``--f0_method`` (``yin`` unless given) and compared over their common width.  Per utterance ``f0_corr`` (the largest
+Pearson correlation of the two F0 tracks over the frames voiced in both, the output read up to K frames, default 8,
+before or after the input) and ``f0_dev_st`` (the standard deviation of the per-frame shift in semitones), both null
+when fewer than 8 frames are voiced in both or a track does not move; ``f0_shift_st``, ``f0_lag_frames``,
+``f0_common_frames`` and ``voicing_agreement``; and ``f0_corr_mean``, ``f0_dev_st_mean``, ``voicing_agreement_mean``
+and ``prosody_scored`` in the final object.
 
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
@@ -134,6 +145,48 @@ class _StoiReport:
             return {}
         tot = self.stats.summarize()
         return {"stoi_mean": tot["stoi"], "estoi_mean": tot["estoi"]}
+
+
+class _ProsodyReport:
+    """--report_prosody true: the pitch track of every waveform about to be written compared with the input's"""
+
+    def __init__(self, settings, f0_method="yin"):
+        self.on = bool(settings.get("report_prosody"))
+        self.max_lag = int(settings.get("prosody_max_lag", vocoder.PROSODY_LAG_DEFAULT))
+        self.method = f0_method
+        self.stats = metrics.ProsodyStats()
+        self.rows = None
+
+    def score(self, ids, wavs, lens, out, counts):
+        """wavs, out [B, *] on the device, lens the relative lengths, counts the samples written per row"""
+        if not self.on:
+            return
+        from speech_anonymization_amd import ops
+        width = min(wavs.shape[1], out.shape[1])
+        n_in = [int(round(float(v) * wavs.shape[1])) for v in lens]
+        nv = torch.tensor([min(a, b, width) for a, b in zip(n_in, counts)], dtype=torch.int32).to(out.device)
+        rel = (nv.double() / width).float()
+        f_in, f_out = (pitchnorm.f0_track(w[:, :width].float().contiguous(), method=self.method, lens=rel)
+                       for w in (wavs, out))
+        frames = (nv // features.HOP + 1).clamp(max=width // features.HOP + 1).to(torch.int32)
+        rho, lag, common, shift, dev, voicing = ops.f0_compare(f_in, f_out, frames, max_lag=self.max_lag)
+        self.stats.append(ids, rho, common, dev, voicing)
+        # (fp64 holds the fp32 and the int32 values exactly: one copy to the host)
+        self.rows = torch.stack([v.double() for v in (rho, lag, common, shift, dev, voicing)]).cpu().tolist()
+
+    def keys(self, i):
+        if not self.on:
+            return {}
+        rho, lag, common, shift, dev, voicing = (v[i] for v in self.rows)
+        return {"f0_corr": rho if common else None, "f0_dev_st": dev if common else None, "f0_shift_st": shift,
+                "f0_lag_frames": int(lag), "f0_common_frames": int(common), "voicing_agreement": voicing}
+
+    def summary(self):
+        if not self.on:
+            return {}
+        tot = self.stats.summarize()
+        return {"f0_corr_mean": tot["f0_corr"], "f0_dev_st_mean": tot["f0_dev_st"],
+                "voicing_agreement_mean": tot["voicing_agreement"], "prosody_scored": tot["scored"]}
 
 
 def _counts(lens, N):
@@ -251,13 +304,14 @@ def main(argv):
     step, head, tail = MODES[vocoder.anonymize_mode(settings)](settings, device, bs, seed)
     f0m = pitchnorm.check_f0_option(settings)
     want_std = "contour_scale" in tail
-    utts, sto = [], _StoiReport(settings)
+    utts, sto, pro = [], _StoiReport(settings), _ProsodyReport(settings, **f0m)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
         out, counts, extra, sc = step(ids, wavs, lens)
         rep = _f0_report(out, lens, want_std=want_std, **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, out, counts)
+        pro.score(ids, wavs, lens, out, counts)
         out = out.cpu()
         for i, uid in enumerate(ids):
             sig = out[i, :counts[i]]
@@ -268,8 +322,10 @@ def main(argv):
                 if want_std:
                     utts[-1].update(f0_std_hz=rep[2][i])
             utts[-1].update(sto.keys(i))
+            utts[-1].update(pro.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
-    print(json.dumps(dict({"out_dir": settings["out_dir"]}, **head, utterances=utts, **tail, **f0m, **sto.summary())))
+    print(json.dumps(dict({"out_dir": settings["out_dir"]}, **head, utterances=utts, **tail, **f0m, **sto.summary(),
+                          **pro.summary())))
 
 
 if __name__ == "__main__":

@@ -745,6 +745,34 @@ int sa_f0_viterbi(const float* dprime, const int* cand_tau, const int* cand_q, c
                   int B, int T, int N, float voicing_cost, float switch_cost, float jump_cost, float lag_bias,
                   unsigned char* psi, int* path, float* f0, void* stream);
 
+/* ---- pitch-correlation scoring (sa_prosody.hip; ops.f0_compare): how much of one F0 track's
+ * movement is found in another.  f0_ref, f0_deg [B][T] fp32 in Hz, 0 or less meaning unvoiced (any two tracks of
+ * sa_yin_f0 or sa_f0_viterbi); frames [B] int32, clamped where it is read to F_b in [0, T]; max_lag Lg in 0..32
+ * frames; min_common m >= 2.  Everything in fp64 on the fp32 inputs:
+ *   v_ref[t] = (t < F_b and f0_ref[t] > 0), v_deg the same way.
+ *   per lag l in [-Lg, Lg]:  O_l = {t : 0 <= t < F_b and 0 <= t + l < F_b};  P_l = {t in O_l : v_ref[t] and
+ *     v_deg[t + l]}, n_l = |P_l|;  with x = f0_ref[t], y = f0_deg[t + l] over P_l:  xm = sum x / n, ym = sum y / n,
+ *     then in a second pass s_xx = sum (x - xm)^2, s_yy = sum (y - ym)^2, s_xy = sum (x - xm)(y - ym).  The lag is
+ *     valid when n_l >= m, s_xx > 0 and s_yy > 0, and then rho_l = s_xy / sqrt(s_xx s_yy) -- exactly 1 for pairwise
+ *     identical x and y.
+ *   l* is chosen on the walk 0, -1, +1, -2, +2, ..., -Lg, +Lg: the first valid lag whose rho is strictly above every
+ *     earlier valid one (an exact tie goes to the smaller |l|, then to the negative lag).
+ *   at l*, over P_l*:  e = 12 log2(y / x);  shift_st = sum e / n;  dev_st = sqrt(sum (e - shift_st)^2 / n);
+ *     common = n_l*;  voicing = #{t in O_l* : v_ref[t] = v_deg[t + l*]} / |O_l*|.
+ *   no valid lag:  rho = 0, lag = 0, common = 0, shift_st = dev_st = 0;  voicing is taken at l = 0, and is 0 when
+ *     F_b = 0.
+ *   rho, shift_st, dev_st, voicing [B] fp32, each rounded once; lag, common [B] int32.  All but rho may be NULL.
+ *   rho is a maximum over lags: an inverted contour reads -1 only at Lg = 0.
+ *   One workgroup per row; no atomics, every sum in a fixed order: the same bits on every run.
+ *   sa_f0cmp_dim(which): 0 the hop 160 the tracks are taken at, 1 the lag limit 32, 2 threads per workgroup; else
+ *     -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer (all outputs but rho may be NULL), B < 1 or > 65535, T < 1 or
+ *     > 104858 (the frames of 2^24 samples), max_lag outside 0..32, min_common < 2. */
+int sa_f0cmp_dim(int which);
+int sa_f0_compare(const float* f0_ref, const float* f0_deg, const int* frames, int B, int T, int max_lag,
+                  int min_common, float* rho, int* lag, int* common, float* shift_st, float* dev_st, float* voicing,
+                  void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

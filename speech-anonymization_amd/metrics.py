@@ -75,3 +75,33 @@ class IntelligibilityStats:
         n = int(self.scored)
         return {"stoi": float(self.stoi_sum) / n if n else None, "estoi": float(self.estoi_sum) / n if n else None,
                 "scored": n, "unscored": self.total - n}
+
+
+class ProsodyStats:
+    """Pitch correlation of a set of utterances (ops.f0_compare), accumulated on the device: the
+    means of the correlation and of the deviation are over the rows that could be scored (common > 0), the mean of
+    the voicing agreement over all rows."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.ids = []
+        self.rho_sum, self.dev_sum, self.voicing_sum, self.scored, self.total = 0.0, 0.0, 0.0, 0, 0
+
+    def append(self, ids, rho, common, dev_st, voicing):
+        """ids: a sequence of B names; rho, dev_st, voicing fp32 [B]; common int [B] (tensors, on any one device)"""
+        ok = common.detach() > 0
+        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+        self.ids.extend(ids)
+        self.rho_sum = self.rho_sum + torch.where(ok, rho.detach().double(), zero).sum()
+        self.dev_sum = self.dev_sum + torch.where(ok, dev_st.detach().double(), zero).sum()
+        self.voicing_sum = self.voicing_sum + voicing.detach().double().sum()
+        self.scored = self.scored + ok.sum()
+        self.total += int(ok.numel())
+
+    def summarize(self):
+        n = int(self.scored)
+        return {"f0_corr": float(self.rho_sum) / n if n else None, "f0_dev_st": float(self.dev_sum) / n if n else None,
+                "voicing_agreement": float(self.voicing_sum) / self.total if self.total else None, "scored": n,
+                "unscored": self.total - n}

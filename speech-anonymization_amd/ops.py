@@ -1398,3 +1398,36 @@ def f0_viterbi(dprime, tau, q, lens, N, voicing_cost=0.15, switch_cost=0.14, jum
     L.check(L.load().sa_f0_viterbi(_f(dprime), _f(tau), _f(q), _f(lens), _f(log_q), B, T, N, *(C.c_float(w) for w in costs),
                                    _f(_f0v_workspace(B, T, dev)), _f(path), _f(f0), L.stream()), "sa_f0_viterbi")
     return (f0, path) if return_path else f0
+
+
+# ---- pitch-correlation scoring (csrc/sa_prosody.hip) ----
+F0CMP_MAX_LAG, F0CMP_MAX_T = 32, (1 << 24) // 160 + 1       # sa_f0cmp_dim(1); the frames of 2^24 samples
+
+_f0cmp_in = functools.partial(_aug_in, family="F0 comparison")
+
+
+def f0_compare(f0_ref, f0_deg, frames, max_lag=8, min_common=8):
+    """f0_ref, f0_deg fp32 [B, T] in Hz (0 or less: unvoiced; two tracks of pitchnorm.f0_track), frames int32 [B] (the
+    frames of a row that count, clamped to [0, T]) -> (rho fp32 [B], lag int32 [B], common int32 [B], shift_st fp32 [B],
+    dev_st fp32 [B], voicing fp32 [B]): the largest Pearson correlation of the two tracks over the frames voiced in
+    both, deg read up to max_lag frames before or after ref; the lag it is found at; the frames it is taken over; the
+    mean and the standard deviation of 12 log2(deg / ref) over them, in semitones; the share of frames on which the
+    voicing of the two agrees.  A row without a lag of at least min_common common frames and a moving contour in both
+    gets rho = lag = common = shift_st = dev_st = 0.  Everything stays on the device (sa_f0_compare)."""
+    if _f0cmp_in(f0_ref, "f0_ref").dim() != 2 or f0_ref.numel() == 0:
+        raise L.SaHipError(f"f0_ref: expected [B, T] with B, T >= 1, got {tuple(f0_ref.shape)}")
+    B, T = f0_ref.shape
+    if B > GL_MAX_B or T > F0CMP_MAX_T:
+        raise L.SaHipError(f"f0_ref: [B, T] = [{B}, {T}] -- B up to {GL_MAX_B} (a grid extent), T up to {F0CMP_MAX_T}")
+    _f0cmp_in(f0_deg, "f0_deg", shape=(B, T))
+    _f0cmp_in(frames, "frames", torch.int32, (B,))
+    max_lag, min_common = int(max_lag), int(min_common)
+    if not 0 <= max_lag <= F0CMP_MAX_LAG or min_common < 2:
+        raise L.SaHipError(f"f0_compare: max_lag in 0..{F0CMP_MAX_LAG} and min_common >= 2 expected, got {max_lag} and "
+                           f"{min_common}")
+    dev = f0_ref.device
+    rho, shift, sdev, voicing = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(4))
+    lag, common = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    L.check(L.load().sa_f0_compare(_f(f0_ref), _f(f0_deg), _f(frames), B, T, max_lag, min_common, _f(rho), _f(lag),
+                                   _f(common), _f(shift), _f(sdev), _f(voicing), L.stream()), "sa_f0_compare")
+    return rho, lag, common, shift, sdev, voicing

@@ -154,6 +154,7 @@ def invert_features(feats, normalizer, lens=None, frames=None, return_magnitude=
 
 
 ANON_MODEL_TYPES = ("convae", "fcae", "endtoend")
+PROSODY_MAX_LAG, PROSODY_LAG_DEFAULT = 32, 8                # ops.F0CMP_MAX_LAG; --prosody_max_lag
 # the two modes that re-synthesise the waveform they are given: their flag and what they write
 RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
                  "formant_shift": ("--formant_ratio", "formant-shifted")}
@@ -203,7 +204,8 @@ def check_anonymize_options(settings, run_opts, environ=None):
     if pitchnorm.check_contour_options(settings) and mode != "pitch_norm":    # 
         raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
                          "pitch")
-    if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0"):
+    if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0") \
+            and settings.get("report_prosody") is not True:
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
     if mode in ("passthrough", "model") and settings.get("model_type") not in ANON_MODEL_TYPES:
         raise SystemExit(f"unknown model_type {settings.get('model_type')!r}: the anonymiser is one of convae, fcae "
@@ -236,6 +238,17 @@ def check_anonymize_options(settings, run_opts, environ=None):
             raise SystemExit(f"--report_stoi {settings['report_stoi']!r}: true or false")
         if settings["report_stoi"] and int(settings.get("sample_rate", 16000)) != 16000:
             raise SystemExit("--report_stoi true scores 16 kHz waveforms only")
+    if settings.get("report_prosody") is not None:          # (any mode, 16 kHz only)
+        if not isinstance(settings["report_prosody"], bool):
+            raise SystemExit(f"--report_prosody {settings['report_prosody']!r}: true or false")
+        if settings["report_prosody"] and int(settings.get("sample_rate", 16000)) != 16000:
+            raise SystemExit("--report_prosody true tracks the pitch of 16 kHz waveforms only")
+    if settings.get("prosody_max_lag") is not None:
+        lag = settings["prosody_max_lag"]
+        if not settings.get("report_prosody"):
+            raise SystemExit("--prosody_max_lag needs --report_prosody true: nothing else compares two pitch tracks")
+        if isinstance(lag, bool) or not isinstance(lag, int) or not 0 <= lag <= PROSODY_MAX_LAG:
+            raise SystemExit(f"--prosody_max_lag {lag!r}: a count of frames in 0..{PROSODY_MAX_LAG}")
     if int(settings.get("n_iter", 32)) < 0:
         raise SystemExit(f"--n_iter {settings.get('n_iter')}: a count of iterations, 0 or more")
     if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
