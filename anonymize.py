@@ -5,7 +5,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
-        [--report_prosody true [--prosody_max_lag K]]
+        [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
 normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
@@ -64,6 +64,14 @@ before or after the input) and ``f0_dev_st`` (the standard deviation of the per-
 when fewer than 8 frames are voiced in both or a track does not move; ``f0_shift_st``, ``f0_lag_frames``,
 ``f0_common_frames`` and ``voicing_agreement``; and ``f0_corr_mean``, ``f0_dev_st_mean``, ``voicing_agreement_mean``
 and ``prosody_scored`` in the final object.
+
+``--report_mcd true [--mcd_band R] [--mcd_order K]`` adds, in any mode, how far the timbre of every waveform written
+lies from its input's (speech_anonymization_amd.metrics.mel_cepstral_distortion, ops.mcd): the
+mel-cepstral distortion in dB over the coefficients 1..K (default 13) of the two log-Mel spectra, along a
+dynamic-time-warping alignment that may move up to R frames (default 16, at most 63) off the diagonal, over their
+common width.  Per utterance ``mcd_db``, ``mcd_sync_db`` (the same figure frame against frame, without an alignment;
+both null when the utterance could not be scored) and ``mcd_frames`` (the frames of both, 0 when not scored);
+``mcd_mean``, ``mcd_sync_mean`` and ``mcd_scored`` in the final object.
 
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the
@@ -189,6 +197,42 @@ class _ProsodyReport:
                 "voicing_agreement_mean": tot["voicing_agreement"], "prosody_scored": tot["scored"]}
 
 
+class _McdReport:
+    """--report_mcd true: the mel-cepstral distortion of every waveform about to be written against the input"""
+
+    def __init__(self, settings):
+        self.on = bool(settings.get("report_mcd"))
+        self.band = int(settings.get("mcd_band", vocoder.MCD_BAND_DEFAULT))
+        self.order = int(settings.get("mcd_order", vocoder.MCD_ORDER_DEFAULT))
+        self.stats = metrics.CepstralStats()
+        self.rows = None
+
+    def score(self, ids, wavs, lens, out, counts):
+        """wavs, out [B, *] on the device, lens the relative lengths, counts the samples written per row"""
+        if not self.on:
+            return
+        width = min(wavs.shape[1], out.shape[1])
+        n_in = [int(round(float(v) * wavs.shape[1])) for v in lens]
+        nv = torch.tensor([min(a, b, width) for a, b in zip(n_in, counts)], dtype=torch.int32).to(out.device)
+        m, sync, frames = metrics.mel_cepstral_distortion(wavs[:, :width], out[:, :width], nv, order=self.order,
+                                                          band=self.band)
+        self.stats.append(ids, m, sync, frames)
+        # (fp64 holds the fp32 and the int32 values exactly: one copy to the host)
+        self.rows = torch.stack([v.double() for v in (m, sync, frames)]).cpu().tolist()
+
+    def keys(self, i):
+        if not self.on:
+            return {}
+        m, sync, frames = (v[i] for v in self.rows)
+        return {"mcd_db": m if frames else None, "mcd_sync_db": sync if frames else None, "mcd_frames": int(frames)}
+
+    def summary(self):
+        if not self.on:
+            return {}
+        tot = self.stats.summarize()
+        return {"mcd_mean": tot["mcd"], "mcd_sync_mean": tot["mcd_sync"], "mcd_scored": tot["scored"]}
+
+
 def _counts(lens, N):
     return [int(round(float(v) * N)) for v in lens]
 
@@ -304,7 +348,7 @@ def main(argv):
     step, head, tail = MODES[vocoder.anonymize_mode(settings)](settings, device, bs, seed)
     f0m = pitchnorm.check_f0_option(settings)
     want_std = "contour_scale" in tail
-    utts, sto, pro = [], _StoiReport(settings), _ProsodyReport(settings, **f0m)
+    utts, sto, pro, cep = [], _StoiReport(settings), _ProsodyReport(settings, **f0m), _McdReport(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
@@ -312,6 +356,7 @@ def main(argv):
         rep = _f0_report(out, lens, want_std=want_std, **f0m) if settings.get("report_f0") else None
         sto.score(ids, wavs, lens, out, counts)
         pro.score(ids, wavs, lens, out, counts)
+        cep.score(ids, wavs, lens, out, counts)
         out = out.cpu()
         for i, uid in enumerate(ids):
             sig = out[i, :counts[i]]
@@ -323,9 +368,10 @@ def main(argv):
                     utts[-1].update(f0_std_hz=rep[2][i])
             utts[-1].update(sto.keys(i))
             utts[-1].update(pro.keys(i))
+            utts[-1].update(cep.keys(i))
             data.write_audio(os.path.join(settings["out_dir"], f"{uid}.wav"), sig)
     print(json.dumps(dict({"out_dir": settings["out_dir"]}, **head, utterances=utts, **tail, **f0m, **sto.summary(),
-                          **pro.summary())))
+                          **pro.summary(), **cep.summary())))
 
 
 if __name__ == "__main__":

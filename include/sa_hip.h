@@ -773,6 +773,36 @@ int sa_f0_compare(const float* f0_ref, const float* f0_deg, const int* frames, i
                   int min_common, float* rho, int* lag, int* common, float* shift_st, float* dev_st, float* voicing,
                   void* stream);
 
+/* ---- mel-cepstral distortion scoring (sa_mcd.hip; ops.mcd): how far the spectral envelope of one
+ * utterance lies from another's, in dB, along a banded dynamic-time-warping alignment.  mel_ref [B][T_ref][n_mels],
+ * mel_deg [B][T_deg][n_mels] fp32, log-Mel power in dB (features.Fbank(...)(wav).clamped()); n_ref, n_deg [B] int32,
+ * clamped where they are read to N in [0, T_ref] and M in [0, T_deg]; order K: the cepstral coefficients 1..K,
+ * 1 <= K <= 32, K < n_mels; band R in 0..63.  A frame at or beyond its row's count is never read into a result.
+ * Everything in fp64 on the fp32 inputs:
+ *   cepstra   c_k(t) = (1 / n_mels) sum_m mel[t][m] cos(pi k (m + 1/2) / n_mels), k = 1..K.  c_0 is left out: a gain
+ *             change costs nothing.
+ *   distance  d(i, j) = sqrt(1/2 sum_k (c_k^ref(i) - c_k^deg(j))^2) -- (10 / ln 10) sqrt(2 sum dc^2) written for
+ *             cepstra of a dB power spectrum; in dB.
+ *   alignment Sakoe-Chiba band, symmetric step weights; only the cells with |i - j| <= R exist:
+ *             g(0, 0) = 2 d(0, 0);  g(i, j) = min(g(i-1, j-1) + 2 d(i, j), g(i-1, j) + d(i, j), g(i, j-1) + d(i, j)).
+ *   mcd       = g(N-1, M-1) / (N + M): the normaliser does not depend on the path, so the figure is a continuous
+ *             function of the inputs, ties between steps change nothing, and no path is traced back.
+ *   mcd_sync  = (1 / min(N, M)) sum_{i < min(N, M)} d(i, i): the figure without an alignment.
+ *   A row is scored iff N >= 1, M >= 1 and |N - M| <= R: frames = N + M.  Any other row gets mcd = mcd_sync = 0 and
+ *   frames = 0.  mcd, mcd_sync [B] fp32, each rounded once; frames [B] int32.
+ *   ws: the caller's, 8 B (K (T_ref + T_deg) + (R + 1) (T_ref + T_deg - 1)) bytes, 8-byte aligned (the cepstra of
+ *     both inputs and the distances of the band, by anti-diagonal); its contents mean nothing between calls.
+ *   Three launches on the given stream (cepstra, band, recurrence: one wave per row over the N + M - 1
+ *     anti-diagonals), one path for every T; no copy to the host, no synchronisation, no atomics, every sum in a fixed
+ *     order: the same bits on every run.
+ *   sa_mcd_dim(which): 0 the band limit 63, 1 the order limit 32, 2 the n_mels limit 128, 3 the T limit 104858 (the
+ *     frames of 2^24 samples); else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer, B < 1 or > 65535 (grid.y), T_ref or T_deg < 1 or > 104858, n_mels < 2
+ *     or > 128, order outside 1..32 or >= n_mels, band outside 0..63. */
+int sa_mcd_dim(int which);
+int sa_mcd(const float* mel_ref, const float* mel_deg, const int* n_ref, const int* n_deg, int B, int T_ref, int T_deg,
+           int n_mels, int order, int band, void* ws, float* mcd, float* mcd_sync, int* frames, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

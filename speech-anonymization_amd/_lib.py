@@ -128,6 +128,7 @@ SYMBOLS = [
     "sa_contour_dim", "sa_pitch_contour", "sa_pv_synth_map", "sa_env_warp_frames", "sa_pitch_resample_map",
     "sa_f0v_dim", "sa_f0_candidates", "sa_f0_viterbi",
     "sa_f0cmp_dim", "sa_f0_compare",
+    "sa_mcd_dim", "sa_mcd",
 ]
 
 _lib = None

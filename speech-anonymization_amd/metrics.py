@@ -105,3 +105,48 @@ class ProsodyStats:
         return {"f0_corr": float(self.rho_sum) / n if n else None, "f0_dev_st": float(self.dev_sum) / n if n else None,
                 "voicing_agreement": float(self.voicing_sum) / self.total if self.total else None, "scored": n,
                 "unscored": self.total - n}
+
+
+_fbank = {}
+
+
+def mel_cepstral_distortion(wav_ref, wav_deg, n_valid, order=13, band=16):
+    """wav_ref, wav_deg fp32 [B, N] at 16 kHz on the GPU, already at a common width; n_valid int [B], the samples of a
+    row that count -> (mcd fp32 [B], mcd_sync fp32 [B], frames int32 [B]) of ops.mcd: both go
+    through features.Fbank and its per-utterance clamp at amax - 80 dB, and the first n_valid // 160 + 1 frames of a
+    row, at most N // 160 + 1, are compared."""
+    from . import features, ops
+    dev = wav_ref.device
+    if dev not in _fbank:
+        _fbank[dev] = features.Fbank().to(dev)
+    mel_ref, mel_deg = (_fbank[dev](w.float().contiguous()).clamped().contiguous() for w in (wav_ref, wav_deg))
+    width = wav_ref.shape[1]
+    frames = (n_valid.to(dev) // features.HOP + 1).clamp(max=width // features.HOP + 1).to(torch.int32)
+    return ops.mcd(mel_ref, mel_deg, frames, frames, order=order, band=band)
+
+
+class CepstralStats:
+    """Mel-cepstral distortion of a set of utterances (ops.mcd), accumulated on the device: the
+    means are over the rows that could be scored (frames > 0); the others are counted apart."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.ids = []
+        self.mcd_sum, self.sync_sum, self.scored, self.total = 0.0, 0.0, 0, 0
+
+    def append(self, ids, mcd, mcd_sync, frames):
+        """ids: a sequence of B names; mcd, mcd_sync fp32 [B]; frames int [B] (tensors, on any one device)"""
+        ok = frames.detach() > 0
+        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+        self.ids.extend(ids)
+        self.mcd_sum = self.mcd_sum + torch.where(ok, mcd.detach().double(), zero).sum()
+        self.sync_sum = self.sync_sum + torch.where(ok, mcd_sync.detach().double(), zero).sum()
+        self.scored = self.scored + ok.sum()
+        self.total += int(ok.numel())
+
+    def summarize(self):
+        n = int(self.scored)
+        return {"mcd": float(self.mcd_sum) / n if n else None, "mcd_sync": float(self.sync_sum) / n if n else None,
+                "scored": n, "unscored": self.total - n}

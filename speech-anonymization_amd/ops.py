@@ -6,6 +6,7 @@ current torch stream.  Activations are channels-last [B, L, C] (see include/sa_h
 import collections
 import ctypes as C
 import functools
+import sys
 
 import torch
 
@@ -1431,3 +1432,56 @@ def f0_compare(f0_ref, f0_deg, frames, max_lag=8, min_common=8):
     L.check(L.load().sa_f0_compare(_f(f0_ref), _f(f0_deg), _f(frames), B, T, max_lag, min_common, _f(rho), _f(lag),
                                    _f(common), _f(shift), _f(sdev), _f(voicing), L.stream()), "sa_f0_compare")
     return rho, lag, common, shift, sdev, voicing
+
+
+# ---- mel-cepstral distortion scoring (csrc/sa_mcd.hip) ----
+_mcd_in = functools.partial(_aug_in, family="MCD")
+_mcd_dims = {"MCD_MAX_BAND": 0, "MCD_MAX_ORDER": 1, "MCD_MAX_MELS": 2, "MCD_MAX_T": 3}
+
+
+def __getattr__(name):
+    """MCD_MAX_BAND, MCD_MAX_ORDER, MCD_MAX_MELS, MCD_MAX_T: sa_mcd_dim(0..3), read from the library on first use"""
+    if name in _mcd_dims:
+        globals()[name] = L.load().sa_mcd_dim(_mcd_dims[name])
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def mcd_workspace(B, T_ref, T_deg, order, band, device):
+    """the workspace sa_mcd takes: 8 B (K (T_ref + T_deg) + (R + 1) (T_ref + T_deg - 1)) bytes"""
+    return torch.empty(B * (order * (T_ref + T_deg) + (band + 1) * (T_ref + T_deg - 1)), dtype=torch.float64,
+                       device=device)
+
+
+def mcd(mel_ref, mel_deg, n_ref, n_deg, order=13, band=16):
+    """mel_ref fp32 [B, T_ref, n_mels], mel_deg fp32 [B, T_deg, n_mels] (log-Mel power in dB: features.Fbank(...)(wav)
+    .clamped()), n_ref, n_deg int32 [B] (the frames of a row that count, clamped to [0, T]) -> (mcd fp32 [B], mcd_sync
+    fp32 [B], frames int32 [B]): the mel-cepstral distortion in dB over the coefficients 1..order along a
+    dynamic-time-warping alignment within a band of ``band`` frames, the same figure frame against frame, and
+    n_ref + n_deg.  A row with an empty input or with counts more than ``band`` apart gets three zeros.  Everything
+    stays on the device (sa_mcd)."""
+    if _mcd_in(mel_ref, "mel_ref").dim() != 3 or mel_ref.numel() == 0:
+        raise L.SaHipError(f"mel_ref: expected [B, T, n_mels] with B, T, n_mels >= 1, got {tuple(mel_ref.shape)}")
+    if _mcd_in(mel_deg, "mel_deg").dim() != 3 or mel_deg.numel() == 0:
+        raise L.SaHipError(f"mel_deg: expected [B, T, n_mels] with B, T, n_mels >= 1, got {tuple(mel_deg.shape)}")
+    (B, T_ref, n_mels), T_deg = mel_ref.shape, mel_deg.shape[1]
+    if (mel_deg.shape[0], mel_deg.shape[2]) != (B, n_mels):
+        raise L.SaHipError(f"mel_deg: expected [{B}, T, {n_mels}] as mel_ref has, got {tuple(mel_deg.shape)}")
+    _mcd_in(n_ref, "n_ref", torch.int32, (B,))
+    _mcd_in(n_deg, "n_deg", torch.int32, (B,))
+    this = sys.modules[__name__]
+    max_band, max_order, max_mels, max_t = (getattr(this, k) for k in _mcd_dims)
+    if B > GL_MAX_B or max(T_ref, T_deg) > max_t or not 2 <= n_mels <= max_mels:
+        raise L.SaHipError(f"mel_ref, mel_deg: B up to {GL_MAX_B} (a grid extent), T up to {max_t}, n_mels in "
+                           f"2..{max_mels}; got B = {B}, T = {T_ref} and {T_deg}, n_mels = {n_mels}")
+    if isinstance(order, bool) or isinstance(band, bool) or not isinstance(order, int) or not isinstance(band, int) \
+            or not 1 <= order <= max_order or order >= n_mels or not 0 <= band <= max_band:
+        raise L.SaHipError(f"mcd: order in 1..{max_order} and below n_mels = {n_mels}, band in 0..{max_band} expected, "
+                           f"got {order!r} and {band!r}")
+    dev = mel_ref.device
+    out, sync = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(2))
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = mcd_workspace(B, T_ref, T_deg, order, band, dev)
+    L.check(L.load().sa_mcd(_f(mel_ref), _f(mel_deg), _f(n_ref), _f(n_deg), B, T_ref, T_deg, n_mels, order, band,
+                            _f(ws), _f(out), _f(sync), _f(frames), L.stream()), "sa_mcd")
+    return out, sync, frames

@@ -155,6 +155,8 @@ def invert_features(feats, normalizer, lens=None, frames=None, return_magnitude=
 
 ANON_MODEL_TYPES = ("convae", "fcae", "endtoend")
 PROSODY_MAX_LAG, PROSODY_LAG_DEFAULT = 32, 8                # ops.F0CMP_MAX_LAG; --prosody_max_lag
+MCD_MAX_BAND, MCD_BAND_DEFAULT = 63, 16                     # ops.MCD_MAX_BAND; --mcd_band
+MCD_MAX_ORDER, MCD_ORDER_DEFAULT = 32, 13                   # ops.MCD_MAX_ORDER; --mcd_order
 # the two modes that re-synthesise the waveform they are given: their flag and what they write
 RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
                  "formant_shift": ("--formant_ratio", "formant-shifted")}
@@ -249,6 +251,20 @@ def check_anonymize_options(settings, run_opts, environ=None):
             raise SystemExit("--prosody_max_lag needs --report_prosody true: nothing else compares two pitch tracks")
         if isinstance(lag, bool) or not isinstance(lag, int) or not 0 <= lag <= PROSODY_MAX_LAG:
             raise SystemExit(f"--prosody_max_lag {lag!r}: a count of frames in 0..{PROSODY_MAX_LAG}")
+    if settings.get("report_mcd") is not None:              # (any mode, 16 kHz only)
+        if not isinstance(settings["report_mcd"], bool):
+            raise SystemExit(f"--report_mcd {settings['report_mcd']!r}: true or false")
+        if settings["report_mcd"] and int(settings.get("sample_rate", 16000)) != 16000:
+            raise SystemExit("--report_mcd true scores 16 kHz waveforms only")
+    for key, lo, hi, what in (("mcd_band", 0, MCD_MAX_BAND, "a count of frames"),
+                              ("mcd_order", 1, MCD_MAX_ORDER, "a count of cepstral coefficients")):
+        val = settings.get(key)
+        if val is None:
+            continue
+        if not settings.get("report_mcd"):
+            raise SystemExit(f"--{key} needs --report_mcd true: nothing else compares two spectral envelopes")
+        if isinstance(val, bool) or not isinstance(val, int) or not lo <= val <= hi:
+            raise SystemExit(f"--{key} {val!r}: {what} in {lo}..{hi}")
     if int(settings.get("n_iter", 32)) < 0:
         raise SystemExit(f"--n_iter {settings.get('n_iter')}: a count of iterations, 0 or more")
     if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""What each signal-processing baseline costs in intelligibility and does to the pitch, on the synthetic set:
-anonymize.py --synthetic N --report_stoi true --report_f0 true once per mode, each a fresh child process, and per
-mode the mean STOI, ESTOI, voiced-mean F0 and voiced share of what it wrote.
+"""What each signal-processing baseline costs in intelligibility, does to the pitch and moves in the spectral
+envelope, on the synthetic set: anonymize.py --synthetic N --report_stoi true --report_f0 true --report_mcd true once
+per mode, each a fresh child process, and per mode the mean STOI, ESTOI, voiced-mean F0 and voiced share of what it
+wrote and its mean mel-cepstral distortion from the input in dB, along the alignment (mcd) and
+frame against frame (mcd_sync).
 
   passthrough             the vocoder alone: Fbank -> Mel pseudo-inverse -> Griffin-Lim of the original features
   pitch_norm              pitch normalisation to 170 Hz
@@ -55,7 +57,8 @@ def main():
             r = subprocess.run([sys.executable, os.path.join(ROOT, "anonymize.py"),
                                 os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", a.device,
                                 "--synthetic", str(a.synthetic), "--batch_size", str(a.batch_size), "--out_dir",
-                                os.path.join(tmp, name), "--report_stoi", "true", "--report_f0", "true"] + flags,
+                                os.path.join(tmp, name), "--report_stoi", "true", "--report_f0", "true",
+                                "--report_mcd", "true"] + flags,
                                cwd=ROOT, capture_output=True, text=True, timeout=a.timeout)
             if r.returncode != 0:
                 raise SystemExit(f"{name}: anonymize.py ended with {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
@@ -64,7 +67,8 @@ def main():
             table[name] = {"stoi": res["stoi_mean"], "estoi": res["estoi_mean"],
                            "scored": sum(1 for u in utts if u["stoi_segments"] > 0), "utterances": len(utts),
                            "f0_mean_hz": _mean([u["f0_mean_hz"] for u in utts if u["voiced_share"] > 0]),
-                           "voiced_share": _mean([u["voiced_share"] for u in utts])}
+                           "voiced_share": _mean([u["voiced_share"] for u in utts]),
+                           "mcd": res["mcd_mean"], "mcd_sync": res["mcd_sync_mean"], "mcd_scored": res["mcd_scored"]}
     line = json.dumps({"synthetic": a.synthetic, "modes": table})
     print(line)
     if a.out:
