@@ -50,103 +50,88 @@ class SimilarityMetricsStats:
         return self.summary["average"]
 
 
-class IntelligibilityStats:
-    """STOI / ESTOI of a set of utterances (ops.stoi), accumulated on the device: the means are
-    over the rows that could be scored (segments > 0); the others are counted apart."""
+class _GatedMeans:
+    """Per-utterance scores of a set of utterances, accumulated on the device in fp64: the columns named in ``gated``
+    are averaged over the rows that could be scored (gate > 0), those in ``ungated`` over all rows; the rows that
+    could not be scored are counted apart.  summarize() gives one key per column, then scored and unscored."""
+    gated, ungated = (), ()
 
     def __init__(self):
         self.clear()
 
     def clear(self):
         self.ids = []
-        self.stoi_sum, self.estoi_sum, self.scored, self.total = 0.0, 0.0, 0, 0
+        self.sums, self.scored, self.total = dict.fromkeys(self.gated + self.ungated, 0.0), 0, 0
+
+    def _add(self, ids, gate, *columns):
+        """gate int [B]; columns fp32 [B], the gated ones and then the ungated ones (tensors, on any one device)"""
+        ok = gate.detach() > 0
+        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
+        self.ids.extend(ids)
+        for name, v in zip(self.sums, columns):
+            v = v.detach().double()
+            self.sums[name] = self.sums[name] + (torch.where(ok, v, zero) if name in self.gated else v).sum()
+        self.scored = self.scored + ok.sum()
+        self.total += int(ok.numel())
+
+    def summarize(self):
+        n = int(self.scored)
+        return dict({name: float(v) / d if d else None for name, v in self.sums.items()
+                     for d in (n if name in self.gated else self.total,)}, scored=n, unscored=self.total - n)
+
+
+class IntelligibilityStats(_GatedMeans):
+    """STOI / ESTOI of a set of utterances (ops.stoi): the means over the rows with segments > 0"""
+    gated = ("stoi", "estoi")
 
     def append(self, ids, stoi, estoi, segments):
         """ids: a sequence of B names; stoi, estoi fp32 [B]; segments int [B] (tensors, on any one device)"""
-        ok = segments.detach() > 0
-        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
-        self.ids.extend(ids)
-        self.stoi_sum = self.stoi_sum + torch.where(ok, stoi.detach().double(), zero).sum()
-        self.estoi_sum = self.estoi_sum + torch.where(ok, estoi.detach().double(), zero).sum()
-        self.scored = self.scored + ok.sum()
-        self.total += int(ok.numel())
-
-    def summarize(self):
-        n = int(self.scored)
-        return {"stoi": float(self.stoi_sum) / n if n else None, "estoi": float(self.estoi_sum) / n if n else None,
-                "scored": n, "unscored": self.total - n}
+        self._add(ids, segments, stoi, estoi)
 
 
-class ProsodyStats:
-    """Pitch correlation of a set of utterances (ops.f0_compare), accumulated on the device: the
-    means of the correlation and of the deviation are over the rows that could be scored (common > 0), the mean of
-    the voicing agreement over all rows."""
-
-    def __init__(self):
-        self.clear()
-
-    def clear(self):
-        self.ids = []
-        self.rho_sum, self.dev_sum, self.voicing_sum, self.scored, self.total = 0.0, 0.0, 0.0, 0, 0
+class ProsodyStats(_GatedMeans):
+    """Pitch correlation of a set of utterances (ops.f0_compare): the means of the correlation and
+    of the deviation over the rows with common > 0, the mean of the voicing agreement over all rows"""
+    gated, ungated = ("f0_corr", "f0_dev_st"), ("voicing_agreement",)
 
     def append(self, ids, rho, common, dev_st, voicing):
         """ids: a sequence of B names; rho, dev_st, voicing fp32 [B]; common int [B] (tensors, on any one device)"""
-        ok = common.detach() > 0
-        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
-        self.ids.extend(ids)
-        self.rho_sum = self.rho_sum + torch.where(ok, rho.detach().double(), zero).sum()
-        self.dev_sum = self.dev_sum + torch.where(ok, dev_st.detach().double(), zero).sum()
-        self.voicing_sum = self.voicing_sum + voicing.detach().double().sum()
-        self.scored = self.scored + ok.sum()
-        self.total += int(ok.numel())
+        self._add(ids, common, rho, dev_st, voicing)
 
-    def summarize(self):
-        n = int(self.scored)
-        return {"f0_corr": float(self.rho_sum) / n if n else None, "f0_dev_st": float(self.dev_sum) / n if n else None,
-                "voicing_agreement": float(self.voicing_sum) / self.total if self.total else None, "scored": n,
-                "unscored": self.total - n}
+
+class CepstralStats(_GatedMeans):
+    """Mel-cepstral distortion of a set of utterances (ops.mcd): the means over the rows with
+    frames > 0"""
+    gated = ("mcd", "mcd_sync")
+
+    def append(self, ids, mcd, mcd_sync, frames):
+        """ids: a sequence of B names; mcd, mcd_sync fp32 [B]; frames int [B] (tensors, on any one device)"""
+        self._add(ids, frames, mcd, mcd_sync)
+
+
+def frame_counts(n_valid, width):
+    """n_valid int32 [B], the samples of a row that count, of ``width`` -> the Fbank frames that count, int32 [B]"""
+    from . import features
+    return (n_valid // features.HOP + 1).clamp(max=width // features.HOP + 1).to(torch.int32)
 
 
 _fbank = {}
 
 
+def log_mels(*wavs):
+    """wavs [B, N] at 16 kHz on one GPU -> their log-Mel spectra through features.Fbank and its per-utterance clamp at
+    amax - 80 dB, contiguous"""
+    from . import features
+    dev = wavs[0].device
+    if dev not in _fbank:
+        _fbank[dev] = features.Fbank().to(dev)
+    return tuple(_fbank[dev](w.float().contiguous()).clamped().contiguous() for w in wavs)
+
+
 def mel_cepstral_distortion(wav_ref, wav_deg, n_valid, order=13, band=16):
     """wav_ref, wav_deg fp32 [B, N] at 16 kHz on the GPU, already at a common width; n_valid int [B], the samples of a
     row that count -> (mcd fp32 [B], mcd_sync fp32 [B], frames int32 [B]) of ops.mcd: both go
-    through features.Fbank and its per-utterance clamp at amax - 80 dB, and the first n_valid // 160 + 1 frames of a
-    row, at most N // 160 + 1, are compared."""
-    from . import features, ops
-    dev = wav_ref.device
-    if dev not in _fbank:
-        _fbank[dev] = features.Fbank().to(dev)
-    mel_ref, mel_deg = (_fbank[dev](w.float().contiguous()).clamped().contiguous() for w in (wav_ref, wav_deg))
-    width = wav_ref.shape[1]
-    frames = (n_valid.to(dev) // features.HOP + 1).clamp(max=width // features.HOP + 1).to(torch.int32)
-    return ops.mcd(mel_ref, mel_deg, frames, frames, order=order, band=band)
-
-
-class CepstralStats:
-    """Mel-cepstral distortion of a set of utterances (ops.mcd), accumulated on the device: the
-    means are over the rows that could be scored (frames > 0); the others are counted apart."""
-
-    def __init__(self):
-        self.clear()
-
-    def clear(self):
-        self.ids = []
-        self.mcd_sum, self.sync_sum, self.scored, self.total = 0.0, 0.0, 0, 0
-
-    def append(self, ids, mcd, mcd_sync, frames):
-        """ids: a sequence of B names; mcd, mcd_sync fp32 [B]; frames int [B] (tensors, on any one device)"""
-        ok = frames.detach() > 0
-        zero = torch.zeros((), dtype=torch.float64, device=ok.device)
-        self.ids.extend(ids)
-        self.mcd_sum = self.mcd_sum + torch.where(ok, mcd.detach().double(), zero).sum()
-        self.sync_sum = self.sync_sum + torch.where(ok, mcd_sync.detach().double(), zero).sum()
-        self.scored = self.scored + ok.sum()
-        self.total += int(ok.numel())
-
-    def summarize(self):
-        n = int(self.scored)
-        return {"mcd": float(self.mcd_sum) / n if n else None, "mcd_sync": float(self.sync_sum) / n if n else None,
-                "scored": n, "unscored": self.total - n}
+    through log_mels, and the first n_valid // 160 + 1 frames of a row, at most N // 160 + 1, are compared."""
+    from . import ops
+    frames = frame_counts(n_valid.to(wav_ref.device), wav_ref.shape[1])
+    return ops.mcd(*log_mels(wav_ref, wav_deg), frames, frames, order=order, band=band)

@@ -297,9 +297,10 @@ def given_options(keys, settings, block=None):
     return {k: v for k in keys for v in (settings.get(k, block.get(k)),) if v is not None}
 
 
-def check_option(key, value):
-    """``value`` of the option ``key`` -> as the classes take it (a float where it is real), or the option's one line"""
-    o = OPTIONS[key]
+def check_option(key, value, options=OPTIONS):
+    """``value`` of the option ``key`` -> as the classes take it (a float where it is real), or the option's one line;
+    options: the table its row is in"""
+    o = options[key]
     if o.kind == "bool":
         ok = isinstance(value, bool)
     elif o.kind == "choice":

@@ -6,6 +6,7 @@ padding).  Three kernels of csrc/sa_vocoder.hip, 2 n_iter + 1 launches for the l
 
 The starting phases are drawn on the host from a ``torch.Generator`` the module owns (the project's plan convention:
 no device RNG, nothing copied back).  Tables are made in fp64 and rounded once."""
+import collections
 import functools
 
 import numpy as np
@@ -154,9 +155,36 @@ def invert_features(feats, normalizer, lens=None, frames=None, return_magnitude=
 
 
 ANON_MODEL_TYPES = ("convae", "fcae", "endtoend")
+# the reports' bounds and defaults, literals because the options are checked before anything loads the library: what
+# REPORT_OPTIONS refuses by and reports.REPORTS defaults to (the GPU tests hold them to sa_f0cmp_dim and sa_mcd_dim)
 PROSODY_MAX_LAG, PROSODY_LAG_DEFAULT = 32, 8                # ops.F0CMP_MAX_LAG; --prosody_max_lag
 MCD_MAX_BAND, MCD_BAND_DEFAULT = 63, 16                     # ops.MCD_MAX_BAND; --mcd_band
 MCD_MAX_ORDER, MCD_ORDER_DEFAULT = 32, 13                   # ops.MCD_MAX_ORDER; --mcd_order
+# the reports' options (reports.REPORTS) in the order they are checked, rows in the style of pitchnorm.OPTIONS.  A
+# flag's ``does`` is what the report does with 16 kHz waveforms only; a dependent option names the flag it needs
+# (``owner``) and what nothing else ``does``
+ReportOption = collections.namedtuple("ReportOption", "flag kind low high text fmt owner does")
+
+
+def _report_flag(key, does):
+    return ReportOption(f"--{key}", "bool", None, None, "true or false", "{!r}", None, does)
+
+
+def _report_count(key, low, high, what, owner, does):
+    return ReportOption(f"--{key}", "count", low, high, f"{what} in {low}..{high}", "{!r}", owner, does)
+
+
+REPORT_OPTIONS = {
+    "report_stoi": _report_flag("report_stoi", "scores"),
+    "report_prosody": _report_flag("report_prosody", "tracks the pitch of"),
+    "prosody_max_lag": _report_count("prosody_max_lag", 0, PROSODY_MAX_LAG, "a count of frames", "report_prosody",
+                                     "compares two pitch tracks"),
+    "report_mcd": _report_flag("report_mcd", "scores"),
+    "mcd_band": _report_count("mcd_band", 0, MCD_MAX_BAND, "a count of frames", "report_mcd",
+                              "compares two spectral envelopes"),
+    "mcd_order": _report_count("mcd_order", 1, MCD_MAX_ORDER, "a count of cepstral coefficients", "report_mcd",
+                               "compares two spectral envelopes"),
+}
 # the two modes that re-synthesise the waveform they are given: their flag and what they write
 RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
                  "formant_shift": ("--formant_ratio", "formant-shifted")}
@@ -235,36 +263,15 @@ def check_anonymize_options(settings, run_opts, environ=None):
         raise SystemExit("--csv FILE and --synthetic N exclude each other")
     if not settings.get("csv") and not settings.get("synthetic"):
         raise SystemExit("one of --csv FILE and --synthetic N is required")
-    if settings.get("report_stoi") is not None:             # (any mode, 16 kHz only)
-        if not isinstance(settings["report_stoi"], bool):
-            raise SystemExit(f"--report_stoi {settings['report_stoi']!r}: true or false")
-        if settings["report_stoi"] and int(settings.get("sample_rate", 16000)) != 16000:
-            raise SystemExit("--report_stoi true scores 16 kHz waveforms only")
-    if settings.get("report_prosody") is not None:          # (any mode, 16 kHz only)
-        if not isinstance(settings["report_prosody"], bool):
-            raise SystemExit(f"--report_prosody {settings['report_prosody']!r}: true or false")
-        if settings["report_prosody"] and int(settings.get("sample_rate", 16000)) != 16000:
-            raise SystemExit("--report_prosody true tracks the pitch of 16 kHz waveforms only")
-    if settings.get("prosody_max_lag") is not None:
-        lag = settings["prosody_max_lag"]
-        if not settings.get("report_prosody"):
-            raise SystemExit("--prosody_max_lag needs --report_prosody true: nothing else compares two pitch tracks")
-        if isinstance(lag, bool) or not isinstance(lag, int) or not 0 <= lag <= PROSODY_MAX_LAG:
-            raise SystemExit(f"--prosody_max_lag {lag!r}: a count of frames in 0..{PROSODY_MAX_LAG}")
-    if settings.get("report_mcd") is not None:              # (any mode, 16 kHz only)
-        if not isinstance(settings["report_mcd"], bool):
-            raise SystemExit(f"--report_mcd {settings['report_mcd']!r}: true or false")
-        if settings["report_mcd"] and int(settings.get("sample_rate", 16000)) != 16000:
-            raise SystemExit("--report_mcd true scores 16 kHz waveforms only")
-    for key, lo, hi, what in (("mcd_band", 0, MCD_MAX_BAND, "a count of frames"),
-                              ("mcd_order", 1, MCD_MAX_ORDER, "a count of cepstral coefficients")):
+    for key, o in REPORT_OPTIONS.items():                   # (DESIGN sections 18, 22, 23: any mode, 16 kHz only)
         val = settings.get(key)
         if val is None:
             continue
-        if not settings.get("report_mcd"):
-            raise SystemExit(f"--{key} needs --report_mcd true: nothing else compares two spectral envelopes")
-        if isinstance(val, bool) or not isinstance(val, int) or not lo <= val <= hi:
-            raise SystemExit(f"--{key} {val!r}: {what} in {lo}..{hi}")
+        if o.owner and not settings.get(o.owner):
+            raise SystemExit(f"{o.flag} needs --{o.owner} true: nothing else {o.does}")
+        pitchnorm.check_option(key, val, REPORT_OPTIONS)
+        if not o.owner and val and int(settings.get("sample_rate", 16000)) != 16000:
+            raise SystemExit(f"{o.flag} true {o.does} 16 kHz waveforms only")
     if int(settings.get("n_iter", 32)) < 0:
         raise SystemExit(f"--n_iter {settings.get('n_iter')}: a count of iterations, 0 or more")
     if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:

@@ -198,8 +198,9 @@ def test_entry_point_refuses_before_it_launches():
 
 @gpu
 def test_binding_refuses_before_it_launches(monkeypatch):
-    from speech_anonymization_amd import _lib, ops
+    from speech_anonymization_amd import _lib, ops, vocoder
     real = _lib.load()
+    assert (vocoder.MCD_MAX_BAND, vocoder.MCD_MAX_ORDER) == (real.sa_mcd_dim(0), real.sa_mcd_dim(1))
 
     class NoLaunch:
         def __getattr__(self, name):
@@ -243,42 +244,22 @@ def test_binding_refuses_before_it_launches(monkeypatch):
 # ---------------------------------------------------------------------------------------------------
 # end to end: anonymize.py in fresh child processes
 # ---------------------------------------------------------------------------------------------------
-ROWS = ("glide", "vibrato")
+ROWS = anon_cli.ROWS
 UTT_KEYS = {"mcd_db", "mcd_sync_db", "mcd_frames"}
 SUM_KEYS = {"mcd_mean", "mcd_sync_mean", "mcd_scored"}
-
-
-def _manifest(tmp_path):
-    """the glide and the vibrato row as 16-bit files and a four-column manifest -> its path"""
-    from speech_anonymization_amd import data
-    from tests import contour_ref as Cr
-    wav = Cr.case_rows()
-    lines = ["ID,duration,wav,gender"]
-    for name, row in zip(ROWS, wav):
-        path = tmp_path / f"{name}.wav"
-        data.write_audio(str(path), row)
-        lines.append(f"{name},{row.shape[0] / 16000.0},{path},M")
-    csv = tmp_path / "rows.csv"
-    csv.write_text("\n".join(lines) + "\n")
-    return str(csv)
-
-
-def _child(tmp_path, name, extra):
-    res = anon_cli.run_child(["--device", DEV, "--csv", _manifest(tmp_path), "--out_dir", str(tmp_path / name)] + extra)
-    return res, {u["id"]: u for u in res["utterances"]}
 
 
 @gpu
 def test_anonymize_reports_an_identity(tmp_path):
     """--mcadams 1.0 copies every row bit for bit: the two spectra are the same"""
-    res, utts = _child(tmp_path, "on", ["--mcadams", "1.0", "--report_mcd", "true"])
+    res, utts = anon_cli.child(tmp_path, "on", ["--mcadams", "1.0", "--report_mcd", "true"])
     assert sorted(utts) == sorted(ROWS)
     for u in utts.values():
         assert UTT_KEYS <= set(u)
         assert u["mcd_db"] == 0.0 == u["mcd_sync_db"] and u["mcd_frames"] > 200
     assert SUM_KEYS <= set(res)
     assert res["mcd_mean"] == 0.0 and res["mcd_sync_mean"] == 0.0 and res["mcd_scored"] == 2
-    plain, putts = _child(tmp_path, "off", ["--mcadams", "1.0"])
+    plain, putts = anon_cli.child(tmp_path, "off", ["--mcadams", "1.0"])
     assert not SUM_KEYS & set(plain) and not any(UTT_KEYS & set(u) for u in putts.values())
     assert sorted(putts) == sorted(utts)
 
@@ -287,8 +268,8 @@ def test_anonymize_reports_an_identity(tmp_path):
 def test_anonymize_reports_a_moved_envelope(tmp_path):
     """--formant_ratio 1.15 --phase vocoder: the envelope moves, and at equal counts an alignment cannot cost more
     than none.  No absolute figure is asserted: synthetic glides say nothing about speech."""
-    res, utts = _child(tmp_path, "f", ["--formant_ratio", "1.15", "--phase", "vocoder", "--report_mcd", "true",
-                                       "--mcd_band", "16", "--mcd_order", "13"])
+    res, utts = anon_cli.child(tmp_path, "f", ["--formant_ratio", "1.15", "--phase", "vocoder", "--report_mcd", "true",
+                                               "--mcd_band", "16", "--mcd_order", "13"])
     for name in ROWS:
         u = utts[name]
         print(f"formant_ratio 1.15 {name}: mcd_db {u['mcd_db']!r} mcd_sync_db {u['mcd_sync_db']!r} frames "

@@ -136,8 +136,9 @@ def test_identical_tracks_score_exactly_one():
 @gpu
 def test_entry_point_and_binding_refuse():
     """only arguments the library rejects before launching: -EINVAL, and the poisoned outputs untouched"""
-    from speech_anonymization_amd import _lib, ops
+    from speech_anonymization_amd import _lib, ops, vocoder
     lib, E = _lib.load(), -errno.EINVAL
+    assert vocoder.PROSODY_MAX_LAG == lib.sa_f0cmp_dim(1)
     B, T = 2, 61
     ref = torch.full((B, T), 150.0, device=DEV)
     fr = torch.full((B,), T, dtype=torch.int32, device=DEV)
@@ -174,35 +175,15 @@ def test_entry_point_and_binding_refuse():
 # ---------------------------------------------------------------------------------------------------
 # end to end: anonymize.py in fresh child processes
 # ---------------------------------------------------------------------------------------------------
-ROWS = ("glide", "vibrato")
+ROWS = anon_cli.ROWS
 UTT_KEYS = {"f0_corr", "f0_dev_st", "f0_shift_st", "f0_lag_frames", "f0_common_frames", "voicing_agreement"}
 SUM_KEYS = {"f0_corr_mean", "f0_dev_st_mean", "voicing_agreement_mean", "prosody_scored"}
-
-
-def _manifest(tmp_path):
-    """the glide and the vibrato row as 16-bit files and a four-column manifest -> its path"""
-    from speech_anonymization_amd import data
-    from tests import contour_ref as Cr
-    wav = Cr.case_rows()
-    lines = ["ID,duration,wav,gender"]
-    for name, row in zip(ROWS, wav):
-        path = tmp_path / f"{name}.wav"
-        data.write_audio(str(path), row)
-        lines.append(f"{name},{row.shape[0] / 16000.0},{path},M")
-    csv = tmp_path / "rows.csv"
-    csv.write_text("\n".join(lines) + "\n")
-    return str(csv)
-
-
-def _child(tmp_path, name, extra):
-    res = anon_cli.run_child(["--device", DEV, "--csv", _manifest(tmp_path), "--out_dir", str(tmp_path / name)] + extra)
-    return res, {u["id"]: u for u in res["utterances"]}
 
 
 @gpu
 def test_anonymize_reports_an_identity(tmp_path):
     """--mcadams 1.0 copies every row bit for bit: the two tracks are the same"""
-    res, utts = _child(tmp_path, "on", ["--mcadams", "1.0", "--report_prosody", "true"])
+    res, utts = anon_cli.child(tmp_path, "on", ["--mcadams", "1.0", "--report_prosody", "true"])
     assert sorted(utts) == sorted(ROWS)
     for u in utts.values():
         assert UTT_KEYS <= set(u)
@@ -211,14 +192,14 @@ def test_anonymize_reports_an_identity(tmp_path):
     assert SUM_KEYS <= set(res)
     assert res["f0_corr_mean"] == 1.0 and res["f0_dev_st_mean"] == 0.0 and res["voicing_agreement_mean"] == 1.0
     assert res["prosody_scored"] == 2
-    plain, putts = _child(tmp_path, "off", ["--mcadams", "1.0"])
+    plain, putts = anon_cli.child(tmp_path, "off", ["--mcadams", "1.0"])
     assert not SUM_KEYS & set(plain) and not any(UTT_KEYS & set(u) for u in putts.values())
     assert sorted(putts) == sorted(utts)
 
 
 def _contour_child(tmp_path, gamma):
-    res, utts = _child(tmp_path, "c", ["--pitch_norm", "true", "--phase", "vocoder", "--contour_scale", gamma,
-                                       "--report_prosody", "true"])
+    res, utts = anon_cli.child(tmp_path, "c", ["--pitch_norm", "true", "--phase", "vocoder", "--contour_scale", gamma,
+                                               "--report_prosody", "true"])
     want = R.E2E_MEASURED[gamma]
     for i, name in enumerate(ROWS):
         u = utts[name]

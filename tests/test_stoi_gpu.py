@@ -13,15 +13,13 @@ The bar, per score:   |score - ref| <= 16 x D + 2^-24 |ref|
 exact: tests/test_stoi_cpu.py checks that no frame energy of these rows lies within 1 +- 1e-6 of its threshold."""
 import ctypes
 import errno
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from tests import anon_cli
 from tests import stoi_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -176,12 +174,8 @@ def test_anonymize_reports_stoi(tmp_path):
     """one fresh child process: --mcadams 1.0 copies every row bit for bit, so every scored
     utterance reports 1 within the bar; the same command without the flag prints none of the new keys"""
     def run(extra):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "anonymize.py"),
-                            os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", DEV, "--synthetic",
-                            "4", "--mcadams", "1.0", "--out_dir", str(tmp_path / ("a" + str(len(extra))))] + extra,
-                           cwd=ROOT, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])
+        return anon_cli.run_child(["--device", DEV, "--synthetic", "4", "--mcadams", "1.0", "--out_dir",
+                                   str(tmp_path / ("a" + str(len(extra))))] + extra)
 
     res = run(["--report_stoi", "true"])
     assert len(res["utterances"]) == 4

@@ -6,10 +6,12 @@
 Every output tensor (the waveforms and ``last``) of PitchNormalizer over phase x formants x f0_method x contour, of
 FormantShifter in both phases and of McAdams with a fixed coefficient and with a range, each on
 data.synthetic_gender_dataset(6, 3) and on one batch of width 16037 (no multiple of the hop) with lens (1.0, 0.73,
-0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of six anonymize.py modes.
+0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of six anonymize.py modes,
+each with --report_f0 and --report_stoi (``anonymize/<mode>``) and with all four reports (``anonymize_reports/<mode>``).
 Prints one JSON object with one digest per transform and input (over the digests of its tensors, batch by batch) and
 one per mode (over its JSON line and its WAV files by name); ``--each`` prints every item's own digest instead, to find
-what differs.  profiles/anon_refactor_digest.json is its output."""
+what differs.  profiles/anon_reports_digest.json is its output; profiles/anon_refactor_digest.json the 62 groups it had
+before the second family."""
 import contextlib
 import hashlib
 import importlib.util
@@ -35,6 +37,10 @@ MODES = {"passthrough": ["--passthrough", "true"],
          "mcadams": ["--mcadams", "0.8"],
          "mcadams_range": ["--mcadams_min", "0.5", "--mcadams_max", "0.9"]}
 COMMON = ["--synthetic", "3", "--batch_size", "3", "--n_iter", "2", "--report_f0", "true", "--report_stoi", "true"]
+# family -> what its runs add to COMMON: the modes as they always ran, and with all four reports on
+FAMILIES = {"anonymize": [],
+            "anonymize_reports": ["--report_prosody", "true", "--report_mcd", "true", "--prosody_max_lag", "4",
+                                  "--mcd_band", "8", "--mcd_order", "12"]}
 
 
 def sha(t):
@@ -73,18 +79,18 @@ def anonymize_modes(device, res):
     spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    for name, argv in MODES.items():
+    for (family, more), (name, argv) in itertools.product(FAMILIES.items(), MODES.items()):
         with tempfile.TemporaryDirectory() as out:
             text = io.StringIO()
             with contextlib.redirect_stdout(text):
                 mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", device, "--out_dir",
-                          out] + COMMON + argv)
+                          out] + COMMON + more + argv)
             line = json.loads(text.getvalue().strip().splitlines()[-1])
             line["out_dir"] = name
-            res[f"anonymize/{name}/json"] = hashlib.sha256(json.dumps(line).encode()).hexdigest()
+            res[f"{family}/{name}/json"] = hashlib.sha256(json.dumps(line).encode()).hexdigest()
             for wav in sorted(os.listdir(out)):
                 with open(os.path.join(out, wav), "rb") as f:
-                    res[f"anonymize/{name}/{wav}"] = hashlib.sha256(f.read()).hexdigest()
+                    res[f"{family}/{name}/{wav}"] = hashlib.sha256(f.read()).hexdigest()
 
 
 def main(argv):
@@ -102,7 +108,7 @@ def main(argv):
     if "--each" not in argv:                                 # one digest per transform and input, one per mode
         groups = {}
         for key in sorted(res):
-            head = "/".join(key.split("/")[:2] if key.startswith("anonymize/") else key.split("/")[:-2])
+            head = "/".join(key.split("/")[:2] if key.startswith("anonymize") else key.split("/")[:-2])
             groups.setdefault(head, hashlib.sha256()).update(f"{key}={res[key]}\n".encode())
         res = {head: h.hexdigest() for head, h in groups.items()}
     text = json.dumps(res, indent=1, sort_keys=True) + "\n"

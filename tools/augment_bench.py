@@ -15,7 +15,6 @@ Device events around each call after a warm-up; the median of --steps calls.  Pr
 import argparse
 import json
 import os
-import statistics
 import sys
 import tempfile
 
@@ -24,21 +23,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
+from tools.bench_common import time_calls  # noqa: E402
 
 
 def torch_restatement(wav, lens, plan, noise, snr, first, w, h):

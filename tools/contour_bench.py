@@ -22,7 +22,6 @@ is that other figure).  Prints one JSON line (and writes it to --out):
   normalizer_vocoder_ms, normalizer_contour_ms, normalizer_contour_formants_ms   the whole call
   step_vocoder_ms, step_contour_ms      GenderPitchNormBrain.fit_batch on the same batch"""
 import argparse
-import json
 import math
 import os
 import statistics
@@ -33,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+from tools.bench_common import write_line  # noqa: E402
 
 SR, HOP, NBIN = 16000, 160, 201
 SHORT_REPS = 32                           # calls per sample of the entry points that take tens of microseconds
@@ -246,12 +246,7 @@ def main():
                 out[f"step_{name}_ms"] = tm(lambda: b.fit_batch(batch))
                 del b
                 torch.cuda.empty_cache()
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -9,34 +9,18 @@ Device events around each call after a warm-up; the median of --steps calls.  Al
 the two methods' f0 differ on data.synthetic_gender_dataset's utterances (its clean harmonic rows: no real speech).
 Prints one JSON line (and writes it to --out)."""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
 SR, HOP, TAU_MIN, TAU_MAX, K = 16000, 160, 40, 266, 8
 BIG = 1 << 40
 INF = 1 << 56
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def torch_candidates(dp):
@@ -129,12 +113,7 @@ def main():
     out["f0_track_yin_ms"] = tm(lambda: pitchnorm.f0_track(wav))
     out["torch_candidates_ms"] = tm(lambda: torch_candidates(dp))
     out["torch_viterbi_ms"] = tm(lambda: torch_viterbi(tau, q, lens, N, LOG, wq))
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

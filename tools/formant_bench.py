@@ -13,33 +13,17 @@ to --out):
                               PitchNormalizer(170) and PitchNormalizer(170, preserve_formants=True), the whole call
   formant_shifter_ms          FormantShifter(1.2), the whole call"""
 import argparse
-import json
 import math
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
 SR, HOP, N_FFT, K = 16000, 160, 400, 201
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def torch_tables(q, n_c, dev):
@@ -101,12 +85,7 @@ def main():
                      ("normalizer_preserve_ms", lambda: keep(wav, lens)),
                      ("formant_shifter_ms", lambda: shifter(wav, lens))):
         out[name] = round(time_calls(fn, a.warmup, a.steps), 4)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

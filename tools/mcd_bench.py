@@ -14,13 +14,13 @@ to --out):
   ref_rows_per_s                the fp64 restatement (tests/mcd_ref.py, numpy) on the host at band 16, over --ref_rows
                                 rows, and max_abs_diff_vs_ref over them
   stage_fbank_ms, stage_score_ms, stage_to_host_ms
-                                anonymize.py --report_mcd true at 32 x 10 s: the two feature passes with their clamp,
-                                the scoring as the script calls it (the frame counts, ops.mcd, the running means) and
-                                the one copy of the three result rows to the host"""
+                                anonymize.py --report_mcd true at 32 x 10 s: the two feature passes with their clamp
+                                (metrics.log_mels on the window of reports.Batch), the scoring on those spectra (the
+                                two steps that metrics.mel_cepstral_distortion takes after them, frame_counts and
+                                ops.mcd, and the report's collect, the running means) and the report's fetch, the one
+                                copy of the three result rows to the host"""
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -29,23 +29,9 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
 SR, HOP = 16000, 160
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def torch_mcd(mel_ref, mel_deg, n_ref, n_deg, order, band):
@@ -100,7 +86,7 @@ def main():
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
     import speech_anonymization_amd  # noqa: F401  (registers the package name)
-    from speech_anonymization_amd import features, metrics, ops
+    from speech_anonymization_amd import metrics, ops, reports
     from tests import mcd_ref as R
     B, T = a.B, a.T
     fields = [R.mel_field(T, 4000 + 2 * b) for b in range(B)]
@@ -136,28 +122,18 @@ def main():
     wav = torch.stack([Cr.glide_row(lambda t: 110.0 + 80.0 * t / (N / SR), N, g) for _ in range(2)]).float()
     wav = wav.repeat(B // 2 + 1, 1)[:B].to(dev).contiguous()
     out_wav = torch.roll(wav, 3 * HOP, 1).contiguous()
-    fb = features.Fbank().to(dev)
-    mels = lambda: tuple(fb(w).clamped().contiguous() for w in (wav, out_wav))
+    win = reports.Batch(wav, torch.ones(B), out_wav, [N] * B).window
+    mels = lambda: metrics.log_mels(win.ref, win.deg)
     m_ref, m_deg = mels()
-    ids, stats = [str(i) for i in range(B)], metrics.CepstralStats()
-    nv = torch.full((B,), N, dtype=torch.int32, device=dev)
+    ids, rep = [str(i) for i in range(B)], reports.Report("report_mcd", {})
 
     def score():
-        fr = (nv // HOP + 1).clamp(max=N // HOP + 1).to(torch.int32)
-        r = ops.mcd(m_ref, m_deg, fr, fr)
-        stats.append(ids, *r)
-        return r
+        fr = metrics.frame_counts(win.nv, win.width)
+        rep.collect(ids, ops.mcd(m_ref, m_deg, fr, fr, order=rep.opts["mcd_order"], band=rep.opts["mcd_band"]))
 
-    got = score()
-    for name, fn in (("stage_fbank_ms", mels), ("stage_score_ms", score),
-                     ("stage_to_host_ms", lambda: torch.stack([v.double() for v in got]).cpu().tolist())):
+    for name, fn in (("stage_fbank_ms", mels), ("stage_score_ms", score), ("stage_to_host_ms", rep.fetch)):
         res[name] = round(time_calls(fn, a.warmup, a.steps), 4)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

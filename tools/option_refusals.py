@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What the three public option checkers say, setting by setting: vocoder.check_anonymize_options,
 pitchnorm.check_pitch_options and mcadams.check_recipe_options are called on enumerated option settings, and each case
-is recorded as either the SystemExit text or the returned value.  No GPU.
+is recorded as either the SystemExit text or the returned value.  No GPU.  check_anonymize_options is walked twice:
+over the anonymisers' options ("anonymize") and over the reports' ("anonymize_reports").
 
     python tools/option_refusals.py [--full] [--out FILE]
 
@@ -9,7 +10,7 @@ The default walks every combination of at most three non-default settings; ``--f
 value sets below.  The output is one JSON object: "outcomes", the distinct {"exit": text} | {"return": value} in order
 of first appearance; per checker "outcome", the index into them of every case in the order walked, and
 "settings_sha256" over the walked settings (compact JSON, one per line), which pins that order; and "cases", the number
-walked.  tests/golden/option_refusals.json is the default walk at the commit before the checkers were rewritten;
+walked.  tests/golden/option_refusals.json is the default walk at the commits before the checkers were rewritten;
 tests/test_option_refusals_cpu.py holds the present code to it."""
 import hashlib
 import itertools
@@ -48,10 +49,22 @@ AXES = {
                            {"f0_method": "x", "r_max": 3.0}])] + RUN,
     "mcadams_recipe": MCADAMS + [
         (("mcadams_options",), [ABSENT, {"alpha_min": 0.6, "alpha_max": 0.7, "seed": 5}, {"alpha": 2.0}])] + RUN,
+    # the reports of anonymize.py: every flag, its dependent options, and what the flags are checked against
+    "anonymize_reports": [
+        (("report_stoi",), [ABSENT, True, "yes"]),
+        (("report_prosody",), [ABSENT, True, False, "yes"]),
+        (("prosody_max_lag",), [ABSENT, 4, 33, True]),
+        (("report_mcd",), [ABSENT, True, "yes"]),
+        (("mcd_band",), [ABSENT, 8, 64]),
+        (("mcd_order",), [ABSENT, 12, 0]),
+        (("sample_rate",), [ABSENT, 8000]),
+        (("f0_method",), [ABSENT, "viterbi"]),
+        (("mcadams",), [ABSENT, 0.8])],
 }
 BASE = {"anonymize": {"out_dir": "o", "synthetic": 2}, "pitch_recipe": {}, "mcadams_recipe": {}}
+BASE["anonymize_reports"] = BASE["anonymize"]
 CHECKERS = {"anonymize": vocoder.check_anonymize_options, "pitch_recipe": pitchnorm.check_pitch_options,
-            "mcadams_recipe": mcadams.check_recipe_options}
+            "mcadams_recipe": mcadams.check_recipe_options, "anonymize_reports": vocoder.check_anonymize_options}
 
 
 def choices(axes, full):

@@ -15,9 +15,7 @@ to --out):
   step_plain_ms, step_pitch_norm_ms
                          GenderBrain.fit_batch and GenderPitchNormBrain.fit_batch on the same batch"""
 import argparse
-import json
 import os
-import statistics
 import sys
 import tempfile
 
@@ -25,23 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
 SR, HOP, W, TAU_MIN, TAU_MAX = 16000, 160, 400, 40, 266
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def torch_yin(wav, threshold, chunk):
@@ -135,12 +119,7 @@ def main():
                 out[name] = round(time_calls(lambda: b.fit_batch(batch), a.warmup, a.steps), 4)
                 del b
                 torch.cuda.empty_cache()
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -10,13 +10,12 @@ to --out):
                                 max_abs_diff of its real outputs from sa_f0_compare's, lags_equal
   ref_rows_per_s                the fp64 restatement (tests/prosody_ref.py, numpy) on the host
   stage_track_ms, stage_compare_ms, stage_to_host_ms
-                                anonymize.py --report_prosody true: the two trackings, the comparison as the script
-                                calls it (the frame counts, ops.f0_compare, the running means) and the one copy of
-                                the six result rows to the host"""
+                                anonymize.py --report_prosody true: the two trackings (reports.f0_tracks on the
+                                window of reports.Batch), the comparison on those tracks (ops.f0_compare over the
+                                window's frame counts and the report's collect, the running means) and the report's
+                                fetch, the one copy of the six result rows to the host"""
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -24,23 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
-SR, HOP = 16000, 160
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
+SR = 16000
 
 
 def torch_compare(f_ref, f_deg, frames, max_lag=8, min_common=8):
@@ -107,18 +92,14 @@ def main():
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
     import speech_anonymization_amd  # noqa: F401  (registers the package name)
-    from speech_anonymization_amd import metrics, ops, pitchnorm
+    from speech_anonymization_amd import ops, pitchnorm, reports
     from tests import prosody_ref as R
     B, N = a.B, int(a.seconds * SR)
     wav, lens_cpu = glides(B, N).to(dev), torch.ones(B)
     out_wav = pitchnorm.PitchNormalizer(170.0, phase="vocoder", contour_scale=a.gamma)(wav, lens_cpu)
-    width = min(wav.shape[1], out_wav.shape[1])
-    rel = torch.ones(B, device=dev)
-    track = lambda: tuple(pitchnorm.f0_track(w[:, :width].float().contiguous(), method="yin", lens=rel)
-                          for w in (wav, out_wav))
-    f_in, f_out = track()
-    frames = torch.full((B,), width // HOP + 1, dtype=torch.int32, device=dev)
-
+    win = reports.Batch(wav, lens_cpu, out_wav, [out_wav.shape[1]] * B).window
+    track = lambda: reports.f0_tracks(win, "yin")
+    (f_in, f_out), frames = track(), win.frames
     got = ops.f0_compare(f_in, f_out, frames)
     ms = time_calls(lambda: ops.f0_compare(f_in, f_out, frames), a.warmup, a.steps)
     tor = torch_compare(f_in, f_out, frames)
@@ -137,25 +118,15 @@ def main():
                  for i, k in ((0, "rho"), (3, "shift_st"), (4, "dev_st"), (5, "voicing")))
     res["max_abs_diff_vs_ref"] = float(f"{vs_ref:.3e}")
 
-    ids = [str(i) for i in range(B)]
-    stats = metrics.ProsodyStats()
-    nv = torch.full((B,), width, dtype=torch.int32, device=dev)
+    ids, rep = [str(i) for i in range(B)], reports.Report("report_prosody", {})
 
-    def score():
-        fr = (nv // HOP + 1).clamp(max=width // HOP + 1).to(torch.int32)
-        r = ops.f0_compare(f_in, f_out, fr)
-        stats.append(ids, r[0], r[2], r[4], r[5])
-        return r
+    def score():                                            # (a fresh Window forms its frame counts, as every batch does)
+        fr = reports.Window(win.width, win.nv, win.ref, win.deg).frames
+        rep.collect(ids, ops.f0_compare(f_in, f_out, fr, max_lag=rep.opts["prosody_max_lag"]))
 
-    for name, fn in (("stage_track_ms", track), ("stage_compare_ms", score),
-                     ("stage_to_host_ms", lambda: torch.stack([v.double() for v in got]).cpu().tolist())):
+    for name, fn in (("stage_track_ms", track), ("stage_compare_ms", score), ("stage_to_host_ms", rep.fetch)):
         res[name] = round(time_calls(fn, a.warmup, a.steps), 4)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(res, a.out)
 
 
 if __name__ == "__main__":

@@ -15,7 +15,6 @@ to --out):
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,23 +22,9 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
+from tools.bench_common import time_calls  # noqa: E402
 
 REFERENCE = dict(freq_mask_width=30, time_mask_width=40, replace_with_zero=False)
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def torch_restatement(x, plan, fm, tm):

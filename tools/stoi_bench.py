@@ -11,12 +11,11 @@ to --out):
   ref_utts_per_s                the fp64 restatement (tests/stoi_ref.py, numpy) on the host, one row
   stage_transform_ms, stage_stoi_ms, stage_stoi_to_host_ms
                                 anonymize.py --mcadams 0.8 --report_stoi true: the transform, the scorer as the script
-                                calls it (slices, n_valid, ops.stoi, the running means) and the copy of the three
+                                calls it (reports.Batch's window, the report's scoring call and collect: slices,
+                                n_valid, ops.stoi, the running means) and the report's fetch, the one copy of the three
                                 result rows to the host"""
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -25,25 +24,11 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from tools.bench_common import time_calls, write_line  # noqa: E402
 
 SR = 16000
 BANDS = (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
 EPS = 2.0 ** -52
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
 
 
 def _unit(v, dim):
@@ -100,7 +85,7 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, mcadams, metrics, ops
+    from speech_anonymization_amd import data, mcadams, ops, reports
     from tests import stoi_ref as R
     B, N = a.B, int(a.seconds * SR)
     wav_cpu, lens_cpu = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N))).sig
@@ -125,25 +110,13 @@ def main():
     out["ref_utts_per_s"] = round(1.0 / (time.perf_counter() - t0), 2)
     out["max_abs_diff_vs_ref_first_row"] = float(f"{max(abs(float(s[0]) - ref.stoi[0]), abs(float(e[0]) - ref.estoi[0])):.3e}")
 
-    counts = [int(round(float(v) * N)) for v in lens_cpu]
-    ids = [str(i) for i in range(B)]
-    stats = metrics.IntelligibilityStats()
-
-    def score():
-        n = torch.tensor([min(c, N) for c in counts], dtype=torch.int32).to(dev)
-        r = ops.stoi(wav[:, :N].float().contiguous(), deg[:, :N].float().contiguous(), n)
-        stats.append(ids, r[0], r[1], r[3])
-        return r
-
+    counts, ids = [int(round(float(v) * N)) for v in lens_cpu], [str(i) for i in range(B)]
+    rep = reports.Report("report_stoi", {})
+    score = lambda: rep.collect(ids, rep.row.score(reports.Batch(wav, lens_cpu, deg, counts)))
     for name, fn in (("stage_transform_ms", lambda: mc(wav, lens_cpu)), ("stage_stoi_ms", score),
-                     ("stage_stoi_to_host_ms", lambda: (s.cpu().tolist(), e.cpu().tolist(), segments.cpu().tolist()))):
+                     ("stage_stoi_to_host_ms", rep.fetch)):
         out[name] = round(time_calls(fn, a.warmup, a.steps), 4)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    write_line(out, a.out)
 
 
 if __name__ == "__main__":

@@ -18,28 +18,13 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-
-
-def time_calls(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
+from tools.bench_common import time_calls  # noqa: E402
 
 
 def torch_loop(S, phi, n_iter, m, window):
