@@ -5,6 +5,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
+        [--psola true]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
@@ -43,6 +44,13 @@ mean) with a ratio per frame: 1 is the additive shift of the
 voice.  Every other mode refuses the option.  The JSON line then carries ``contour_scale`` and ``contour_smooth``, the
 utterances' ``ratio`` is the mean ratio of the row, and with ``--report_f0 true`` each utterance also gains
 ``f0_std_hz``, the standard deviation of the voiced F0 over the counted frames.
+
+``--pitch_norm true --psola true`` moves the pitch in the time domain (TD-PSOLA; speech_anonymization_amd.ops.psola;
+DESIGN section 24): the waveform is cut into two-period grains centred on pitch marks and the same grains are laid
+down again at the new spacing.  The spectral envelope and the duration stay by construction; there is no STFT, no
+phase, no iteration and no random number.  It takes ``--contour_scale G`` without ``--phase vocoder``, and none of
+--phase, --preserve_formants true, --formant_ratio and --lifter.  The JSON line then carries ``"psola": true`` and
+``"n_iter": null``.
 
 ``--f0_method viterbi`` tracks F0 with a Viterbi decode through every frame's d' dips (speech_anonymization_amd.
 pitchnorm.f0_track) instead of first-dip YIN (``yin``, the default).  With ``--pitch_norm true`` it
@@ -110,10 +118,11 @@ def _pitch_norm(settings, device, bs, seed):
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
     contour = pitchnorm.check_contour_options(settings)
+    psola = pitchnorm.check_psola_option(settings)
     pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)),
                                    n_iter=int(settings.get("n_iter", 32)),
                                    momentum=float(settings.get("momentum", 0.99)), seed=seed, **formant, **phase,
-                                   **contour, **pitchnorm.check_f0_option(settings))
+                                   **contour, **pitchnorm.check_f0_option(settings), **psola)
     if contour:
         contour = {"contour_scale": pn.contour_scale, "contour_smooth": pn.contour_smooth}
 
@@ -122,7 +131,7 @@ def _pitch_norm(settings, device, bs, seed):
         return out, _counts(lens, out.shape[1]), [{"ratio": r} for r in pn.last[0].cpu().tolist()], None
 
     return step, {"pitch_norm": True, "pitch_target_hz": pn.target_hz, "n_iter": pn.gl.n_iter if pn.gl else None,
-                  "seed": seed}, dict(formant, **phase, **contour)
+                  "seed": seed}, dict(formant, **phase, **contour, **psola)
 
 
 def _formant_shift(settings, device, bs, seed):

@@ -8,7 +8,7 @@ still recover once the mean pitch is gone?" -- the number the learned anonymiser
     python gender_classifier_train_pitch_norm.py speechbrain_configs/gender_classifier_pitch_norm.yaml \
         --device cuda:0 [--pitch_target_hz 170] [--preserve_formants true | --formant_ratio X] [--lifter 30] \
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi] \
-        [--synthetic N] [--key value ...]
+        [--psola true] [--synthetic N] [--key value ...]
 
 ``--preserve_formants true`` moves the pitch and leaves the spectral envelope where it was (what the reference's
 WORLD re-synthesis does); ``--formant_ratio X`` scales it by X instead.  Without either the
@@ -18,7 +18,10 @@ stretch instead of Griffin-Lim's reconstruction: one pass in
 frame: 1 is the reference's additive shift, 0 a monotone voice; ``--contour_smooth S`` is the
 half-width in frames of the triangle the contour is smoothed with (default 2).  ``--f0_method viterbi`` forms the F0
 track the ratios come from with a path decode through every frame's d' dips instead of first-dip
-YIN.
+YIN.  ``--psola true`` (or ``psola: true`` in the YAML's ``pitch_norm:`` block) moves the pitch in the time domain
+instead (TD-PSOLA): grains between pitch marks laid down again at the new spacing, which keeps the
+envelope and the duration and needs no phase; it takes ``--contour_scale`` without ``--phase vocoder`` and none of
+--phase, --preserve_formants true, --formant_ratio and --lifter.
 
 Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
 summary as the last line (with pitch_target_hz added, and the envelope settings that were given)."""
@@ -51,7 +54,7 @@ def main(argv):
     summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
                "best_checkpoint": getattr(brain, "best_checkpoint", None), "pitch_target_hz": pn["target_hz"]}
     summary.update({k: pn[k] for k in ("preserve_formants", "formant_ratio", "lifter", "phase", "contour_scale",
-                                        "contour_smooth", "f0_method") if k in pn})
+                                        "contour_smooth", "f0_method", "psola") if k in pn})
     print(json.dumps(summary))
 
 

@@ -803,6 +803,58 @@ int sa_mcd_dim(int which);
 int sa_mcd(const float* mel_ref, const float* mel_deg, const int* n_ref, const int* n_deg, int B, int T_ref, int T_deg,
            int n_mels, int order, int band, void* ws, float* mcd, float* mcd_sync, int* frames, void* stream);
 
+/* ---- TD-PSOLA pitch modification (sa_psola.hip; ops.psola_marks, ops.psola_plan, ops.psola): the
+ * waveform is cut into two-period grains centred on pitch marks, and the same grains are laid down again at the new
+ * spacing.  The grains are moved, not altered: the spectral envelope stays, the duration stays, and there is no STFT,
+ * no phase, no iteration and no random number.  Every decision is made on integers, or on fp64 formed from the fp32
+ * inputs; only the overlap-add rounds.
+ *   Per row b:  wav [N] fp32;  f0 [T] fp32 in Hz, <= 0 (or NaN) meaning unvoiced, from either tracker;  rho_q [T]
+ *   int32, the ratio per frame in units of 2^-16, clamped to [2^15, 2^17] where it is read (sa_pitch_contour's);
+ *   n_valid int32, clamped to [0, N].  T is the frames of the waveform or of the waveform padded to a multiple of
+ *   the hop: T = N / 160 + 1 or T = ceil(N / 160) + 1, nothing else.
+ *     F_b = min(T, n_valid / 160 + 1);   frame(n) = min((n + 80) / 160, T - 1);   U = 80;
+ *     per[t] = (int)clamp(rint(16000.0 / (double)f0[t]), 40, 266) when t < F_b and f0[t] > 0, otherwise 0 (unvoiced).
+ *   sa_psola_marks: the analysis marks m_0 < m_1 < ... -> marks [B][Mcap] int32, count [B] int32, Mcap = N / 30 + 2.
+ *     The first mark is the argmax of wav over [0, per[0] - 1] if per[0] > 0, otherwise 0.  The mark after m, with
+ *     p = per[frame(m)]: the argmax of wav over [m + p - (p >> 2), m + p + (p >> 2)] if p > 0, otherwise m + U (a
+ *     window of that one sample).  A mark exists only if its whole window lies below n_valid; the first window that
+ *     does not ends the row.  The argmax compares the signed samples with >, a NaN counting as -inf: ties go to the
+ *     smallest index and a NaN never wins.  The spacing of the marks is therefore in [30, 332].
+ *   sa_psola_plan: where the grains go, in int64 units of 2^-16 samples.  s_0 = m_0 << 16.  For s_j: a(j) is the mark
+ *     nearest to s_j -- a pointer that starts at 0 and advances while the next mark is strictly nearer;
+ *     P = m_{a+1} - m_a, or m_a - m_{a-1} at the last mark;  r = rho_q[frame(m_a)] if per[frame(m_a)] > 0, otherwise
+ *     2^16;  inv = (2^32 + r / 2) / r;  s_{j+1} = s_j + P inv;  while s_j <= m_last << 16.
+ *     -> syn_pos[j] = (s_j + 2^15) >> 16 and syn_src[j] = a(j), [B][Jcap] int32, Jcap = N / 15 + 2; syn_count [B].
+ *     A row with fewer than 2 marks has no plan: syn_count 0.  ws: the caller's, sa_psola_workspace_bytes(B, N) bytes,
+ *     8-byte aligned (P inv per mark); its contents mean nothing between calls.
+ *   sa_psola_ola: for n < n_valid, out[n] = (sum_j w wav[m_a + d]) / max(sum_j w, 0.5) over the grains j in ascending
+ *     order with d = n - syn_pos[j] inside grain j's support, a = syn_src[j].  Half-widths: L = m_a - m_{a-1} and
+ *     R = m_{a+1} - m_a; at the first mark L = R, at the last R = L.  w = 0.5 (1 + cos(pi d / L)) for -L < d < 0, the
+ *     same with R for 0 < d < R, 1 at d = 0, formed in fp64 and rounded once to fp32; the products and both sums are
+ *     fp32, each rounded on its own (no fused multiply-add), and so is the quotient.  The left side of grain 0 is
+ *     rectangular (w = 1) down to source sample 0, the right side of the last grain up to source sample n_valid - 1.
+ *     A source index outside [0, n_valid) contributes nothing; a sample no grain reaches is 0.  A row without a plan
+ *     is copied, out[n] = wav[n]; out[n] = 0 for n >= n_valid.  Neighbouring halves sum to 1, so at rho_q = 2^16
+ *     throughout the plan is the marks themselves and the output is the input.
+ *   What the kernels read from device tables is clamped before it is used: n_valid to [0, N], the counts to [0, Mcap]
+ *   and [0, Jcap], a mark and a syn_pos to [0, N - 1], syn_src to [0, count - 1], a spacing to [30, 332], rho_q to
+ *   [2^15, 2^17] -- none of which changes a table the kernels wrote.  Entries past a row's count mean nothing.
+ *   One wave per row (marks, plan), one workgroup per 256 samples (ola); no atomics, every sum in a fixed order, a
+ *   row's result does not depend on its neighbours: the same bits on every run and in every batch.
+ *   sa_psola_dim(which): 0 U = 80, 1 and 2 the period bounds 40 and 266, 3 and 4 the spacing bounds 30 and 332,
+ *     5 samples per workgroup of sa_psola_ola, 6 and 7 the divisors 30 and 15 of Mcap and Jcap; else -EINVAL.
+ *   sa_psola_workspace_bytes(B, N): 8 B Mcap, or -EINVAL for a B or N the kernels refuse.
+ *   -EINVAL, before any launch: a NULL pointer, B < 1 or > 65535, N < 1 or > 2^24, a T that is neither of the two
+ *     above (sa_psola_marks, sa_psola_plan). */
+int sa_psola_dim(int which);
+long long sa_psola_workspace_bytes(int B, int N);
+int sa_psola_marks(const float* wav, const float* f0, const int* n_valid, int B, int N, int T, int* marks, int* count,
+                   void* stream);
+int sa_psola_plan(const int* marks, const int* count, const float* f0, const int* rho_q, const int* n_valid, int B,
+                  int N, int T, void* ws, int* syn_pos, int* syn_src, int* syn_count, void* stream);
+int sa_psola_ola(const float* wav, const int* marks, const int* count, const int* syn_pos, const int* syn_src,
+                 const int* syn_count, const int* n_valid, int B, int N, float* out, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -129,6 +129,7 @@ SYMBOLS = [
     "sa_f0v_dim", "sa_f0_candidates", "sa_f0_viterbi",
     "sa_f0cmp_dim", "sa_f0_compare",
     "sa_mcd_dim", "sa_mcd",
+    "sa_psola_dim", "sa_psola_marks", "sa_psola_plan", "sa_psola_ola",
 ]
 
 _lib = None
@@ -149,7 +150,8 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         for s in SYMBOLS:
             getattr(_lib, s).restype = C.c_int
-        _lib.sa_pv_workspace_bytes.restype = C.c_longlong     # (the one entry point that does not return an int)
+        _lib.sa_pv_workspace_bytes.restype = C.c_longlong     # (the two entry points that do not return an int)
+        _lib.sa_psola_workspace_bytes.restype = C.c_longlong
         for i, rec in enumerate((SaConvArgs, SaWgradArgs, SaEwArgs, SaPackDesc, SaTaps, SaBiasMulti, SaWredMulti, SaFlats)):
             if _lib.sa_abi_sizeof(i) != C.sizeof(rec):
                 raise SaHipError(f"{rec.__name__}: binding has {C.sizeof(rec)} bytes, {LIB_PATH} "

@@ -1485,3 +1485,104 @@ def mcd(mel_ref, mel_deg, n_ref, n_deg, order=13, band=16):
     L.check(L.load().sa_mcd(_f(mel_ref), _f(mel_deg), _f(n_ref), _f(n_deg), B, T_ref, T_deg, n_mels, order, band,
                             _f(ws), _f(out), _f(sync), _f(frames), L.stream()), "sa_mcd")
     return out, sync, frames
+
+
+# ---- TD-PSOLA pitch modification (csrc/sa_psola.hip; pitchnorm.py) ----
+PSOLA_MAX_N = 1 << 24
+PSOLA_MDIV, PSOLA_JDIV = 30, 15            # sa_psola_dim(6), (7): Mcap = N // 30 + 2, Jcap = N // 15 + 2
+
+_ps_in = functools.partial(_aug_in, family="PSOLA")
+
+
+def _ps_dims(who, B, N, T):
+    if B > GL_MAX_B or not 1 <= N <= PSOLA_MAX_N:
+        raise L.SaHipError(f"{who}: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N in 1..{PSOLA_MAX_N}")
+    if T not in (N // YIN_HOP + 1, -(-N // YIN_HOP) + 1):
+        raise L.SaHipError(f"{who}: f0 has {T} frames; N // 160 + 1 = {N // YIN_HOP + 1} of the waveform (or "
+                           f"{-(-N // YIN_HOP) + 1} of the padded one) expected")
+
+
+def _ps_wav(who, wav, f0, n_valid):
+    if _ps_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    if _ps_in(f0, "f0").dim() != 2 or f0.shape[0] != B:
+        raise L.SaHipError(f"f0: expected [{B}, T], got {tuple(f0.shape)}")
+    _ps_in(n_valid, "n_valid", torch.int32, (B,))
+    _ps_dims(who, B, N, f0.shape[1])
+    return B, N, f0.shape[1]
+
+
+def psola_marks(wav, f0, n_valid):
+    """wav fp32 [B, N], f0 fp32 [B, T] in Hz (0 or less: unvoiced; yin_f0's or f0_viterbi's), n_valid int32 [B] ->
+    (marks int32 [B, N // 30 + 2], count int32 [B]): the pitch marks of every row, a peak of the waveform per period
+    where the frame is voiced and a mark every 80 samples where it is not; entries from count on mean nothing
+    (sa_psola_marks)"""
+    B, N, T = _ps_wav("psola_marks", wav, f0, n_valid)
+    marks = torch.empty(B, N // PSOLA_MDIV + 2, dtype=torch.int32, device=wav.device)
+    count = torch.empty(B, dtype=torch.int32, device=wav.device)
+    L.check(L.load().sa_psola_marks(_f(wav), _f(f0), _f(n_valid), B, N, T, _f(marks), _f(count), L.stream()),
+            "sa_psola_marks")
+    return marks, count
+
+
+def _ps_marks(marks, count, N):
+    if _ps_in(marks, "marks", torch.int32).dim() != 2 or marks.numel() == 0:
+        raise L.SaHipError(f"marks: expected [B, Mcap], got {tuple(marks.shape)}")
+    B = marks.shape[0]
+    if marks.shape[1] != N // PSOLA_MDIV + 2:
+        raise L.SaHipError(f"marks: expected [{B}, N // 30 + 2 = {N // PSOLA_MDIV + 2}], got {tuple(marks.shape)}")
+    _ps_in(count, "count", torch.int32, (B,))
+    return B
+
+
+def psola_plan(marks, count, f0, rho_q, n_valid, *, N):
+    """psola_marks' (marks, count), f0 fp32 [B, T], rho_q int32 [B, T] (the ratio per frame in units of 2^-16:
+    pitch_contour's, or a constant), n_valid int32 [B], N (by keyword: the samples per row, which no table determines) -> (syn_pos int32 [B, N // 15 + 2], syn_src
+    int32 [B, N // 15 + 2], count int32 [B]): where every grain goes and the mark it is cut at; a row under 2 marks
+    has count 0 (sa_psola_plan)"""
+    N = int(N)
+    B = _ps_marks(marks, count, N)
+    if _ps_in(f0, "f0").dim() != 2 or f0.shape[0] != B:
+        raise L.SaHipError(f"f0: expected [{B}, T], got {tuple(f0.shape)}")
+    T = f0.shape[1]
+    _ps_in(rho_q, "rho_q", torch.int32, (B, T))
+    _ps_in(n_valid, "n_valid", torch.int32, (B,))
+    _ps_dims("psola_plan", B, N, T)
+    dev = marks.device
+    lib = L.load()
+    ws = torch.empty(lib.sa_psola_workspace_bytes(B, N) // 8, dtype=torch.int64, device=dev)
+    syn_pos, syn_src = (torch.empty(B, N // PSOLA_JDIV + 2, dtype=torch.int32, device=dev) for _ in range(2))
+    syn_count = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(lib.sa_psola_plan(_f(marks), _f(count), _f(f0), _f(rho_q), _f(n_valid), B, N, T, _f(ws), _f(syn_pos),
+                              _f(syn_src), _f(syn_count), L.stream()), "sa_psola_plan")
+    return syn_pos, syn_src, syn_count
+
+
+def psola_ola(wav, marks, count, syn_pos, syn_src, syn_count, n_valid):
+    """the overlap-add of a plan: wav fp32 [B, N] and the tables of psola_marks and psola_plan -> out fp32 [B, N], zero
+    from n_valid on; a row without a plan is copied (sa_psola_ola)"""
+    if _ps_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    _ps_dims("psola_ola", B, N, N // YIN_HOP + 1)
+    if _ps_marks(marks, count, N) != B:
+        raise L.SaHipError(f"marks: expected {B} rows as wav has, got {marks.shape[0]}")
+    for name, t in (("syn_pos", syn_pos), ("syn_src", syn_src)):
+        _ps_in(t, name, torch.int32, (B, N // PSOLA_JDIV + 2))
+    _ps_in(syn_count, "syn_count", torch.int32, (B,))
+    _ps_in(n_valid, "n_valid", torch.int32, (B,))
+    out = torch.empty_like(wav)
+    L.check(L.load().sa_psola_ola(_f(wav), _f(marks), _f(count), _f(syn_pos), _f(syn_src), _f(syn_count), _f(n_valid),
+                                  B, N, _f(out), L.stream()), "sa_psola_ola")
+    return out
+
+
+def psola(wav, f0, rho_q, n_valid):
+    """wav fp32 [B, N], f0 fp32 [B, T], rho_q int32 [B, T], n_valid int32 [B] -> out fp32 [B, N]: the pitch of every
+    voiced frame multiplied by rho_q / 2^16, envelope and duration kept -- marks, plan and overlap-add, three launches
+    and nothing copied to the host"""
+    B, N, T = _ps_wav("psola", wav, f0, n_valid)
+    _ps_in(rho_q, "rho_q", torch.int32, (B, T))
+    marks, count = psola_marks(wav, f0, n_valid)
+    return psola_ola(wav, marks, count, *psola_plan(marks, count, f0, rho_q, n_valid, N=N), n_valid)

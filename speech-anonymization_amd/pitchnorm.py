@@ -26,7 +26,13 @@ frame so that the output's F0 contour is target + gamma (f0 - mean) -- 1 the add
 baseline, 0 a monotone voice: sa_pitch_contour -> [sa_env_warp_frames] -> sa_pv_synth_map -> sa_pitch_resample_map.
 
 The track: with ``f0_method="viterbi"`` the F0 of every path above is a Viterbi decode through each
-frame's d' dips (sa_f0_candidates -> sa_f0_viterbi on sa_yin_f0's d') instead of the first dip under the threshold."""
+frame's d' dips (sa_f0_candidates -> sa_f0_viterbi on sa_yin_f0's d') instead of the first dip under the threshold.
+
+In the time domain: with ``psola=True`` nothing above but the track and the ratios runs.  The
+waveform is cut into two-period grains centred on pitch marks and the same grains are laid down again at the new spacing
+(TD-PSOLA): sa_psola_marks -> sa_psola_plan -> sa_psola_ola.  The grains are moved, not altered, so the envelope stays
+where it was and there is no phase to choose; the duration is kept, a ratio per frame costs nothing extra, and nothing
+is copied to the host."""
 import collections
 import math
 
@@ -64,6 +70,7 @@ OPTIONS = {
     "contour_smooth": Option("--contour_smooth", "count", 0, SMOOTH_MAX, f"a half-width in frames, 0 to {SMOOTH_MAX}"),
     "f0_method": Option("--f0_method", "choice", F0_METHODS, None, "yin (the first dip of d' under the threshold, the "
                         "default) or viterbi (a path decoded through every frame's dips)"),
+    "psola": Option("--psola", "bool", None, None, "true or false"),
     "target_hz": Option("--pitch_target_hz", "real", TARGET_LOW, TARGET_HIGH, f"a target between {TARGET_LOW:g} and "
                         f"{TARGET_HIGH:g} Hz, the range the F0 tracker covers", "{:g}"),
 }
@@ -156,11 +163,11 @@ def phase_setting(who, phase):
     return phase
 
 
-def contour_settings(who, contour_scale, contour_smooth, phase):
-    """-> (gamma or None, smooth), or ValueError: the contour needs the vocoder's phases"""
+def contour_settings(who, contour_scale, contour_smooth, phase, psola=False):
+    """-> (gamma or None, smooth), or ValueError: the contour needs the vocoder's phases, or PSOLA"""
     if contour_scale is None:
         return None, int(contour_smooth)
-    if phase != "vocoder":
+    if phase != "vocoder" and not psola:
         raise ValueError(f"{who}: contour_scale needs phase=\"vocoder\" (Griffin-Lim with a contour is not built)")
     gamma = float(contour_scale)
     if not CONTOUR_LOW <= gamma <= CONTOUR_HIGH:
@@ -169,6 +176,23 @@ def contour_settings(who, contour_scale, contour_smooth, phase):
             not 0 <= int(contour_smooth) <= SMOOTH_MAX:
         raise ValueError(f"{who}: contour_smooth {contour_smooth} in 0..{SMOOTH_MAX} expected")
     return gamma, int(contour_smooth)
+
+
+# what PitchNormalizer(psola=True) takes no value of but the default: the STFT path's settings
+PSOLA_DEFAULTS = {"preserve_formants": False, "formant_ratio": None, "lifter": 30, "floor_rel": 1e-4,
+                  "max_gain_db": 40.0, "phase": "griffin_lim"}
+
+
+def psola_setting(who, psola, given):
+    """-> psola, or ValueError when it is no bool or comes with a setting (``given``: a dict of those in
+    PSOLA_DEFAULTS) of the path it replaces"""
+    if not isinstance(psola, bool):
+        raise ValueError(f"{who}: psola {psola!r}: True or False expected")
+    for key, value in given.items():
+        if psola and value != PSOLA_DEFAULTS[key]:
+            raise ValueError(f"{who}: psola=True takes no {key}: the grains are moved, not altered, so the envelope is "
+                             "already preserved and there is no phase to choose")
+    return psola
 
 
 class PitchNormalizer:
@@ -181,31 +205,42 @@ class PitchNormalizer:
     ``phase="vocoder"``) moves the contour to target + gamma (f0 - mean) with a ratio per frame, smoothed by a triangle
     of half-width ``contour_smooth`` frames; ``last[0]`` is then the row's mean ratio.  None: one ratio per row.
     ``f0_method="viterbi"`` forms the track with the path decode instead of first-dip YIN, with
-    ``f0_costs`` (a dict of voicing_cost, switch_cost, jump_cost, lag_bias) in place of its defaults."""
+    ``f0_costs`` (a dict of voicing_cost, switch_cost, jump_cost, lag_bias) in place of its defaults.
+    ``psola=True`` moves the pitch in the time domain instead: the grains between pitch marks are
+    laid down again at the new spacing, which keeps the envelope and the duration by construction.  No STFT, no phase
+    (``gl`` is None; n_iter, momentum and seed are unused), no device-to-host copy; ``contour_scale`` then needs no
+    ``phase="vocoder"``, and ``preserve_formants``, ``formant_ratio``, ``phase`` and the envelope's settings are refused."""
 
     def __init__(self, target_hz=170.0, n_iter=32, momentum=0.99, seed=1, r_min=0.5, r_max=2.0, min_voiced=5,
                  threshold=0.15, preserve_formants=False, formant_ratio=None, lifter=30, floor_rel=1e-4,
                  max_gain_db=40.0, phase="griffin_lim", contour_scale=None, contour_smooth=2, f0_method="yin",
-                 f0_costs=None):
+                 f0_costs=None, psola=False):
+        self.psola = psola_setting("PitchNormalizer", psola, dict(
+            preserve_formants=preserve_formants, formant_ratio=formant_ratio, lifter=lifter, floor_rel=floor_rel,
+            max_gain_db=max_gain_db, phase=phase))
         self.f0_method, self.f0_costs = f0_settings("PitchNormalizer", f0_method, f0_costs)
         self.formant_ratio, self.lifter, self.floor_rel, self.max_gain_db = envelope_settings(
             "PitchNormalizer", preserve_formants, formant_ratio, lifter, floor_rel, max_gain_db)
         self.phase = phase_setting("PitchNormalizer", phase)
         self.contour_scale, self.contour_smooth = contour_settings("PitchNormalizer", contour_scale, contour_smooth,
-                                                                   self.phase)
+                                                                   self.phase, self.psola)
         if not TARGET_LOW <= float(target_hz) <= TARGET_HIGH:
             raise ValueError(f"PitchNormalizer: target_hz {target_hz} in {TARGET_LOW:g}..{TARGET_HIGH:g} expected")
         if not R_LOW <= float(r_min) <= float(r_max) <= R_HIGH:
             raise ValueError(f"PitchNormalizer: {R_LOW} <= r_min {r_min} <= r_max {r_max} <= {R_HIGH} expected")
         self.target_hz, self.r_min, self.r_max = float(target_hz), float(r_min), float(r_max)
         self.min_voiced, self.threshold = int(min_voiced), float(threshold)
-        self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed) if phase == "griffin_lim" else None
+        self.gl = None
+        if phase == "griffin_lim" and not self.psola:
+            self.gl = vocoder.GriffinLim(n_iter=n_iter, momentum=momentum, seed=seed)
         self.last = None
 
     @torch.no_grad()
     def __call__(self, wavs, lens):
         gpu_only("PitchNormalizer", wavs)
         lens = lens.to(wavs.device, torch.float32).contiguous()
+        if self.psola:
+            return self.shift_psola(wavs, lens)
         if self.contour_scale is not None:
             return self.shift_contour(wavs, lens)
         f0 = self.track(wavs, lens)
@@ -216,6 +251,27 @@ class PitchNormalizer:
         """the F0 track the ratios are formed from: f0_track with the object's method, threshold and costs (N: the
         unpadded width when wavs is padded)"""
         return f0_track(wavs, self.threshold, self.f0_method, lens, N, **self.f0_costs)
+
+    @torch.no_grad()
+    def shift_psola(self, wavs, lens):
+        """the time-domain path: the track -> one ratio per row (pitch_ratio, as rho_q = rint(ratio
+        2^16) in every frame) or one per frame (pitch_contour) -> psola_marks -> psola_plan -> psola_ola.  Everything
+        stays on the device.  ``last`` as the other paths leave it."""
+        B, N = wavs.shape
+        wavs = wavs.contiguous()
+        f0 = self.track(wavs, lens)
+        T = f0.shape[1]
+        if self.contour_scale is None:
+            self.last = ops.pitch_ratio(f0, lens, N, self.target_hz, self.r_min, self.r_max, self.min_voiced)
+            rho_q = torch.round(self.last[0].double() * ops.CT_RHO_ONE).to(torch.int32)[:, None].expand(B, T)
+            rho_q = rho_q.contiguous()
+        else:
+            if T < 2:                                            # (ops.pitch_contour's bound, said before its division below)
+                raise L.SaHipError(f"PitchNormalizer: contour_scale needs 2 frames, {HOP} samples or more; got {N}")
+            rho_q, Q, _, mean, voiced = ops.pitch_contour(f0, lens, N, self.target_hz, self.contour_scale,
+                                                          self.contour_smooth, self.r_min, self.r_max, self.min_voiced)
+            self.last = ((Q[:, T - 1].double() / float((T - 1) * ops.CT_Q_ONE)).float(), mean, voiced)
+        return ops.psola(wavs, f0, rho_q, n_valid(lens, N, wavs.device).to(torch.int32))
 
     @torch.no_grad()
     def shift_contour(self, wavs, lens):
@@ -346,12 +402,30 @@ def check_f0_option(settings, block=None):
     return {k: check_option(k, v) for k, v in given_options(("f0_method",), settings, block).items()}
 
 
+def check_psola_option(settings, block=None):
+    """the ``psola`` of a recipe's ``pitch_norm:`` block (if any) under the top-level override -> a dict that carries
+    the key only when it was given; anything but true and false is refused in one line, and so is ``psola: true`` next
+    to a setting of the STFT path it replaces (``phase`` with any value, ``preserve_formants: true``, ``formant_ratio``,
+    ``lifter``)"""
+    given = {k: check_option(k, v) for k, v in given_options(("psola",), settings, block).items()}
+    if given.get("psola"):
+        other = given_options(("phase", "preserve_formants", "formant_ratio", "lifter"), settings, block)
+        if other.get("preserve_formants") is False:
+            del other["preserve_formants"]
+        for key in other:
+            why = "there is no phase to choose" if key == "phase" else "the envelope is already preserved"
+            raise SystemExit(f"--psola true and {OPTIONS[key].flag} exclude each other: the grains are moved, not "
+                             f"altered, so {why}")
+    return given
+
+
 def check_contour_options(settings, block=None):
     """``contour_scale`` and ``contour_smooth`` of a recipe's ``pitch_norm:`` block (if any) under the top-level
     overrides -> a dict that carries a key only when it was given; each is refused in one line when out of range or
-    given without ``phase: vocoder``"""
+    given without ``phase: vocoder`` or ``psola: true``"""
     given = given_options(("contour_scale", "contour_smooth"), settings, block)
-    if given and given_options(("phase",), settings, block).get("phase") != "vocoder":
+    if given and given_options(("phase",), settings, block).get("phase") != "vocoder" and \
+            given_options(("psola",), settings, block).get("psola") is not True:
         raise SystemExit(f"--{next(iter(given))} needs --phase vocoder: the contour is moved on the phase-vocoder path "
                          "only")
     for key in given:
@@ -384,4 +458,4 @@ def check_pitch_options(settings, run_opts, environ=None):
         raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
     return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn),
                 **check_phase_option(settings, pn), **check_contour_options(settings, pn),
-                **check_f0_option(settings, pn))
+                **check_f0_option(settings, pn), **check_psola_option(settings, pn))

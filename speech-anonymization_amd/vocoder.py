@@ -234,6 +234,9 @@ def check_anonymize_options(settings, run_opts, environ=None):
     if pitchnorm.check_contour_options(settings) and mode != "pitch_norm":    # 
         raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
                          "pitch")
+    if pitchnorm.check_psola_option(settings).get("psola") and mode != "pitch_norm":       # 
+        raise SystemExit("--psola true goes with --pitch_norm true: it is the pitch normalisation done in the time "
+                         "domain, grains between pitch marks laid down again at the new spacing")
     if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0") \
             and settings.get("report_prosody") is not True:
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)

@@ -13,6 +13,9 @@ frame against frame (mcd_sync).
   pitch_norm_pv, pitch_norm_preserve_pv, formant_ratio_1.15_pv
                           the three Griffin-Lim rows with --phase vocoder: the input's own phases carried through
                           
+  pitch_norm_psola, pitch_norm_psola_contour
+                          pitch normalisation in the time domain (--psola true, TD-PSOLA), with one
+                          ratio per utterance and with --contour_scale 1, a ratio per frame
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech.
@@ -35,7 +38,9 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("mcadams_0.8", ["--mcadams", "0.8"]),
          ("pitch_norm_pv", ["--pitch_norm", "true", "--phase", "vocoder"]),
          ("pitch_norm_preserve_pv", ["--pitch_norm", "true", "--preserve_formants", "true", "--phase", "vocoder"]),
-         ("formant_ratio_1.15_pv", ["--formant_ratio", "1.15", "--phase", "vocoder"]))
+         ("formant_ratio_1.15_pv", ["--formant_ratio", "1.15", "--phase", "vocoder"]),
+         ("pitch_norm_psola", ["--pitch_norm", "true", "--psola", "true"]),
+         ("pitch_norm_psola_contour", ["--pitch_norm", "true", "--psola", "true", "--contour_scale", "1"]))
 
 
 def _mean(vals):
