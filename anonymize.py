@@ -7,6 +7,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
         [--psola true]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
+        [--report_formants true]
 
 DIR is a CKPT+* directory written by speechbrain_convae_train.py (model.ckpt with the ModuleList's ``0.`` keys,
 normalizer.ckpt: the anonymiser's own normaliser, which both feeds it and de-normalises its output).  FILE is a
@@ -54,8 +55,8 @@ phase, no iteration and no random number.  It takes ``--contour_scale G`` withou
 
 ``--f0_method viterbi`` tracks F0 with a Viterbi decode through every frame's d' dips (speech_anonymization_amd.
 pitchnorm.f0_track) instead of first-dip YIN (``yin``, the default).  With ``--pitch_norm true`` it
-steers the normaliser; with ``--report_f0 true`` or ``--report_prosody true``, in any mode, the report is measured
-with it.  Without any of them it is refused: nothing tracks F0.  The JSON line carries ``"f0_method"`` only when the
+steers the normaliser; with ``--report_f0 true``, ``--report_prosody true`` or ``--report_formants true``, in any mode,
+the report is measured with it.  Without any of them it is refused: nothing tracks F0.  The JSON line carries ``"f0_method"`` only when the
 option is given.
 
 ``--report_stoi true`` adds, in any mode, the intelligibility of every waveform written against the waveform it was
@@ -80,6 +81,17 @@ dynamic-time-warping alignment that may move up to R frames (default 16, at most
 common width.  Per utterance ``mcd_db``, ``mcd_sync_db`` (the same figure frame against frame, without an alignment;
 both null when the utterance could not be scored) and ``mcd_frames`` (the frames of both, 0 when not scored);
 ``mcd_mean``, ``mcd_sync_mean`` and ``mcd_scored`` in the final object.
+
+``--report_formants true`` adds, in any mode, where the vocal-tract resonances of every waveform written lie and by
+which factor each moved from its input's (speech_anonymization_amd.metrics.formant_shift, ops.formant_tracks,
+ops.formant_compare): both waveforms are tracked over their common width -- per frame the three
+lowest poles of an order-18 LPC fit between 90 and 5500 Hz with a bandwidth up to 700 Hz -- and read on the frames
+that have all three and are voiced in both (F0 by ``--f0_method``, ``yin`` unless given; with ``--report_prosody true``
+the same tracks serve both).  Per utterance ``f1_hz``, ``f2_hz``, ``f3_hz`` (the median formants of the output),
+``f1_shift``, ``f2_shift``, ``f3_shift`` (the median per-frame ratio output / input of each) and ``formant_shift`` (the
+geometric mean of the three), all null when fewer than 8 frames count, and ``formant_frames`` (those frames, 0 when not
+scored); ``formant_shift_mean``, ``f1_shift_mean``, ``f2_shift_mean``, ``f3_shift_mean`` and ``formants_scored`` in the
+final object.  On ``--synthetic`` rows, bare harmonic series, the poles sit on harmonics: a check of the plumbing.
 
 The last line printed is one JSON object: per utterance the spectral convergence || |STFT(wav)| - S || / || S ||
 of the waveform against the magnitudes it was made from (not with --pitch_norm, which has no such magnitudes), the

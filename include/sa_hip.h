@@ -855,6 +855,51 @@ int sa_psola_plan(const int* marks, const int* count, const float* f0, const int
 int sa_psola_ola(const float* wav, const int* marks, const int* count, const int* syn_pos, const int* syn_src,
                  const int* syn_count, const int* n_valid, int B, int N, float* out, void* stream);
 
+/* ---- LPC formant tracking and its comparison (sa_formants.hip; ops.formant_tracks, ops.formant_compare; DESIGN section
+ * 25): where the vocal-tract resonances of a waveform lie, frame by frame, and by which factor each of them moved from
+ * one waveform to another.  Sample rate 16000, hop 160, W = 400, order P = 18.
+ *   sa_formant_tracks: wav [B][N] fp32; n_valid [B] int32, clamped where it is read to [0, N]; a sample outside
+ *   [0, n_valid_b) reads as 0.  T = N / 160 + 1 frames, the frame grid of sa_yin_f0; frame t covers
+ *   [160 t - 200, 160 t + 200).  Per frame, everything in fp64 on the fp32 samples:
+ *     e[n] = x[n] - 0.97 x[n - 1], e = 0 outside [0, n_valid_b);  f[j] = w[j] e[160 t - 200 + j] with
+ *       w[j] = 0.54 - 0.46 cos(2 pi j / 399), j = 0..399.
+ *     r_k = sum_j f[j] f[j + k], k = 0..18.  r_0 < 1e-10: the frame is silent (status 1); otherwise r_0 *= 1 + 1e-9.
+ *     Levinson-Durbin gives a[0..18]; some |k_i| >= 1 or a prediction error <= 0: a fallback (status 2).
+ *     The 18 roots z of a by Aberth-Ehrlich from 0.9 exp(2 pi i (j + 0.25) / 18), until the largest correction is
+ *       under 1e-14, at most 64 iterations; no convergence: a fallback (status 2).
+ *     A root with Im z > 1e-6 |z| is a candidate: f = arg z 16000 / (2 pi), b = -ln|z| 16000 / pi; it is kept when
+ *       90 <= f <= 5500 and b <= 700.
+ *     Fewer than three kept: short (status 3).  Otherwise status 0, and F1..F3 and their bandwidths are those of the
+ *       three kept candidates of lowest f, in ascending f.
+ *   -> freq [B][T][3] and bw [B][T][3] fp32 in Hz, each rounded once, 0 for any status other than 0; status [B][T]
+ *   int32.  bw and status may be NULL.  One wave per frame, grid (T, B); one launch on the given stream.
+ *   sa_formant_compare: F_ref, F_deg [B][T][3] fp32 and st_ref, st_deg [B][T] int32 (two outputs of
+ *   sa_formant_tracks); f0_ref, f0_deg [B][T] fp32 in Hz, 0 or less meaning unvoiced (two tracks of sa_yin_f0 or
+ *   sa_f0_viterbi); frames [B] int32, clamped where it is read to F_b in [0, T]; min_common m >= 1.
+ *     Frame t counts when t < F_b, st_ref[t] = st_deg[t] = 0, f0_ref[t] > 0 and f0_deg[t] > 0; n of them do.
+ *     n >= m:  med_k = the lower median of F_deg[t][k] over the counted frames, the element at index (n - 1) / 2 of the
+ *       sorted values (an element of the track: exact);  ratio_k = the lower median of
+ *       q_k[t] = fp32((double)F_deg[t][k] / (double)F_ref[t][k]);
+ *       shift = fp32(exp((ln ratio_1 + ln ratio_2 + ln ratio_3) / 3)) in fp64 (exactly 1 for ratios of 1);
+ *       common = n.
+ *     n < m:  med, ratio, shift and common are all 0: the row is not scored.
+ *   -> med [B][3], ratio [B][3], shift [B] fp32; common [B] int32.  All but shift may be NULL.
+ *   The medians are selected exactly, bit by bit from the top of an order-preserving key of the fp32 values: 33 passes
+ *   over the row by one workgroup, one path for every T, no workspace.  The same order holds for values of any sign;
+ *   a NaN sorts past the infinity of its sign.
+ *   No copy to the host, no synchronisation, no atomics, every sum in a fixed order: the same bits on every run.
+ *   sa_formant_dim(which): 0 W = 400, 1 the hop 160, 2 P = 18, 3 the 3 formants, 4 threads per workgroup of
+ *     sa_formant_tracks, 5 the iteration limit 64, 6 the T limit 104858 of sa_formant_compare (the frames of 2^24
+ *     samples), 7 threads per workgroup of sa_formant_compare; else -EINVAL.
+ *   -EINVAL, before any launch: a NULL required pointer, B < 1 or > 65535, N < 1 or > 2^24 (sa_formant_tracks),
+ *     T < 1 or > 104858 and min_common < 1 (sa_formant_compare). */
+int sa_formant_dim(int which);
+int sa_formant_tracks(const float* wav, const int* n_valid, int B, int N, float* freq, float* bw, int* status,
+                      void* stream);
+int sa_formant_compare(const float* F_ref, const float* F_deg, const int* st_ref, const int* st_deg,
+                       const float* f0_ref, const float* f0_deg, const int* frames, int B, int T, int min_common,
+                       float* med, float* ratio, float* shift, int* common, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

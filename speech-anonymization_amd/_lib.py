@@ -130,6 +130,7 @@ SYMBOLS = [
     "sa_f0cmp_dim", "sa_f0_compare",
     "sa_mcd_dim", "sa_mcd",
     "sa_psola_dim", "sa_psola_marks", "sa_psola_plan", "sa_psola_ola",
+    "sa_formant_dim", "sa_formant_tracks", "sa_formant_compare",
 ]
 
 _lib = None

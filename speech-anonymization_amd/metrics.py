@@ -109,6 +109,16 @@ class CepstralStats(_GatedMeans):
         self._add(ids, frames, mcd, mcd_sync)
 
 
+class FormantStats(_GatedMeans):
+    """Formant shifts of a set of utterances (ops.formant_compare): the means of the geometric-mean
+    ratio and of the three per-formant ratios over the rows with common > 0"""
+    gated = ("formant_shift", "f1_shift", "f2_shift", "f3_shift")
+
+    def append(self, ids, shift, r1, r2, r3, common):
+        """ids: a sequence of B names; shift, r1, r2, r3 fp32 [B]; common int [B] (tensors, on any one device)"""
+        self._add(ids, common, shift, r1, r2, r3)
+
+
 def frame_counts(n_valid, width):
     """n_valid int32 [B], the samples of a row that count, of ``width`` -> the Fbank frames that count, int32 [B]"""
     from . import features
@@ -135,3 +145,14 @@ def mel_cepstral_distortion(wav_ref, wav_deg, n_valid, order=13, band=16):
     from . import ops
     frames = frame_counts(n_valid.to(wav_ref.device), wav_ref.shape[1])
     return ops.mcd(*log_mels(wav_ref, wav_deg), frames, frames, order=order, band=band)
+
+
+def formant_shift(wav_ref, wav_deg, n_valid, f0_ref, f0_deg, frames, min_common=8):
+    """wav_ref, wav_deg fp32 [B, N] at 16 kHz on the GPU, already at a common width; n_valid int32 [B], the samples of
+    a row that count; f0_ref, f0_deg fp32 [B, N // 160 + 1], their F0 tracks; frames int32 [B], the frames that count
+    -> the columns of ops.formant_compare: both waveforms are tracked in one launch, as a [2 B, N]
+    batch, and wav_deg's formants are read against wav_ref's on the frames voiced in both."""
+    from . import ops
+    B = wav_ref.shape[0]
+    F, st = ops.formant_tracks(torch.cat((wav_ref, wav_deg)), torch.cat((n_valid, n_valid)))
+    return ops.formant_compare(F[:B], F[B:], st[:B], st[B:], f0_ref, f0_deg, frames, min_common=min_common)

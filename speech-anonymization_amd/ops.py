@@ -1586,3 +1586,62 @@ def psola(wav, f0, rho_q, n_valid):
     _ps_in(rho_q, "rho_q", torch.int32, (B, T))
     marks, count = psola_marks(wav, f0, n_valid)
     return psola_ola(wav, marks, count, *psola_plan(marks, count, f0, rho_q, n_valid, N=N), n_valid)
+
+
+# ---- LPC formant tracking and its comparison (csrc/sa_formants.hip) ----
+FORMANT_W, FORMANT_P, FORMANTS = 400, 18, 3                # sa_formant_dim(0), (2), (3)
+FORMANT_MAX_N, FORMANT_MAX_T = 1 << 24, (1 << 24) // 160 + 1          # sa_formant_dim(6): the frames of 2^24 samples
+
+_fm_in = functools.partial(_aug_in, family="formant")
+
+
+def formant_tracks(wav, n_valid, return_bw=False):
+    """wav fp32 [B, N] at 16 kHz, n_valid int32 [B] (the samples of a row that count, clamped to [0, N]) -> (freq fp32
+    [B, T, 3], status int32 [B, T][, bw fp32 [B, T, 3]]), T = N // 160 + 1 (the frames of yin_f0): per frame of 400
+    pre-emphasised, Hamming-windowed samples the three lowest resonances of an order-18 LPC fit between 90 and 5500 Hz
+    with a bandwidth up to 700 Hz, in Hz, and their bandwidths; status 0 a frame that has them, 1 a silent one, 2 one
+    whose fit or roots failed, 3 one with fewer than three resonances (freq and bw 0 for all but 0).  Everything stays
+    on the device (sa_formant_tracks)."""
+    if _fm_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    if B > GL_MAX_B or N > FORMANT_MAX_N:
+        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {FORMANT_MAX_N}")
+    _fm_in(n_valid, "n_valid", torch.int32, (B,))
+    T = N // YIN_HOP + 1
+    freq = torch.empty(B, T, FORMANTS, dtype=torch.float32, device=wav.device)
+    bw = torch.empty(B, T, FORMANTS, dtype=torch.float32, device=wav.device) if return_bw else None
+    status = torch.empty(B, T, dtype=torch.int32, device=wav.device)
+    L.check(L.load().sa_formant_tracks(_f(wav), _f(n_valid), B, N, _f(freq), _f(bw), _f(status), L.stream()),
+            "sa_formant_tracks")
+    return (freq, status, bw) if return_bw else (freq, status)
+
+
+def formant_compare(F_ref, F_deg, st_ref, st_deg, f0_ref, f0_deg, frames, min_common=8):
+    """F_ref, F_deg fp32 [B, T, 3] and st_ref, st_deg int32 [B, T] (two outputs of formant_tracks), f0_ref, f0_deg fp32
+    [B, T] in Hz (0 or less: unvoiced; two tracks of pitchnorm.f0_track), frames int32 [B] (the frames of a row that
+    count, clamped to [0, T]) -> (med1, med2, med3, r1, r2, r3, shift fp32 [B], common int32 [B]): over the frames with
+    status 0 and a voiced F0 in both, the lower median of each formant of F_deg in Hz, the lower median of each
+    formant's per-frame ratio F_deg / F_ref, the geometric mean of the three ratios, and the number of those frames.
+    A row with fewer than min_common of them gets eight zeros.  Everything stays on the device (sa_formant_compare)."""
+    if _fm_in(F_ref, "F_ref").dim() != 3 or F_ref.shape[2] != FORMANTS or F_ref.numel() == 0:
+        raise L.SaHipError(f"F_ref: expected [B, T, {FORMANTS}] with B, T >= 1, got {tuple(F_ref.shape)}")
+    B, T, _ = F_ref.shape
+    if B > GL_MAX_B or T > FORMANT_MAX_T:
+        raise L.SaHipError(f"F_ref: [B, T] = [{B}, {T}] -- B up to {GL_MAX_B} (a grid extent), T up to {FORMANT_MAX_T}")
+    _fm_in(F_deg, "F_deg", shape=(B, T, FORMANTS))
+    _fm_in(st_ref, "st_ref", torch.int32, (B, T))
+    _fm_in(st_deg, "st_deg", torch.int32, (B, T))
+    _fm_in(f0_ref, "f0_ref", shape=(B, T))
+    _fm_in(f0_deg, "f0_deg", shape=(B, T))
+    _fm_in(frames, "frames", torch.int32, (B,))
+    if isinstance(min_common, bool) or not isinstance(min_common, int) or min_common < 1:
+        raise L.SaHipError(f"formant_compare: min_common, a count of frames, 1 or more expected, got {min_common!r}")
+    dev = F_ref.device
+    med, ratio = (torch.empty(B, FORMANTS, dtype=torch.float32, device=dev) for _ in range(2))
+    shift = torch.empty(B, dtype=torch.float32, device=dev)
+    common = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.load().sa_formant_compare(_f(F_ref), _f(F_deg), _f(st_ref), _f(st_deg), _f(f0_ref), _f(f0_deg), _f(frames),
+                                        B, T, min_common, _f(med), _f(ratio), _f(shift), _f(common), L.stream()),
+            "sa_formant_compare")
+    return (*med.unbind(1), *ratio.unbind(1), shift, common)

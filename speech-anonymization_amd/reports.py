@@ -1,6 +1,7 @@
-"""The reports of anonymize.py: what ``--report_f0``, ``--report_stoi``, ``--report_prosody`` and ``--report_mcd`` add
-to its JSON line (DESIGN sections 15, 18, 22, 23).  One row of ``REPORTS`` per flag, one ``Report`` per row that is on:
-the driver scores every batch with each of them, asks each for its keys per utterance and, at the end, for its summary.
+"""The reports of anonymize.py: what ``--report_f0``, ``--report_stoi``, ``--report_prosody``, ``--report_mcd`` and
+``--report_formants`` add to its JSON line (DESIGN sections 15, 18, 22, 23, 25).  One row of ``REPORTS`` per flag, one
+``Report`` per row that is on: the driver scores every batch with each of them, asks each for its keys per utterance
+and, at the end, for its summary.
 The options are checked by vocoder.check_anonymize_options (vocoder.REPORT_OPTIONS) before anything here runs."""
 import collections
 import functools
@@ -13,10 +14,12 @@ from . import features, metrics, ops, pitchnorm, vocoder
 class Window:
     """The common window of a batch's two waveforms: width, the smaller of their widths; nv int32 [B] on the device,
     the samples of a row that count in both; ref and deg, the input and the output cut to width, fp32 and contiguous;
-    frames int32 [B], the Fbank frames of nv, formed when the first report asks for them."""
+    frames int32 [B], the Fbank frames of nv, formed when the first report asks for them; f0, the F0 tracks of the pair
+    per tracker, kept by f0_tracks."""
 
     def __init__(self, width, nv, ref, deg):
         self.width, self.nv, self.ref, self.deg = width, nv, ref, deg
+        self.f0 = {}
 
     @functools.cached_property
     def frames(self):
@@ -66,9 +69,12 @@ def _stoi(batch):
 
 
 def f0_tracks(window, f0_method="yin"):
-    """the F0 tracks of window.ref and window.deg over the samples that count"""
-    rel = (window.nv.double() / window.width).float()
-    return tuple(pitchnorm.f0_track(w, method=f0_method, lens=rel) for w in (window.ref, window.deg))
+    """the F0 tracks of window.ref and window.deg over the samples that count, tracked once per window and tracker"""
+    if f0_method not in window.f0:
+        rel = (window.nv.double() / window.width).float()
+        window.f0[f0_method] = tuple(pitchnorm.f0_track(w, method=f0_method, lens=rel)
+                                     for w in (window.ref, window.deg))
+    return window.f0[f0_method]
 
 
 def _prosody(batch, f0_method, prosody_max_lag):
@@ -79,6 +85,11 @@ def _prosody(batch, f0_method, prosody_max_lag):
 def _mcd(batch, mcd_band, mcd_order):
     w = batch.window
     return metrics.mel_cepstral_distortion(w.ref, w.deg, w.nv, order=mcd_order, band=mcd_band)
+
+
+def _formants(batch, f0_method):
+    w = batch.window
+    return metrics.formant_shift(w.ref, w.deg, w.nv, *f0_tracks(w, f0_method), w.frames)
 
 
 # options: the settings the scoring call takes by name, with their defaults; score: Batch, **options -> a tuple of
@@ -105,6 +116,14 @@ REPORTS = {                                                 # in the order of th
                       (metrics.CepstralStats, (0, 1, 2)),
                       (("mcd_db", 0, 2, float), ("mcd_sync_db", 1, 2, float), ("mcd_frames", 2, None, int)),
                       (("mcd_mean", "mcd"), ("mcd_sync_mean", "mcd_sync"), ("mcd_scored", "scored"))),
+    # columns: med1, med2, med3, r1, r2, r3, shift, common
+    "report_formants": Row({"f0_method": "yin"}, _formants, (metrics.FormantStats, (6, 3, 4, 5, 7)),
+                           (("f1_hz", 0, 7, float), ("f2_hz", 1, 7, float), ("f3_hz", 2, 7, float),
+                            ("f1_shift", 3, 7, float), ("f2_shift", 4, 7, float), ("f3_shift", 5, 7, float),
+                            ("formant_shift", 6, 7, float), ("formant_frames", 7, None, int)),
+                           (("formant_shift_mean", "formant_shift"), ("f1_shift_mean", "f1_shift"),
+                            ("f2_shift_mean", "f2_shift"), ("f3_shift_mean", "f3_shift"),
+                            ("formants_scored", "scored"))),
 }
 
 

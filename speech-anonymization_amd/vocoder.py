@@ -184,6 +184,7 @@ REPORT_OPTIONS = {
                               "compares two spectral envelopes"),
     "mcd_order": _report_count("mcd_order", 1, MCD_MAX_ORDER, "a count of cepstral coefficients", "report_mcd",
                                "compares two spectral envelopes"),
+    "report_formants": _report_flag("report_formants", "tracks the formants of"),
 }
 # the two modes that re-synthesise the waveform they are given: their flag and what they write
 RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
@@ -238,7 +239,7 @@ def check_anonymize_options(settings, run_opts, environ=None):
         raise SystemExit("--psola true goes with --pitch_norm true: it is the pitch normalisation done in the time "
                          "domain, grains between pitch marks laid down again at the new spacing")
     if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0") \
-            and settings.get("report_prosody") is not True:
+            and settings.get("report_prosody") is not True and settings.get("report_formants") is not True:
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
     if mode in ("passthrough", "model") and settings.get("model_type") not in ANON_MODEL_TYPES:
         raise SystemExit(f"unknown model_type {settings.get('model_type')!r}: the anonymiser is one of convae, fcae "
@@ -266,7 +267,7 @@ def check_anonymize_options(settings, run_opts, environ=None):
         raise SystemExit("--csv FILE and --synthetic N exclude each other")
     if not settings.get("csv") and not settings.get("synthetic"):
         raise SystemExit("one of --csv FILE and --synthetic N is required")
-    for key, o in REPORT_OPTIONS.items():                   # (DESIGN sections 18, 22, 23: any mode, 16 kHz only)
+    for key, o in REPORT_OPTIONS.items():                   # (DESIGN sections 18, 22, 23, 25: any mode, 16 kHz only)
         val = settings.get(key)
         if val is None:
             continue

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """What each signal-processing baseline costs in intelligibility, does to the pitch and moves in the spectral
-envelope, on the synthetic set: anonymize.py --synthetic N --report_stoi true --report_f0 true --report_mcd true once
-per mode, each a fresh child process, and per mode the mean STOI, ESTOI, voiced-mean F0 and voiced share of what it
-wrote and its mean mel-cepstral distortion from the input in dB, along the alignment (mcd) and
-frame against frame (mcd_sync).
+envelope, on the synthetic set: anonymize.py --synthetic N --report_stoi true --report_f0 true --report_mcd true
+--report_formants true once per mode, each a fresh child process, and per mode the mean STOI, ESTOI, voiced-mean F0 and
+voiced share of what it wrote, its mean mel-cepstral distortion from the input in dB, along the
+alignment (mcd) and frame against frame (mcd_sync), and the mean factor by which its LPC formants
+moved, all three together (formant_shift) and one by one (f1_shift, f2_shift, f3_shift).
 
   passthrough             the vocoder alone: Fbank -> Mel pseudo-inverse -> Griffin-Lim of the original features
   pitch_norm              pitch normalisation to 170 Hz
@@ -18,7 +19,8 @@ frame against frame (mcd_sync).
                           ratio per utterance and with --contour_scale 1, a ratio per frame
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
-run end to end and how they rank on that material.  It says nothing about real speech.
+run end to end and how they rank on that material.  It says nothing about real speech; the formant columns in
+particular read poles that sit on harmonics, not on resonances, and are a check of the plumbing there.
 
     python tools/anonymiser_table.py [--synthetic 32]         # one JSON line, also written to --out
 """
@@ -63,7 +65,7 @@ def main():
                                 os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", a.device,
                                 "--synthetic", str(a.synthetic), "--batch_size", str(a.batch_size), "--out_dir",
                                 os.path.join(tmp, name), "--report_stoi", "true", "--report_f0", "true",
-                                "--report_mcd", "true"] + flags,
+                                "--report_mcd", "true", "--report_formants", "true"] + flags,
                                cwd=ROOT, capture_output=True, text=True, timeout=a.timeout)
             if r.returncode != 0:
                 raise SystemExit(f"{name}: anonymize.py ended with {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
@@ -73,7 +75,10 @@ def main():
                            "scored": sum(1 for u in utts if u["stoi_segments"] > 0), "utterances": len(utts),
                            "f0_mean_hz": _mean([u["f0_mean_hz"] for u in utts if u["voiced_share"] > 0]),
                            "voiced_share": _mean([u["voiced_share"] for u in utts]),
-                           "mcd": res["mcd_mean"], "mcd_sync": res["mcd_sync_mean"], "mcd_scored": res["mcd_scored"]}
+                           "mcd": res["mcd_mean"], "mcd_sync": res["mcd_sync_mean"], "mcd_scored": res["mcd_scored"],
+                           "formant_shift": res["formant_shift_mean"], "f1_shift": res["f1_shift_mean"],
+                           "f2_shift": res["f2_shift_mean"], "f3_shift": res["f3_shift_mean"],
+                           "formants_scored": res["formants_scored"]}
     line = json.dumps({"synthetic": a.synthetic, "modes": table})
     print(line)
     if a.out:
