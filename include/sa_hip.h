@@ -267,6 +267,10 @@ int sa_pool_nseg(int B);
 int sa_pool_gather(const float* part, int B, int nseg, int L, double* sums, void* stream);
 int sa_pool_fin(const double* sums, int B, int n, const float* noise, float eps, float* pooled,
                 float* mean, float* stdraw, void* stream);
+/* sa_pool_gather + sa_pool_fin in one launch (same bits).  raw != 0: noise [B][128] is the N(0,1) draw itself
+ * and is normalised in the kernel, (g - min g) / max(g - min g) over all B*128 values */
+int sa_pool_gather_fin(const float* part, int B, int nseg, int L, const float* noise, int raw, float eps,
+                       float* pooled, float* mean, float* stdraw, void* stream);
 /* stats (optional, [B][ceil(L/256)][128][2]): partial (sum g, sum g*(r-bn_mean[c])*bn_rstd[c]) of
  * the written gradient, i.e. what sa_ew_stats would compute from g and r in a second pass */
 int sa_pool_bwd(int dtype, const void* r, const float* scale, const float* shift,
@@ -293,6 +297,15 @@ int sa_cls_losses(const float* logp, const long long* label, int B, int NC, floa
                   float* dconf, void* stream);                   /* out = (nll, confusion) */
 int sa_cosine_loss(const float* x1, const float* x2, int B, int S, int D, float* rowloss,
                    float* loss, float* dx1, void* stream);
+/* The loss tail of the ConvAE train step as two launches.  sa_recon_loss_part: sa_recon_loss without its
+ * finaliser; the partial sums stay in the workspace and grad[i] = fl(gscale * g_i), g_i the gradient
+ * sa_recon_loss stores.  sa_step_loss (one workgroup): out = (recon, sex, total) with recon / sex the values of
+ * sa_recon_loss / sa_cls_losses and total = fl(fl(w_recon*recon) + fl(w_sex*sex)) + 0.0f; dlogp (optional) =
+ * dnll * fl(1.0f * w_sex); *nonfinite (optional, device int32) += !isfinite(total). */
+int sa_recon_loss_part(const float* a, const float* b, long long n, int kind, float* grad, float gscale,
+                       void* workspace, void* stream);
+int sa_step_loss(const void* workspace, long long n, const float* logp, const long long* label, int B, int NC,
+                 float w_recon, float w_sex, float* out, float* dlogp, int* nonfinite, void* stream);
 
 /* The FC head (classify: Linear(256,128) ReLU BatchNorm Linear(128,64) ReLU BatchNorm Linear(64,2),
  * models/ConvAutoEncoder.py:47-55, + log_softmax :68) as ONE forward and ONE backward launch
@@ -310,6 +323,13 @@ int sa_head_bwd(const float* dlogp, const float* logp, const float* pooled, cons
                 const float* h2, const float* f2, const float* w1, const float* g1, const float* w2,
                 const float* g2, const float* w3, float* dw1, float* db1, float* dg1, float* dbe1, float* dw2,
                 float* db2, float* dg2, float* dbe2, float* dw3, float* db3, float* dpooled, int M, void* stream);
+/* sa_head_bwd over 16 workgroups: each recomputes the dependent chain and writes a slice of d W1, d W2 and
+ * dpooled; same arguments, same bits */
+int sa_head_bwd_wide(const float* dlogp, const float* logp, const float* pooled, const float* h1, const float* f1,
+                     const float* h2, const float* f2, const float* w1, const float* g1, const float* w2,
+                     const float* g2, const float* w3, float* dw1, float* db1, float* dg1, float* dbe1, float* dw2,
+                     float* db2, float* dg2, float* dbe2, float* dw3, float* db3, float* dpooled, int M,
+                     void* stream);
 int sa_head_max_rows(void);
 
 /* x-vector gender classifier forward (sa_xvector.hip; models/external_gender_classifiers.py:71-115,144-183;

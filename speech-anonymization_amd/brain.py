@@ -133,6 +133,11 @@ class Brain:
         # input and target in one pass (InputNormalization.forward_pair: the bits and the state of the two
         # features() calls of the reference's step); see SexAnonymizationTraining.features
         self.front_end_once = bool(run_opts.get("front_end_once", os.environ.get("SA_FRONT_END_ONCE", "1") == "1"))
+        # step_tail (default on; SA_STEP_TAIL=0): the loss tail of the ConvAE train step -- both loss finalisers,
+        # the weighted sum, the scale of the two gradients and the non-finite count -- in one launch, and the
+        # backward started from the model outputs instead of through a graph of 0-dim tensors (same bits;
+        # SexAnonymizationTraining._native_tail says when)
+        self.step_tail = bool(run_opts.get("step_tail", os.environ.get("SA_STEP_TAIL", "1") == "1"))
         self.distributed_launch = bool(run_opts.get("distributed_launch", sdist.is_distributed()))
         self.modules = torch.nn.ModuleDict(modules or {})
         # dp_batch_sizes (default "equal"): how the data-parallel ranks' batches relate.  The data
@@ -255,18 +260,24 @@ class Brain:
         recorded in the graph, the event is recorded by the replaying host code."""
         if not (self.lazy_finite_check and loss.is_cuda):
             return 0 if bool(torch.isfinite(loss)) else 1
-        st = getattr(self, "_finite_state", None)
-        if st is None:
-            st = self._finite_state = dict(dev=torch.zeros((), dtype=torch.int32, device=loss.device),
-                                           host=torch.zeros((), dtype=torch.int32).pin_memory(),
-                                           event=torch.cuda.Event(), seen=0, pending=False)
+        st = self._finite_counter(loss.device)
         new = self._poll_nonfinite()
-        st["dev"].add_((~torch.isfinite(loss.detach())).to(torch.int32))
+        if st.pop("counted", None) is not loss:       # (the native loss tail has counted this loss already)
+            st["dev"].add_((~torch.isfinite(loss.detach())).to(torch.int32))
         st["host"].copy_(st["dev"], non_blocking=True)
         if not torch.cuda.is_current_stream_capturing():
             st["event"].record()
             st["pending"] = True
         return new
+
+    def _finite_counter(self, device):
+        """the lazy check's state: device counter, its pinned host copy and the event behind the copy"""
+        st = getattr(self, "_finite_state", None)
+        if st is None:
+            st = self._finite_state = dict(dev=torch.zeros((), dtype=torch.int32, device=device),
+                                           host=torch.zeros((), dtype=torch.int32).pin_memory(),
+                                           event=torch.cuda.Event(), seen=0, pending=False)
+        return st
 
     def _poll_nonfinite(self, wait=False):
         st = getattr(self, "_finite_state", None)
@@ -429,6 +440,8 @@ class SexAnonymizationTraining(Brain):
             utility_loss = asr.utility_loss(asr_brain, hp.loss_utility, feats, reconstructed_speech,
                                             wav_lens, tokens_bos, batch)
         B = reconstructed_speech.shape[0]
+        if self._native_tail(stage, predictions):
+            return self._objectives_native(reconstructed_speech, sex_logits, feats, sex_label)
         recon_loss = hp.loss_reconstruction(reconstructed_speech.view(B, -1), feats.view(B, -1))
         sex_loss = hp.loss_sex_classification(sex_logits, sex_label)
         if hp.model_type == "endtoend":
@@ -471,6 +484,61 @@ class SexAnonymizationTraining(Brain):
                     self.utility_similarity_aggregator.append(
                         ops.cosine_rows(recon_enc.reshape(nb, -1), orig_enc.reshape(nb, -1)))
         return loss
+
+    def _native_tail(self, stage=Stage.TRAIN, predictions=None):
+        """whether compute_objectives, called by this class's fit_batch, takes the one-launch loss tail
+        (run_opts step_tail): the plain ConvAE objective `w_r * recon + w_s * sex + 0.0` with the library's own
+        recon and NLL losses, no utility term, no accumulation, on the GPU.  Host state only (part of
+        _graph_key); everything else -- endtoend's signed sum, the confusion and utility terms, accumulation,
+        a call from outside fit_batch -- goes through the loss modules and autograd as before."""
+        from . import losses
+        hp = self.hparams
+        if not (self.step_tail and stage == Stage.TRAIN and self.__dict__.get("_in_fit_batch")
+                and self.device.type == "cuda" and hp.model_type == "convae"
+                and getattr(hp, "gradient_accumulation", 1) == 1
+                and isinstance(hp.loss_reconstruction, losses.ReconLoss)
+                and isinstance(hp.loss_sex_classification, losses.NLLLoss)):
+            return False
+        w = (hp.recon_loss_weight, hp.sex_loss_weight, hp.utility_loss_weight)
+        if not all(isinstance(x, (int, float)) and x == x and abs(x) != float("inf") for x in w):
+            return False
+        if not (w[2] == 0 or (w[2] > 0 and getattr(self, "asr_brain", None) is None)):
+            return False
+        if predictions is not None:
+            recon, logp = predictions
+            return bool(recon.is_cuda and recon.requires_grad and logp.requires_grad and logp.dim() == 2
+                        and recon.dtype == logp.dtype == torch.float32)
+        return True
+
+    def _objectives_native(self, recon, logp, feats, label):
+        """compute_objectives on the _native_tail path: two launches (ops.step_loss) leave the loss terms, the
+        total, the gradients of the two model outputs and the non-finite count; _backward starts from those."""
+        from . import ops
+        hp = self.hparams
+        B = recon.shape[0]
+        st = self._finite_counter(recon.device) if self.lazy_finite_check else None
+        label = torch.as_tensor(label, device=logp.device).long().contiguous()
+        out, d_recon, d_logp = ops.step_loss(
+            recon.detach().view(B, -1).contiguous(), feats.detach().view(B, -1).contiguous().float(),
+            hp.loss_reconstruction.kind, logp.detach().contiguous(), label,
+            float(hp.recon_loss_weight), float(hp.sex_loss_weight), nonfinite=st["dev"] if st else None)
+        loss = out[2]
+        self.last_losses = dict(recon=out[0], sex=out[1])
+        self._tail = (loss, (recon, logp), (d_recon.view_as(recon), d_logp))
+        if st is not None:
+            st["counted"] = loss
+        return loss
+
+    def _backward(self, loss, accumulate=False):
+        """loss.backward() of a step (accumulate: of loss / gradient_accumulation); on the native-tail path the
+        backward of the model outputs with the gradients the loss launch prepared"""
+        tail, self._tail = self.__dict__.get("_tail"), None
+        if tail is not None and tail[0] is loss:
+            torch.autograd.backward(tail[1], tail[2])
+        elif accumulate:
+            (loss / self.hparams.gradient_accumulation).backward()
+        else:
+            loss.backward()
 
     def apply_epoch_schedule(self):
         """HEAD's epoch-parity schedule (speechbrain_convae_train.py:212-235), enabled with
@@ -540,12 +608,14 @@ class SexAnonymizationTraining(Brain):
                 # front_end_once: whether the captured normalisation writes one tensor or two
                 self.front_end_once, bool(not upd and getattr(nrm, "_count_positive", False)),
                 # SpecAugment of the input: three more launches in the captured step
-                self.__dict__.get("_specaug") is not None)
+                self.__dict__.get("_specaug") is not None,
+                # step_tail: whether the captured step ends in the one-launch loss tail
+                self._native_tail())
 
     def _step_core(self, batch):
         predictions = self.compute_forward(batch, Stage.TRAIN)
         loss = self.compute_objectives(predictions, batch, Stage.TRAIN)
-        loss.backward()
+        self._backward(loss)
         if getattr(self.hparams, "epoch_parity_schedule", False):
             self._zero_grads_of_frozen()
         self.check_gradients(loss)
@@ -619,11 +689,11 @@ class SexAnonymizationTraining(Brain):
     def fit_batch(self, batch):
         # front_end_once: compute_forward normalises input and target together while this flag is up; a
         # target left over from an earlier step is never served
-        self._target_stash, self._in_fit_batch = None, True
+        self._target_stash, self._in_fit_batch, self._tail = None, True, None
         try:
             return self._fit_batch(batch)
         finally:
-            self._target_stash, self._in_fit_batch = None, False
+            self._target_stash, self._in_fit_batch, self._tail = None, False, None
 
     def _fit_batch(self, batch):
         self.apply_epoch_schedule()
@@ -634,7 +704,7 @@ class SexAnonymizationTraining(Brain):
             batch = batch.to(self.device)       # once: both hooks then see the same device tensors
         predictions = self.compute_forward(batch, Stage.TRAIN)
         loss = self.compute_objectives(predictions, batch, Stage.TRAIN)
-        (loss / self.hparams.gradient_accumulation).backward()
+        self._backward(loss, accumulate=True)
         if self.step % self.hparams.gradient_accumulation == 0:
             if getattr(self.hparams, "epoch_parity_schedule", False):
                 self._zero_grads_of_frozen()

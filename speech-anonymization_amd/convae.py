@@ -119,6 +119,12 @@ class ConvAutoencoder(nn.Module):
         # decoder.8's data gradient and weight gradient from one read of y8 (sa_bwd1C; same bits);
         # SA_FUSED_BWD1C=0: the two launches (conv1toC + wgrad1C)
         self.fused_bwd1c = os.environ.get("SA_FUSED_BWD1C", "1") == "1"
+        # the pooling finaliser in the tail of the gather launch, the noise draw normalised there instead of on
+        # four ATen kernels (sa_pool_gather_fin; same bits); SA_FUSED_POOL_FIN=0: gather + finaliser launches
+        self.fused_pool_fin = os.environ.get("SA_FUSED_POOL_FIN", "1") == "1"
+        # the fused head's backward over 16 workgroups, each with a slice of d W1 / d W2 / d pooled
+        # (sa_head_bwd_wide; same bits); SA_WIDE_HEAD_BWD=0: the one-workgroup launch (sa_head_bwd)
+        self.wide_head_bwd = os.environ.get("SA_WIDE_HEAD_BWD", "1") == "1"
         # data-parallel FC head: None = every BatchNorm1d of the head exchanges its sums (any batch
         # split); "equal" = every rank holds a batch as large as this one (what data.shard_indices
         # deals); [b0, b1, ...] = the ranks' batch sizes.  With the sizes known the pooled rows are
@@ -405,7 +411,11 @@ class _ConvAEFn(torch.autograd.Function):
         bn1 = bn_stats(st, B * Lb, cls.tdnn[5], "sex_classifier.tdnn.5", 128, 2)
         r2, st = cg(lay["sex_classifier.tdnn.6"], r1, s2=bn1[2], t2=bn1[3], relu=True, want_stats=True)
         bn2 = bn_stats(st, B * Lc, cls.tdnn[8], "sex_classifier.tdnn.8", 128, 3)
-        pooled, pmean, psd = ops.pool_fwd(r2, bn2[2], bn2[3], noise=_noise(model, B, feats.device))
+        if model.fused_pool_fin:
+            nz, raw = ops.pooling_noise_raw(model.pooling_noise, B, 128, feats.device)
+            pooled, pmean, psd = ops.pool_fwd(r2, bn2[2], bn2[3], noise=nz, fused=True, raw=raw)
+        else:
+            pooled, pmean, psd = ops.pool_fwd(r2, bn2[2], bn2[3], noise=_noise(model, B, feats.device))
         def head_fwd(X, n, local=False):
             H1 = ops.dense(X, P["sex_classifier.classify.0.weight"], P["sex_classifier.classify.0.bias"],
                            128, 256, relu=True)
@@ -433,11 +443,13 @@ class _ConvAEFn(torch.autograd.Function):
         logp_all = logp
         if plan:                               # this rank's rows of the global log-probabilities
             logp = logp_all[plan[0]:plan[0] + B]
+        # the BatchNorm step counters: all of them are known here, and issued before the decoder the bump does
+        # not sit between the forward's last kernel and the losses
+        if tracked:
+            torch._foreach_add_(tracked, 1)
         # ---------------- decoder ----------------
         y6, n6, y7, y8, n8, recon = _decoder_launches(model, P, cg, inorm, y5, Ltot)
 
-        if tracked:
-            torch._foreach_add_(tracked, 1)
         S.update(x0=x0, y=[y0, y1, y2, y3, y4, y5, y6, y7, y8], r=[r0, r1, r2],
                  n=[None, n1, n2, n3, n4, None, n6, None, n8], bn=[bn_n, bn0, bn1, bn2], f=[f1, f2],
                  pooled=head_in, pmean=pmean, psd=psd, H1=H1, H2=H2, logp=logp_all, head_plan=plan,
@@ -636,7 +648,8 @@ class _ConvAEFn(torch.autograd.Function):
                     if need[c + k]:
                         views[k] = G[c + k] = newg(c + k)
                 clsP = {k: P[c + k] for k in short}
-                return ops.head_bwd(dlp, S["logp"], S["pooled"], S["H1"], f1, S["H2"], f2, clsP, views)
+                return ops.head_bwd(dlp, S["logp"], S["pooled"], S["H1"], f1, S["H2"], f2, clsP, views,
+                                    wide=model.wide_head_bwd)
             glob = (lambda l: l) if local else (lambda l: model._bn_global(l)[0])
             cd = (lambda i: None) if local else cdev
             dLG = ops.log_softmax_bwd(dlp, S["logp"])

@@ -124,22 +124,76 @@ extern "C" int sa_pool_gather(const float* part, int B, int nseg, int L, double*
 
 // sums [B][128][2] -> pooled [B][256] = (mean + eps*((1-9)*noise+9) if noise, std_unbiased + eps)
 // and saves mean / raw std for the backward.
-__global__ void sa_pool_fin_kernel(const double* __restrict__ sums, int B, int n,
-                                   const float* __restrict__ noise, float eps, float* pooled,
-                                   float* mean, float* stdraw) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 128) return;
-  const int b = i / 128, j = i % 128;
-  const double S = sums[2 * i], Q = sums[2 * i + 1];
+// (S, Q) of pooled column j of utterance b -> its outputs; nz: the column's noise value in [0, 1]
+__device__ __forceinline__ void sa_pool_finish(double S, double Q, int b, int j, int n, bool has_noise, float nz,
+                                               float eps, float* pooled, float* mean, float* stdraw) {
+  const int i = b * 128 + j;
   const double m = S / n;
   double var = (Q - S * m) / (n - 1);
   if (var < 0.0) var = 0.0;
   const float sd = (float)sqrt(var);
   mean[i] = (float)m; stdraw[i] = sd;
   float mo = (float)m;
-  if (noise) mo += eps * ((1.0f - 9.0f) * noise[i] + 9.0f);
+  if (has_noise) mo += eps * ((1.0f - 9.0f) * nz + 9.0f);
   pooled[(size_t)b * 256 + j] = mo;
   pooled[(size_t)b * 256 + 128 + j] = sd + eps;
+}
+
+__global__ void sa_pool_fin_kernel(const double* __restrict__ sums, int B, int n,
+                                   const float* __restrict__ noise, float eps, float* pooled,
+                                   float* mean, float* stdraw) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * 128) return;
+  sa_pool_finish(sums[2 * i], sums[2 * i + 1], i / 128, i % 128, n, noise != nullptr, noise ? noise[i] : 0.0f, eps,
+                 pooled, mean, stdraw);
+}
+
+// sa_pool_gather with sa_pool_fin in its tail: the h == 0 threads hold (s, q) of their column in fp64 and run
+// the finaliser's operations on them (one launch less, no round trip of sums).  raw != 0: noise is the N(0,1)
+// draw g [B][128] itself and is normalised here, noise_i = fl(fl(g_i - m) / fl(max g - m)), m = min g over all
+// B*128 values -- the bits of `g = g - g.min(); g / g.max()` (rounding is monotone: max_i fl(g_i - m) =
+// fl(max g - m)); every workgroup reduces the B*128 values itself.
+__global__ __launch_bounds__(1024) void sa_pool_gather_fin_kernel(const float* __restrict__ part, int nseg, int L,
+                                                                  int B, const float* __restrict__ noise, int raw,
+                                                                  float eps, float* pooled, float* mean,
+                                                                  float* stdraw) {
+  __shared__ double grp[7][128][2];
+  __shared__ float wmin[16], wmax[16];
+  const int tid = threadIdx.x, b = blockIdx.x, j = tid & 127, h = tid >> 7, Lm = L % 128;
+  float gmin = 0.0f, gmax = 0.0f;
+  if (noise && raw) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = tid; i < B * 128; i += 1024) { const float g = noise[i]; lo = fminf(lo, g); hi = fmaxf(hi, g); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o)); hi = fmaxf(hi, __shfl_xor(hi, o)); }
+    if ((tid & 63) == 0) { wmin[tid >> 6] = lo; wmax[tid >> 6] = hi; }
+  }
+  double s = 0.0, q = 0.0;
+  for (int seg = 0; seg < nseg; ++seg) {
+    const float2* p = reinterpret_cast<const float2*>(part) + ((size_t)b * nseg + seg) * 128 * 128;
+#pragma unroll 16
+    for (int c = h * 16; c < h * 16 + 16; ++c) {
+      const float2 v = p[(size_t)c * 128 + ((j - c * Lm) & 127)];
+      s += v.x; q += v.y;
+    }
+  }
+  if (h > 0) { grp[h - 1][j][0] = s; grp[h - 1][j][1] = q; }
+  __syncthreads();
+  if (h == 0) {
+#pragma unroll
+    for (int g = 0; g < 7; ++g) { s += grp[g][j][0]; q += grp[g][j][1]; }
+    float nz = 0.0f;
+    if (noise) {
+      nz = noise[b * 128 + j];
+      if (raw) {
+        gmin = wmin[0]; gmax = wmax[0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) { gmin = fminf(gmin, wmin[w]); gmax = fmaxf(gmax, wmax[w]); }
+        nz = __fdiv_rn(__fsub_rn(nz, gmin), __fsub_rn(gmax, gmin));
+      }
+    }
+    sa_pool_finish(s, q, b, j, L, noise != nullptr, nz, eps, pooled, mean, stdraw);
+  }
 }
 
 extern "C" int sa_pool_fin(const double* sums, int B, int n, const float* noise, float eps,
@@ -148,6 +202,15 @@ extern "C" int sa_pool_fin(const double* sums, int B, int n, const float* noise,
   hipLaunchKernelGGL(sa_pool_fin_kernel, dim3(sa_div_up(B * 128, 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), sums, B, n, noise, eps, pooled, mean,
                      stdraw);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+extern "C" int sa_pool_gather_fin(const float* part, int B, int nseg, int L, const float* noise, int raw,
+                                  float eps, float* pooled, float* mean, float* stdraw, void* stream) {
+  if (!part || !pooled || !mean || !stdraw || B <= 0 || nseg < 1 || L < 2) return -22;
+  hipLaunchKernelGGL(sa_pool_gather_fin_kernel, dim3(B), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream),
+                     part, nseg, L, B, noise, raw, eps, pooled, mean, stdraw);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
@@ -440,10 +503,13 @@ extern "C" int sa_log_softmax_bwd(const float* dY, const float* Y, float* dX, in
 // ---------------------------------------------------------------------------------
 // recon loss: mean over N of |a-b| (kind 0, nn.L1Loss) or (a-b)^2 (kind 1, nn.MSELoss);
 // grad[i] = d loss / d a[i].  Two-level deterministic reduction: part[block] then one thread.
+// SCALED: the stored gradient is fl(gscale * g), g the value the unscaled kernel stores -- the two roundings
+// of `grad * weight` as a separate pass over the tensor (sa_recon_loss_part, the step's native loss tail)
+template <bool SCALED>
 __global__ __launch_bounds__(256) void sa_recon_loss_kernel(const float* __restrict__ a,
                                                             const float* __restrict__ b, size_t n,
                                                             int kind, float* __restrict__ grad,
-                                                            double* __restrict__ part) {
+                                                            double* __restrict__ part, float gscale) {
   __shared__ double wsum[4];
   const float inv = 1.0f / (float)n;
   double s = 0.0;
@@ -455,14 +521,18 @@ __global__ __launch_bounds__(256) void sa_recon_loss_kernel(const float* __restr
     for (int j = 0; j < 4; ++j) {
       if (kind == 0) { s += fabsf(d[j]); g[j] = d[j] > 0.f ? inv : (d[j] < 0.f ? -inv : 0.f); }
       else { s += (double)d[j] * d[j]; g[j] = 2.0f * d[j] * inv; }
+      if (SCALED) g[j] = __fmul_rn(g[j], gscale);
     }
     if (grad) reinterpret_cast<float4*>(grad)[i] = make_float4(g[0], g[1], g[2], g[3]);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
     for (size_t i = n4 * 4; i < n; ++i) {
       const float d = a[i] - b[i];
-      if (kind == 0) { s += fabsf(d); if (grad) grad[i] = d > 0.f ? inv : (d < 0.f ? -inv : 0.f); }
-      else { s += (double)d * d; if (grad) grad[i] = 2.0f * d * inv; }
+      float g;
+      if (kind == 0) { s += fabsf(d); g = d > 0.f ? inv : (d < 0.f ? -inv : 0.f); }
+      else { s += (double)d * d; g = 2.0f * d * inv; }
+      if (SCALED) g = __fmul_rn(g, gscale);
+      if (grad) grad[i] = g;
     }
   s = sa_wave_sum_d(s);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
@@ -485,19 +555,37 @@ __global__ void sa_recon_loss_fin_kernel(const double* part, int nb, double n, f
 }
 #define SA_LOSS_BLOCKS 512
 extern "C" int sa_loss_workspace_bytes() { return SA_LOSS_BLOCKS * (int)sizeof(double); }
+// workgroups (= partial sums in the workspace) of the reduction over n elements
+static int sa_loss_nblocks(long long n) {
+  long long nb = (n / 4 + 255) / 256;
+  return nb < 1 ? 1 : (nb > SA_LOSS_BLOCKS ? SA_LOSS_BLOCKS : (int)nb);
+}
 extern "C" int sa_recon_loss(const float* a, const float* b, long long n, int kind, float* grad,
                              float* loss, void* workspace, void* stream) {
   if (!a || !b || !loss || !workspace || n <= 0) return -22;
   if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
        reinterpret_cast<uintptr_t>(grad)) & 15) return -22;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int nb = (int)((n / 4 + 255) / 256);
-  if (nb < 1) nb = 1;
-  if (nb > SA_LOSS_BLOCKS) nb = SA_LOSS_BLOCKS;
-  hipLaunchKernelGGL(sa_recon_loss_kernel, dim3(nb), dim3(256), 0, st, a, b, (size_t)n, kind, grad,
-                     reinterpret_cast<double*>(workspace));
+  const int nb = sa_loss_nblocks(n);
+  hipLaunchKernelGGL(sa_recon_loss_kernel<false>, dim3(nb), dim3(256), 0, st, a, b, (size_t)n, kind, grad,
+                     reinterpret_cast<double*>(workspace), 1.0f);
   hipLaunchKernelGGL(sa_recon_loss_fin_kernel, dim3(1), dim3(64), 0, st,
                      reinterpret_cast<const double*>(workspace), nb, (double)n, loss);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+// The first half of sa_recon_loss for the step's native loss tail: the per-block partial sums stay in the
+// workspace for sa_step_loss, and the gradient is stored already multiplied by the loss weight's gradient
+// (grad[i] = fl(gscale * g_i): what `grad * weight` gives in a pass of its own).
+extern "C" int sa_recon_loss_part(const float* a, const float* b, long long n, int kind, float* grad,
+                                  float gscale, void* workspace, void* stream) {
+  if (!a || !b || !workspace || n <= 0) return -22;
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
+       reinterpret_cast<uintptr_t>(grad)) & 15) return -22;
+  hipLaunchKernelGGL(sa_recon_loss_kernel<true>, dim3(sa_loss_nblocks(n)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a, b, (size_t)n, kind, grad,
+                     reinterpret_cast<double*>(workspace), gscale);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }
@@ -535,6 +623,63 @@ extern "C" int sa_cls_losses(const float* logp, const long long* label, int B, i
   if (!logp || !label || !out) return -22;
   hipLaunchKernelGGL(sa_cls_losses_kernel, dim3(1), dim3(64), 0,
                      reinterpret_cast<hipStream_t>(stream), logp, label, B, NC, out, dnll, dconf);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+// The loss tail of the ConvAE train step in one launch: sa_recon_loss_fin + sa_cls_losses (NLL only) + the
+// weighted sum total = fl(fl(wr*recon) + fl(ws*sex)) + 0.0f (the fp32 operations of `wr * recon + ws * sex + 0.0`
+// on 0-dim tensors) + the gradient autograd hands back to log p, dlogp = dnll * fl(1.0f * ws), + the non-finite
+// counter (`counter += !isfinite(total)`).  part: the partial sums sa_recon_loss_part left in the workspace.
+// out = (recon, sex, total).
+// Three separately rounded operations, as three element-wise kernels compute them: contraction is switched off
+// for this block (hipcc contracts a * b + c into an fma by default, and __fmul_rn / __fadd_rn are plain
+// operators to it), which would round fl(wr*recon) away.
+__device__ __forceinline__ float sa_weighted_total(float wr, float recon, float ws, float sex) {
+#pragma clang fp contract(off)
+  const float a = wr * recon;
+  const float b = ws * sex;
+  const float s = a + b;
+  return s + 0.0f;
+}
+__global__ __launch_bounds__(64) void sa_step_loss_kernel(const double* __restrict__ part, int nb, double n,
+                                                          const float* __restrict__ logp,
+                                                          const long long* __restrict__ label, int B, int NC,
+                                                          float wr, float ws, float* __restrict__ out,
+                                                          float* __restrict__ dlogp, int* nonfinite) {
+  __shared__ double lane_sum[64], pn[64];
+  const int t = threadIdx.x;
+  double s = 0.0;
+#pragma unroll 8
+  for (int i = t; i < nb; i += 64) s += part[i];
+  const float gs = __fmul_rn(1.0f, ws);
+  double nll = 0.0;
+  for (int e = t; e < B * NC; e += 64) {
+    const int b = e / NC, c = e % NC;
+    const float lp = logp[e];
+    const bool hit = (long long)c == label[b];
+    if (hit) nll -= lp;
+    if (dlogp) dlogp[e] = __fmul_rn(hit ? -1.0f / (float)B : 0.0f, gs);
+  }
+  lane_sum[t] = s; pn[t] = nll;
+  __syncthreads();
+  if (t == 0) {
+    double r = 0.0, a = 0.0;
+    for (int i = 0; i < 64; ++i) r += lane_sum[i];
+    for (int i = 0; i < 64; ++i) a += pn[i];
+    const float recon = (float)(r / n), sex = (float)(a / B);
+    const float total = sa_weighted_total(wr, recon, ws, sex);
+    out[0] = recon; out[1] = sex; out[2] = total;
+    if (nonfinite && !isfinite(total)) *nonfinite += 1;
+  }
+}
+extern "C" int sa_step_loss(const void* workspace, long long n, const float* logp, const long long* label,
+                            int B, int NC, float w_recon, float w_sex, float* out, float* dlogp,
+                            int* nonfinite, void* stream) {
+  if (!workspace || !logp || !label || !out || n <= 0 || B <= 0 || NC <= 0) return -22;
+  hipLaunchKernelGGL(sa_step_loss_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const double*>(workspace), sa_loss_nblocks(n), (double)n, logp, label, B, NC,
+                     w_recon, w_sex, out, dlogp, nonfinite);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : -(int)e;
 }

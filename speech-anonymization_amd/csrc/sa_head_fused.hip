@@ -354,4 +354,148 @@ extern "C" int sa_head_bwd(const float* dlogp, const float* logp, const float* p
   return e == hipSuccess ? 0 : -(int)e;
 }
 
+// The same backward over SA_HEAD_BWD_WG workgroups.  One workgroup spends most of its time in the two wide
+// products at the end (d W1: M dependent global loads of pooled per thread; d pooled: 128 of W1) with the rest
+// of the chip idle.  Here every workgroup recomputes the short dependent chain (d logits -> d N2 -> BatchNorm
+// backward -> d N1 -> BatchNorm backward: the operations of sa_head_bwd_kernel in its own LDS, no hand-off
+// between workgroups) and then takes a slice of the outputs: workgroup g owns SA_HEAD_BWD_KS columns k of
+// pooled -- those columns of d W1 and of d pooled -- and 1/SA_HEAD_BWD_WG of d W2; the small vectors and d W3
+// are written by workgroup 0.  Its columns of W1 and pooled are fetched at the top of the kernel (one float4
+// per thread, in flight while the chain runs) and read from LDS in the long loops.  Every output element is
+// accumulated in the order of the one-workgroup kernel (ascending m, ascending n), so the bits are the same.
+#define SA_HEAD_BWD_WG 16
+constexpr int HB_KS = K0 / SA_HEAD_BWD_WG;                  // 16 pooled columns per workgroup
+
+__global__ __launch_bounds__(1024) void sa_head_bwd_wide_kernel(SaHeadBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int M = a.M, tid = threadIdx.x, wg = blockIdx.x, kbase = wg * HB_KS;
+  const bool first = wg == 0;
+  float* H1 = reinterpret_cast<float*>(smem);               // [M][128] forward activation (post-ReLU)
+  float* H2 = H1 + M * N1;                                  // [M][64]
+  float* D1 = H2 + M * N2;                                  // [M][128] d N1 -> d H1
+  float* D2 = D1 + M * N1;                                  // [M][64]  d N2 -> d H2
+  float* DL = D2 + M * N2;                                  // [M][2]   d logits
+  float* Ws = DL + SA_HEAD_MAXB * NC;                       // [128][HB_KS] this workgroup's columns of W1
+  float* Xs = Ws + N1 * HB_KS;                              // [M][HB_KS]   ... and of pooled
+  // this workgroup's operand slices: threads 0..511 one float4 of W1, threads 512..512+4M-1 one of pooled
+  constexpr int Q = HB_KS / 4;                              // float4 per slice row
+  float4 stage = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const int sw = tid, sx = tid - N1 * Q;
+  if (sw < N1 * Q) stage = *reinterpret_cast<const float4*>(a.w1 + (size_t)(sw / Q) * K0 + kbase + 4 * (sw % Q));
+  else if (sx < M * Q) stage = *reinterpret_cast<const float4*>(a.pooled + (size_t)(sx / Q) * K0 + kbase + 4 * (sx % Q));
+  for (int i = tid; i < M * N1 / 4; i += 1024) reinterpret_cast<float4*>(H1)[i] = reinterpret_cast<const float4*>(a.h1)[i];
+  for (int i = tid; i < M * N2 / 4; i += 1024) reinterpret_cast<float4*>(H2)[i] = reinterpret_cast<const float4*>(a.h2)[i];
+  if (tid < M) {                                            // d logits = d logp - exp(logp) * sum_c d logp
+    const float d0 = a.dlogp[tid * NC], d1 = a.dlogp[tid * NC + 1], s = d0 + d1;
+    DL[tid * NC] = d0 - expf(a.logp[tid * NC]) * s;
+    DL[tid * NC + 1] = d1 - expf(a.logp[tid * NC + 1]) * s;
+  }
+  __syncthreads();
+  const float* s2 = a.f2 + 2 * N2; const float* t2 = a.f2 + 3 * N2;
+  const float* s1 = a.f1 + 2 * N1; const float* t1 = a.f1 + 3 * N1;
+  if (first) {                                              // d W3, d b3
+    if (tid < NC * N2) {
+      const int c = tid / N2, k = tid % N2;
+      float acc = 0.0f;
+      for (int m = 0; m < M; ++m) acc = fmaf(DL[m * NC + c], fmaf(H2[m * N2 + k], s2[k], t2[k]), acc);
+      if (a.dw3) a.dw3[tid] = acc;
+    } else if (tid < NC * N2 + NC) {
+      const int c = tid - NC * N2;
+      float acc = 0.0f;
+      for (int m = 0; m < M; ++m) acc += DL[m * NC + c];
+      if (a.db3) a.db3[c] = acc;
+    }
+  }
+  for (int i = tid; i < M * N2; i += 1024) {
+    const int m = i / N2, k = i % N2;
+    D2[i] = fmaf(DL[m * NC], a.w3[k], DL[m * NC + 1] * a.w3[N2 + k]);
+  }
+  __syncthreads();
+  if (tid < N2) head_bn_bwd(D2, H2, M, N2, tid, a.f2, a.g2, first ? a.dg2 : nullptr, first ? a.dbe2 : nullptr);
+  __syncthreads();
+  // d W2[n][k]: this workgroup's 1/SA_HEAD_BWD_WG of the 64 x 128 outputs; d b2: workgroup 0
+  if (a.dw2) {
+    constexpr int PER = N2 * N1 / SA_HEAD_BWD_WG;
+    for (int j = tid; j < PER; j += 1024) {
+      const int i = wg * PER + j, n = i / N1, k = i % N1;
+      float acc = 0.0f;
+      const float sk = s1[k], tk = t1[k];
+      for (int m = 0; m < M; ++m) acc = fmaf(D2[m * N2 + n], fmaf(H1[m * N1 + k], sk, tk), acc);
+      a.dw2[i] = acc;
+    }
+  }
+  if (first && tid < N2 && a.db2) {
+    float acc = 0.0f;
+    for (int m = 0; m < M; ++m) acc += D2[m * N2 + tid];
+    a.db2[tid] = acc;
+  }
+  // d N1[m][k] = sum_n dH2[m][n] * W2[n][k]
+  for (int i = tid; i < M * N1; i += 1024) {
+    const int m = i / N1, k = i % N1;
+    float acc = 0.0f;
+#pragma unroll 8
+    for (int n = 0; n < N2; ++n) acc = fmaf(D2[m * N2 + n], a.w2[n * N1 + k], acc);
+    D1[i] = acc;
+  }
+  // the operand slices fetched at the top go to LDS now (their loads have had the chain to arrive)
+  if (sw < N1 * Q) *reinterpret_cast<float4*>(Ws + 4 * sw) = stage;
+  else if (sx < M * Q) *reinterpret_cast<float4*>(Xs + 4 * sx) = stage;
+  __syncthreads();
+  if (tid < N1) head_bn_bwd(D1, H1, M, N1, tid, a.f1, a.g1, first ? a.dg1 : nullptr, first ? a.dbe1 : nullptr);
+  __syncthreads();
+  // d W1[n][kbase + kk] = sum_m dH1[m][n] * pooled[m][kbase + kk]: 128 x HB_KS outputs, thread = (n, k quad)
+  if (a.dw1 && tid < N1 * Q) {
+    const int n = tid / Q, kq = tid % Q;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    for (int m = 0; m < M; ++m) {
+      const float4 x = *reinterpret_cast<const float4*>(Xs + m * HB_KS + 4 * kq);
+      const float d = D1[m * N1 + n];
+      a0 = fmaf(d, x.x, a0); a1 = fmaf(d, x.y, a1); a2 = fmaf(d, x.z, a2); a3 = fmaf(d, x.w, a3);
+    }
+    *reinterpret_cast<float4*>(a.dw1 + (size_t)n * K0 + kbase + 4 * kq) = make_float4(a0, a1, a2, a3);
+  }
+  if (first && tid >= 512 && tid < 512 + N1 && a.db1) {    // d b1[n] = sum_m dH1[m][n]
+    const int n = tid - 512;
+    float acc = 0.0f;
+    for (int m = 0; m < M; ++m) acc += D1[m * N1 + n];
+    a.db1[n] = acc;
+  }
+  // d pooled[m][kbase + kk] = sum_n dH1[m][n] * W1[n][kbase + kk]: M x HB_KS outputs, thread = (m, kk)
+  if (a.dpooled) {
+    const int kk = tid % HB_KS, m = tid / HB_KS;            // 1024 / 16 = 64 = SA_HEAD_MAXB rows
+    if (m < M) {
+      float acc = 0.0f;
+#pragma unroll 8
+      for (int n = 0; n < N1; ++n) acc = fmaf(D1[m * N1 + n], Ws[n * HB_KS + kk], acc);
+      a.dpooled[(size_t)m * K0 + kbase + kk] = acc;
+    }
+  }
+}
+
+// sa_head_bwd's arguments, sa_head_bwd's bits
+extern "C" int sa_head_bwd_wide(const float* dlogp, const float* logp, const float* pooled, const float* h1,
+                                const float* f1, const float* h2, const float* f2, const float* w1, const float* g1,
+                                const float* w2, const float* g2, const float* w3, float* dw1, float* db1,
+                                float* dg1, float* dbe1, float* dw2, float* db2, float* dg2, float* dbe2,
+                                float* dw3, float* db3, float* dpooled, int M, void* stream) {
+  if (!dlogp || !logp || !pooled || !h1 || !f1 || !h2 || !f2 || !w1 || !g1 || !w2 || !g2 || !w3 || M < 1 ||
+      M > SA_HEAD_MAXB)
+    return -22;
+  SaHeadBwdArgs a{dlogp, logp, pooled, h1, f1, h2, f2, w1, g1, w2, g2, w3,
+                  dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dw3, db3, dpooled, M};
+  static_assert(1024 / HB_KS >= SA_HEAD_MAXB && (N1 + SA_HEAD_MAXB) * HB_KS / 4 <= 1024, "slice geometry");
+  const size_t lds = ((size_t)M * (2 * N1 + 2 * N2 + HB_KS) + SA_HEAD_MAXB * NC + N1 * HB_KS) * sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sa_head_bwd_wide_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return -(int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(sa_head_bwd_wide_kernel, dim3(SA_HEAD_BWD_WG), dim3(1024), lds,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
 extern "C" int sa_head_max_rows(void) { return SA_HEAD_MAXB; }

@@ -552,18 +552,36 @@ def pooling_noise(setting, B, Cc, device):
     return (g / g.max()).contiguous()
 
 
-def pool_fwd(r, scale, shift, noise=None, eps=1e-5):
+def pooling_noise_raw(setting, B, Cc, device):
+    """pooling_noise for pool_fwd(fused=True): (noise, raw).  True draws the same torch.randn and hands it over
+    as it is (raw = True: sa_pool_gather_fin normalises it, the bits of pooling_noise's three ATen steps)."""
+    if setting is True:
+        return torch.randn(B, Cc, device=device), True
+    return pooling_noise(setting, B, Cc, device), False
+
+
+def pool_fwd(r, scale, shift, noise=None, eps=1e-5, fused=False, raw=False):
+    """fused: sa_pool_gather_fin instead of sa_pool_gather + sa_pool_fin (same bits); raw (fused only): noise is
+    the N(0,1) draw, normalised to [0, 1] in that launch"""
     lib = L.load()
     B, Ln, _ = r.shape
     nseg = lib.sa_pool_nseg(B)
     part = torch.empty(B, nseg, 128, 128, 2, dtype=torch.float32, device=r.device)
     L.check(lib.sa_pool_fwd(L.dt_code(r.dtype), _f(r), _f(scale), _f(shift), _f(part), B, Ln, nseg,
                             L.stream()), "sa_pool_fwd")
-    sums = torch.empty(B, 128, 2, dtype=torch.float64, device=r.device)
-    L.check(lib.sa_pool_gather(_f(part), B, nseg, Ln, _f(sums), L.stream()), "sa_pool_gather")
     pooled = torch.empty(B, 256, dtype=torch.float32, device=r.device)
     mean = torch.empty(B, 128, dtype=torch.float32, device=r.device)
     sd = torch.empty(B, 128, dtype=torch.float32, device=r.device)
+    if fused:
+        if noise is not None and (noise.numel() != B * 128 or noise.dtype != torch.float32):
+            raise L.SaHipError(f"pooling noise must be fp32 [{B}, 128], got {noise.dtype} {tuple(noise.shape)}")
+        L.check(lib.sa_pool_gather_fin(_f(part), B, nseg, Ln, _f(noise), int(bool(raw)), C.c_float(eps), _f(pooled),
+                                       _f(mean), _f(sd), L.stream()), "sa_pool_gather_fin")
+        return pooled, mean, sd
+    if raw:
+        raise L.SaHipError("raw pooling noise needs fused=True")
+    sums = torch.empty(B, 128, 2, dtype=torch.float64, device=r.device)
+    L.check(lib.sa_pool_gather(_f(part), B, nseg, Ln, _f(sums), L.stream()), "sa_pool_gather")
     L.check(lib.sa_pool_fin(_f(sums), B, Ln, _f(noise), C.c_float(eps), _f(pooled), _f(mean), _f(sd),
                             L.stream()), "sa_pool_fin")
     return pooled, mean, sd
@@ -648,17 +666,20 @@ def head_fwd(pooled, P, bn1, bn2, eps=1e-5, momentum=0.1):
     return H1, tuple(f1[i] for i in range(4)), H2, tuple(f2[i] for i in range(4)), logp
 
 
-def head_bwd(dlogp, logp, pooled, H1, f1, H2, f2, P, grads):
+def head_bwd(dlogp, logp, pooled, H1, f1, H2, f2, P, grads, wide=False):
     """sa_head_bwd: grads maps the short parameter names to fp32 gradient views (or None); returns dpooled.
-    f1 / f2: the tuples head_fwd returned (rows of one [4][N] tensor)."""
+    f1 / f2: the tuples head_fwd returned (rows of one [4][N] tensor).  wide: sa_head_bwd_wide, the same
+    backward (same bits) over 16 workgroups."""
     M = pooled.shape[0]
     dpooled = torch.empty(M, 256, dtype=torch.float32, device=pooled.device)
     g = lambda k: _f(grads.get(k))
-    L.check(L.load().sa_head_bwd(_f(dlogp), _f(logp), _f(pooled), _f(H1), _f(f1[0]), _f(H2), _f(f2[0]),
-                                 _f(P["0.weight"]), _f(P["2.weight"]), _f(P["3.weight"]), _f(P["5.weight"]),
-                                 _f(P["6.weight"]), g("0.weight"), g("0.bias"), g("2.weight"), g("2.bias"),
-                                 g("3.weight"), g("3.bias"), g("5.weight"), g("5.bias"), g("6.weight"), g("6.bias"),
-                                 _f(dpooled), M, L.stream()), "sa_head_bwd")
+    lib = L.load()
+    entry, name = (lib.sa_head_bwd_wide, "sa_head_bwd_wide") if wide else (lib.sa_head_bwd, "sa_head_bwd")
+    L.check(entry(_f(dlogp), _f(logp), _f(pooled), _f(H1), _f(f1[0]), _f(H2), _f(f2[0]),
+                  _f(P["0.weight"]), _f(P["2.weight"]), _f(P["3.weight"]), _f(P["5.weight"]),
+                  _f(P["6.weight"]), g("0.weight"), g("0.bias"), g("2.weight"), g("2.bias"),
+                  g("3.weight"), g("3.bias"), g("5.weight"), g("5.bias"), g("6.weight"), g("6.bias"),
+                  _f(dpooled), M, L.stream()), name)
     return dpooled
 
 
@@ -702,6 +723,33 @@ def cls_losses(logp, label, want_grad=True):
     L.check(lib.sa_cls_losses(_f(logp), _f(label), B, NC, _f(out), _f(dn), _f(dc), L.stream()),
             "sa_cls_losses")
     return out, dn, dc
+
+
+def step_loss(pred, target, kind, logp, label, w_recon, w_sex, nonfinite=None):
+    """The loss tail of the ConvAE train step in two launches (sa_recon_loss_part + sa_step_loss) instead of
+    recon_loss + cls_losses + the weighted sum, its autograd graph and the non-finite count on ATen kernels.
+    pred / target: contiguous fp32 of one shape; logp [B, NC]; label int64 [B]; nonfinite: the device int32
+    counter that receives `+= !isfinite(total)` (or None).  Returns out = (recon, sex, total) and the gradients
+    the scalar graph would hand to pred and logp, bit for bit: d_pred = g * fl(1.0f * w_recon) with g the
+    gradient recon_loss returns, d_logp = dnll * fl(1.0f * w_sex)."""
+    lib = L.load()
+    n = pred.numel()
+    if pred.data_ptr() % 16:
+        pred = pred.clone()
+    if target.data_ptr() % 16:
+        target = target.clone()
+    B, NC = logp.shape
+    dev = pred.device
+    ws = torch.empty(lib.sa_loss_workspace_bytes() // 8, dtype=torch.float64, device=dev)
+    d_pred = torch.empty_like(pred)
+    d_logp = torch.empty_like(logp)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    # (c_float rounds the Python float to fp32 as torch rounds a scalar operand; 1.0f * weight is exact)
+    L.check(lib.sa_recon_loss_part(_f(pred), _f(target), C.c_longlong(n), 0 if kind == "l1" else 1, _f(d_pred),
+                                   C.c_float(w_recon), _f(ws), L.stream()), "sa_recon_loss_part")
+    L.check(lib.sa_step_loss(_f(ws), C.c_longlong(n), _f(logp), _f(label), B, NC, C.c_float(w_recon),
+                             C.c_float(w_sex), _f(out), _f(d_logp), _f(nonfinite), L.stream()), "sa_step_loss")
+    return out, d_pred, d_logp
 
 
 def cosine_loss(x1, x2, want_grad=False):
