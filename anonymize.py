@@ -5,7 +5,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
     python anonymize.py speechbrain_configs/convae.yaml --device cuda:0 --model_type convae|fcae|endtoend \
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
-        [--psola true]
+        [--psola true] [--formant_norm true [--formant_target F1,F2,F3]] [--formant_norm_ratio X]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
         [--report_formants true]
 
@@ -34,6 +34,18 @@ model and reads no checkpoint either: OUT receives the McAdams-transformed wavef
 and timing untouched, no Griffin-Lim.  It takes none of --pitch_norm, --formant_ratio, --preserve_formants,
 --recon_ckpt and --passthrough.  Its JSON line carries ``"mcadams": true`` and per utterance ``alpha``, ``gain``,
 ``silent_frames``, ``fallback_frames`` and ``peak``.
+
+``--formant_norm true [--formant_target F1,F2,F3] [--formant_q_min A --formant_q_max B] [--f0_method M]`` (or
+``--formant_norm_ratio X``, which implies the mode: one ratio for all) runs no model and reads no checkpoint either: OUT
+receives the formant-normalised waveforms (speech_anonymization_amd.formantnorm) -- every utterance's
+formants are tracked on its voiced frames, the ratio q that brings the geometric mean of their medians to the target's
+(default 550,1650,2750 Hz, a convention) is clamped to [A, B] (default 0.8, 1.2), and every frame's complex LPC poles
+move from angle phi to q phi; pitch and timing untouched, no Griffin-Lim.  It takes none of --mcadams, --recon_ckpt,
+--passthrough, --formant_ratio, --preserve_formants and --phase; with ``--pitch_norm true`` it needs ``--psola true``,
+the pitch path that keeps the envelope, and PSOLA then runs on the normalised waveform.  Its JSON line carries
+``"formant_norm": true`` and per utterance ``q``, ``gain``, ``formant_frames_in`` (0 when the utterance had fewer than
+8 scored frames and was left as it is), ``f1_in_hz``, ``f2_in_hz``, ``f3_in_hz`` (the input's median formants, null
+when not scored), ``silent_frames``, ``fallback_frames`` and ``peak``.
 
 ``--phase vocoder`` (with --pitch_norm true and/or --formant_ratio X) carries the input's own phases through the
 stretch instead of reconstructing them with Griffin-Lim (speech_anonymization_amd.ops.pv_synth):
@@ -103,7 +115,7 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, features, gender, mcadams, pitchnorm, reports, vocoder
+from speech_anonymization_amd import data, features, formantnorm, gender, mcadams, pitchnorm, reports, vocoder
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -177,6 +189,39 @@ def _mcadams(settings, device, bs, seed):
     return step, {"mcadams": True}, {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
 
 
+def _formant_norm(settings, device, bs, seed):
+    """--formant_norm true / --formant_norm_ratio X: every utterance's LPC pole angles scaled by the ratio that brings
+    its formants to the target (by X) and written, no model; with --pitch_norm true --psola true the result's pitch is
+    then normalised in the time domain"""
+    opts = formantnorm.check_formant_norm_options(settings)
+    fn = formantnorm.FormantNormalizer(**opts)
+    pn, head, tail = None, {"formant_norm": True}, {}
+    if settings.get("pitch_norm"):
+        contour = pitchnorm.check_contour_options(settings)
+        pn = pitchnorm.PitchNormalizer(target_hz=float(settings.get("pitch_target_hz", 170.0)), psola=True,
+                                       f0_method=opts["f0_method"], **contour)
+        head.update(pitch_norm=True, pitch_target_hz=pn.target_hz, n_iter=None)
+        tail = dict(contour, psola=True)
+
+    def step(ids, wavs, lens):
+        out = fn(wavs, lens)
+        q, med, count, gain, counts = (v.cpu().tolist() for v in fn.last)
+        extra = [dict({"q": q[i], "gain": gain[i], "formant_frames_in": count[i], "silent_frames": counts[i][1],
+                       "fallback_frames": counts[i][2]},
+                      **{f"f{k + 1}_in_hz": med[i][k] if count[i] else None for k in range(3)})
+                 for i in range(len(ids))]
+        if pn is not None:
+            out = pn(out, lens)
+            for e, r in zip(extra, pn.last[0].cpu().tolist()):
+                e["ratio"] = r
+        return out, _counts(lens, out.shape[1]), extra, None
+
+    shown = {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items() if k != "f0_method"}
+    if "ratio" in shown:
+        shown = {"formant_norm_ratio": shown["ratio"], "level": shown["level"]}
+    return step, head, dict(shown, **tail)
+
+
 def _model(settings, device, bs, seed):
     """an anonymiser's reconstruction (or with --passthrough true the original features) inverted by Griffin-Lim"""
     mt, passthrough = settings["model_type"], bool(settings.get("passthrough"))
@@ -218,7 +263,7 @@ def _model(settings, device, bs, seed):
                   "n_iter": gl.n_iter, "seed": seed}, {}
 
 
-MODES = {"mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
+MODES = {"formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
          "model": _model}
 
 

@@ -920,6 +920,54 @@ int sa_formant_compare(const float* F_ref, const float* F_deg, const int* st_ref
                        const float* f0_ref, const float* f0_deg, const int* frames, int B, int T, int min_common,
                        float* med, float* ratio, float* shift, int* common, void* stream);
 
+/* ---- LPC formant normalisation (sa_formant_norm.hip; formantnorm.py, ops.pole_warp, ops.formant_centre; DESIGN
+ * section 26): every complex LPC pole's angle scaled by a ratio q per utterance, and the q that brings an utterance's
+ * own tracked formants to a target.  Sample rate 16000.
+ *   sa_pole_warp: wav [B][N] fp32, q [B] fp32, n_valid [B] int32 -> out [B][N] fp32, out != wav.  Everything is
+ *   sa_mcadams's (above), word for word: frames of W = 320 at hop H = 160 under the periodic sqrt-Hann window w,
+ *   T = (N + 159) / 160 + 1 of them, frame t over [160 t - 160, 160 t + 160); a sample outside [0, n_valid_b) reads
+ *   as 0.  Per frame, in fp64:
+ *     f = w x;  r_k = sum_j f[j] f[j + k], k = 0..20;  r_0 < 1e-10: silent (status 1), rec = f;  r_0 *= 1 + 1e-9;
+ *     a[0..20] by Levinson-Durbin; some |k_i| >= 1 or a prediction error <= 0: fallback (status 2), rec = f;
+ *     the 20 roots z of a by Aberth-Ehrlich from 0.9 exp(2 pi i (j + 0.25) / 20), stopped when the largest
+ *       correction is under 1e-14, given up (fallback) after 64 iterations;  a root is real when
+ *       |Im z| <= 1e-6 |z|, kept when Im z > 1e-6 |z|, dropped otherwise;  2 kept + real != 20: fallback;
+ *     a' = prod_real (1 - Re z x) prod_kept (1 - 2 |z| cos(phi') x + |z|^2 x^2), phi = arg z and
+ *       phi' = q phi                                               for phi <= phi0,
+ *       phi' = q phi0 + (pi - q phi0) (phi - phi0) / (pi - phi0)   above it,   phi0 = 0.85 pi min(1, 1 / q):
+ *       continuous, strictly increasing, (0, pi) onto itself; |z| and the real poles are kept;
+ *     res = FIR(a) f, rec = IIR(1 / a') res, both from zero history;  the frame stored is fp32(rec w).
+ *   y[n] = F_t0[n - 160 t0 + 160] + F_{t0 + 1}[n - 160 t0], t0 = n / 160 (fp32);  out[n] = fp32(g_b y[n]) for
+ *   n < n_valid_b and 0 from there on;  level != 0: g_b = sqrt(sum x^2 / sum y^2) over n < n_valid_b (fp64, a fixed
+ *   order; 1 when either sum is 0), else 1.  q is read on the device: a value outside [0.5, 2] is taken as the nearer
+ *   bound, a NaN as 1; a row whose q is 1 is copied bit for bit below n_valid_b (gain 1, status 0).  n_valid_b is
+ *   clamped to [0, N].  The same bits on every run.
+ *   ws: the caller's, 4 B T 320 + 8 (2 B ceil(N / C) + B) bytes, 8-byte aligned, C = sa_pole_warp_dim(6); its
+ *     contents mean nothing between calls.  status: NULL, or int32 [B][T].  gain: NULL, or fp32 [B].
+ *   sa_pole_warp_dim(which): 0 W 320, 1 H 160, 2 P 20, 3 frames per workgroup, 4 threads per workgroup, 5 the largest
+ *     iteration count 64, 6 samples per block of the level sums, 7 the knee 0.85 in thousandths (850); else -EINVAL.
+ *   -EINVAL, before any launch: a NULL pointer (status and gain may be NULL), B < 1 or > 65535 (grid.y), N < 1 or
+ *     > 2^30, T > 2^23.
+ *   sa_formant_centre: freq [B][T][3] fp32 and status [B][T] int32 (one output of sa_formant_tracks); f0 [B][T] fp32 in
+ *   Hz, 0 or less meaning unvoiced, or NULL: every frame voiced; frames [B] int32, clamped where it is read to F_b in
+ *   [0, T]; the target t1 < t2 < t3 in Hz; q_min <= 1 <= q_max; min_frames m >= 1.
+ *     Frame t counts when t < F_b, status[t] = 0 and f0[t] > 0; n of them do.
+ *     n >= m:  med_k = the lower median of freq[t][k] over the counted frames, the element at index (n - 1) / 2 of the
+ *       sorted values (an element of the track: exact);
+ *       q = fp32(clamp(exp((ln(t1 / med_1) + ln(t2 / med_2) + ln(t3 / med_3)) / 3), q_min, q_max)) in fp64 (exactly 1
+ *       when the medians are the target; 1 when the value is a NaN, which takes a median of 0 or less);  count = n.
+ *     n < m:  med = 0, q = 1, count = 0: the row is left as it is.
+ *   -> med [B][3] fp32, q [B] fp32, count [B] int32.  med and count may be NULL.  One workgroup of 16 waves per row, the
+ *   medians by sa_formant_compare's bitwise select on three keys; no workspace, no atomics, the same bits on every run.
+ *   -EINVAL, before any launch: a NULL required pointer, B < 1 or > 65535, T < 1 or > 104858, a target that is not
+ *     90 <= t1 < t2 < t3 <= 5500, bounds that are not 0.5 <= q_min <= 1 <= q_max <= 2, min_frames < 1. */
+int sa_pole_warp_dim(int which);
+int sa_pole_warp(const float* wav, const float* q, const int* n_valid, int B, int N, int level, float* out, void* ws,
+                 int* status, float* gain, void* stream);
+int sa_formant_centre(const float* freq, const int* status, const float* f0, const int* frames, int B, int T, float t1,
+                      float t2, float t3, float q_min, float q_max, int min_frames, float* med, float* q, int* count,
+                      void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

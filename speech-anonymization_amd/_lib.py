@@ -131,6 +131,7 @@ SYMBOLS = [
     "sa_mcd_dim", "sa_mcd",
     "sa_psola_dim", "sa_psola_marks", "sa_psola_plan", "sa_psola_ola",
     "sa_formant_dim", "sa_formant_tracks", "sa_formant_compare",
+    "sa_pole_warp_dim", "sa_pole_warp", "sa_formant_centre",
 ]
 
 _lib = None

@@ -377,3 +377,17 @@ class GenderPitchNormBrain(GenderBrain):
 
     def prepare_features(self, wavs, lens, stage):
         return super().prepare_features(self.hparams.pitch_normalizer(wavs, lens), lens, stage)
+
+
+class GenderFormantNormBrain(GenderBrain):
+    """gender_classifier_train_formant_norm.py: ``hparams.formant_normalizer`` (formantnorm.FormantNormalizer; DESIGN
+    section 26) brings every waveform's formants to the target at every stage, train, valid and test alike, before
+    augmentation and features; with ``hparams.pitch_normalizer`` (a PitchNormalizer with psola=True, or None) the
+    pitch of the result is normalised too.  Shapes and lengths are kept, so the rest of the recipe is GenderBrain's."""
+
+    def prepare_features(self, wavs, lens, stage):
+        wavs = self.hparams.formant_normalizer(wavs, lens)
+        pn = getattr(self.hparams, "pitch_normalizer", None)
+        if pn is not None:
+            wavs = pn(wavs, lens)
+        return super().prepare_features(wavs, lens, stage)

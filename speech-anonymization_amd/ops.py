@@ -1693,3 +1693,77 @@ def formant_compare(F_ref, F_deg, st_ref, st_deg, f0_ref, f0_deg, frames, min_co
                                         B, T, min_common, _f(med), _f(ratio), _f(shift), _f(common), L.stream()),
             "sa_formant_compare")
     return (*med.unbind(1), *ratio.unbind(1), shift, common)
+
+
+# ---- LPC formant normalisation (csrc/sa_formant_norm.hip; formantnorm.py) ----
+PW_Q_LOW, PW_Q_HIGH = 0.5, 2.0             # what sa_pole_warp clamps q to on the device
+PW_KNEE = 0.85                             # sa_pole_warp_dim(7) / 1000
+FORMANT_F_LOW, FORMANT_F_HIGH = 90.0, 5500.0               # the tracker's gate: where a target may lie
+
+_fn_in = functools.partial(_aug_in, family="formant normalisation")
+
+
+def pole_warp_workspace(B, N, device):
+    """the workspace sa_pole_warp takes: sa_mcadams's formula ([B][T][320] fp32 frames, then the level sums and gains
+    in fp64), as one 8-byte-aligned buffer"""
+    return mcadams_workspace(B, N, device)
+
+
+def pole_warp(wav, q, n_valid, level=True, return_status=False):
+    """wav fp32 [B, N] at 16 kHz, q fp32 [B], n_valid int32 [B] -> (out fp32 [B, N], gain fp32 [B]): every frame's
+    complex LPC poles moved from angle phi to q_b phi (piecewise linear above the knee 0.85 pi min(1, 1 / q_b), so that
+    (0, pi) maps onto itself) and the frame re-synthesised from its own residual, in sa_mcadams's framing; ``level``:
+    the RMS over the samples below n_valid_b brought back to the input's (sa_pole_warp).  return_status: also int32
+    [B, T], 0 a frame that was transformed, 1 a silent one, 2 one kept as it was."""
+    if _fn_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    T = mcadams_frames(N)
+    if B > GL_MAX_B or N > PN_MAX_N or T > GL_MAX_T:
+        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
+    _fn_in(q, "q", shape=(B,))
+    _fn_in(n_valid, "n_valid", torch.int32, (B,))
+    out = torch.empty_like(wav)
+    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
+    status = torch.empty(B, T, dtype=torch.int32, device=wav.device) if return_status else None
+    ws = pole_warp_workspace(B, N, wav.device)
+    L.check(L.load().sa_pole_warp(_f(wav), _f(q), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws), _f(status),
+                                  _f(gain), L.stream()), "sa_pole_warp")
+    return (out, gain, status) if return_status else (out, gain)
+
+
+def formant_centre(freq, status, f0, frames, target_hz, q_min=0.8, q_max=1.2, min_frames=8):
+    """freq fp32 [B, T, 3] and status int32 [B, T] (one output of formant_tracks), f0 fp32 [B, T] in Hz (0 or less:
+    unvoiced) or None (every frame voiced), frames int32 [B] (the frames of a row that count, clamped to [0, T]),
+    target_hz (t1, t2, t3) -> (med fp32 [B, 3], q fp32 [B], count int32 [B]): over the frames with status 0 and a
+    voiced F0, the lower median of each formant, the ratio clamp((t1 t2 t3 / (m1 m2 m3))^(1/3), q_min, q_max) that
+    brings them to the target, and the number of those frames.  A row with fewer than min_frames of them gets med 0,
+    q 1 and count 0.  Everything stays on the device (sa_formant_centre)."""
+    if _fn_in(freq, "freq").dim() != 3 or freq.shape[2] != FORMANTS or freq.numel() == 0:
+        raise L.SaHipError(f"freq: expected [B, T, {FORMANTS}] with B, T >= 1, got {tuple(freq.shape)}")
+    B, T, _ = freq.shape
+    if B > GL_MAX_B or T > FORMANT_MAX_T:
+        raise L.SaHipError(f"freq: [B, T] = [{B}, {T}] -- B up to {GL_MAX_B} (a grid extent), T up to {FORMANT_MAX_T}")
+    _fn_in(status, "status", torch.int32, (B, T))
+    if f0 is not None:
+        _fn_in(f0, "f0", shape=(B, T))
+    _fn_in(frames, "frames", torch.int32, (B,))
+    try:
+        t1, t2, t3 = (float(v) for v in target_hz)
+    except (TypeError, ValueError):
+        raise L.SaHipError(f"formant_centre: target_hz {target_hz!r}: three frequencies in Hz expected") from None
+    if not FORMANT_F_LOW <= t1 < t2 < t3 <= FORMANT_F_HIGH:
+        raise L.SaHipError(f"formant_centre: target_hz {target_hz!r}: {FORMANT_F_LOW:g} <= t1 < t2 < t3 <= "
+                           f"{FORMANT_F_HIGH:g} expected")
+    if not PW_Q_LOW <= float(q_min) <= 1.0 <= float(q_max) <= PW_Q_HIGH:
+        raise L.SaHipError(f"formant_centre: {PW_Q_LOW} <= q_min {q_min} <= 1 <= q_max {q_max} <= {PW_Q_HIGH} expected")
+    if isinstance(min_frames, bool) or not isinstance(min_frames, int) or min_frames < 1:
+        raise L.SaHipError(f"formant_centre: min_frames, a count of frames, 1 or more expected, got {min_frames!r}")
+    dev = freq.device
+    med = torch.empty(B, FORMANTS, dtype=torch.float32, device=dev)
+    q = torch.empty(B, dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.load().sa_formant_centre(_f(freq), _f(status), _f(f0), _f(frames), B, T, C.c_float(t1), C.c_float(t2),
+                                       C.c_float(t3), C.c_float(float(q_min)), C.c_float(float(q_max)), min_frames,
+                                       _f(med), _f(q), _f(count), L.stream()), "sa_formant_centre")
+    return med, q, count

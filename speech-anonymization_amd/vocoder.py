@@ -192,8 +192,10 @@ RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
 
 
 def anonymize_mode(settings):
-    """what anonymize.py runs: mcadams, pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough
-    or model"""
+    """what anonymize.py runs: formant_norm (--formant_norm true or --formant_norm_ratio X), mcadams,
+    pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough or model"""
+    if settings.get("formant_norm") or settings.get("formant_norm_ratio") is not None:
+        return "formant_norm"
     if any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")):
         return "mcadams"
     if settings.get("pitch_norm"):
@@ -206,12 +208,15 @@ def anonymize_mode(settings):
 def check_anonymize_options(settings, run_opts, environ=None):
     """what anonymize.py refuses before anything touches a GPU, one line each"""
     import os
-    from . import mcadams, pitchnorm                        # (both import this module)
+    from . import formantnorm, mcadams, pitchnorm           # (all import this module)
     environ = os.environ if environ is None else environ
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
     mode = anonymize_mode(settings)
-    given = {"--mcadams": mode == "mcadams", "--pitch_norm true": settings.get("pitch_norm"),
+    # the modes that move the pitch: --pitch_norm true, and the formant normalisation with a PSOLA stage behind it
+    pitch = mode == "pitch_norm" or (mode == "formant_norm" and bool(settings.get("pitch_norm")))
+    given = {"--mcadams": any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")),
+             "--pitch_norm true": settings.get("pitch_norm"),
              "--formant_ratio": "formant_ratio" in formant,
              "--preserve_formants true": formant.get("preserve_formants"),
              "--recon_ckpt": settings.get("recon_ckpt"), "--passthrough true": settings.get("passthrough")}
@@ -221,6 +226,21 @@ def check_anonymize_options(settings, run_opts, environ=None):
             if given[flag]:
                 raise SystemExit(text.format(flag))
 
+    if mode == "formant_norm":                              # (no model, no checkpoint, no STFT)
+        formantnorm.check_formant_norm_options(settings)
+        exclude("--formant_norm and {} exclude each other: the formant normalisation runs no model and no envelope "
+                "warp, and re-synthesises every frame from its own residual", "--mcadams", "--recon_ckpt",
+                "--passthrough true", "--formant_ratio", "--preserve_formants true")
+        if phase:
+            raise SystemExit("--formant_norm and --phase exclude each other: there is no STFT whose phases could be "
+                             "chosen")
+        if settings.get("pitch_norm") and not pitchnorm.check_psola_option(settings).get("psola"):
+            raise SystemExit("--formant_norm true with --pitch_norm true needs --psola true: the one pitch path that "
+                             "keeps the envelope the formants were moved to")
+    else:
+        for key in formantnorm.FLAGS[1:]:
+            if settings.get(key) is not None:
+                raise SystemExit(f"--{key} goes with --formant_norm true: nothing else normalises the formants")
     if mode == "mcadams":                                   # (no model, no checkpoint)
         mcadams.check_mcadams_options(settings)
         exclude("--mcadams and {} exclude each other: the McAdams transform runs no model, no pitch change and no "
@@ -232,13 +252,13 @@ def check_anonymize_options(settings, run_opts, environ=None):
         if mode not in RESYNTH_MODES:
             raise SystemExit("--phase vocoder goes with --pitch_norm true or --formant_ratio: the paths that "
                              "re-synthesise a waveform they were given")
-    if pitchnorm.check_contour_options(settings) and mode != "pitch_norm":    # 
+    if pitchnorm.check_contour_options(settings) and not pitch:               # 
         raise SystemExit("--contour_scale goes with --pitch_norm true --phase vocoder: the one mode that moves the "
                          "pitch")
-    if pitchnorm.check_psola_option(settings).get("psola") and mode != "pitch_norm":       # 
+    if pitchnorm.check_psola_option(settings).get("psola") and not pitch:                  # 
         raise SystemExit("--psola true goes with --pitch_norm true: it is the pitch normalisation done in the time "
                          "domain, grains between pitch marks laid down again at the new spacing")
-    if pitchnorm.check_f0_option(settings) and mode != "pitch_norm" and not settings.get("report_f0") \
+    if pitchnorm.check_f0_option(settings) and not pitch and mode != "formant_norm" and not settings.get("report_f0") \
             and settings.get("report_prosody") is not True and settings.get("report_formants") is not True:
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
     if mode in ("passthrough", "model") and settings.get("model_type") not in ANON_MODEL_TYPES:
@@ -256,7 +276,7 @@ def check_anonymize_options(settings, run_opts, environ=None):
                              "the other the vocoded originals")
         if settings.get("recon_ckpt"):
             raise SystemExit(f"{flag} takes no --recon_ckpt: no anonymiser runs, the waveforms are {written}")
-    if mode == "pitch_norm":
+    if pitch:
         pitchnorm.check_pitch_target(settings.get("pitch_target_hz", 170.0))
     if mode == "model" and not settings.get("recon_ckpt"):
         raise SystemExit("--recon_ckpt DIR is required without --passthrough true: a CKPT+* directory of "

@@ -17,6 +17,9 @@ moved, all three together (formant_shift) and one by one (f1_shift, f2_shift, f3
   pitch_norm_psola, pitch_norm_psola_contour
                           pitch normalisation in the time domain (--psola true, TD-PSOLA), with one
                           ratio per utterance and with --contour_scale 1, a ratio per frame
+  formant_norm, formant_norm_psola
+                          formant normalisation to (550, 1650, 2750) Hz (--formant_norm true), alone
+                          and with --pitch_norm true --psola true behind it: both cues at their targets
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech; the formant columns in
@@ -42,7 +45,9 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("pitch_norm_preserve_pv", ["--pitch_norm", "true", "--preserve_formants", "true", "--phase", "vocoder"]),
          ("formant_ratio_1.15_pv", ["--formant_ratio", "1.15", "--phase", "vocoder"]),
          ("pitch_norm_psola", ["--pitch_norm", "true", "--psola", "true"]),
-         ("pitch_norm_psola_contour", ["--pitch_norm", "true", "--psola", "true", "--contour_scale", "1"]))
+         ("pitch_norm_psola_contour", ["--pitch_norm", "true", "--psola", "true", "--contour_scale", "1"]),
+         ("formant_norm", ["--formant_norm", "true"]),
+         ("formant_norm_psola", ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"]))
 
 
 def _mean(vals):
