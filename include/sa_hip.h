@@ -248,6 +248,23 @@ int sa_fin_bias(const double* sums, int B, int C, int ncomp, float* db, void* st
 typedef struct SaFlat { float* p; long long n; } SaFlat;
 typedef struct SaFlats { int n, pad_; SaFlat f[SA_FLATS_MAX]; } SaFlats;
 int sa_clip_grads(const SaFlats* f, float max_norm, float eps, double* partials, float* total_norm, void* stream);
+/* The arithmetic of torch.optim.Adam(fused=True).step() (fp32, no weight decay / amsgrad / maximize / grad
+ * scaler; torch 2.10's fused kernel, same bits) for ntensors tensors in ONE launch (sa_optim.hip).  table
+ * (DEVICE memory, ntensors records) names each tensor's parameter, moments, step counter (fp32 scalar, already
+ * advanced by the caller) and gradient: bases->f[gbase].p + goff when gbase >= 0 -- a view of a flat gradient
+ * bucket, so that buckets reallocated by every backward change an argument, not the table -- else g.  map
+ * (DEVICE memory, [nblocks][2] int): block -> (tensor, chunk of SA_ADAM_CHUNK elements).  lr_dev (optional,
+ * device fp32 scalar: the capturable optimizer's rate) is read on the device and lr is ignored.
+ * sa_adam_record_bytes: sizeof(SaAdamRec), for the binding's layout check. */
+#define SA_ADAM_CHUNK 1024
+typedef struct SaAdamRec {
+  float* p; float* m; float* v; const float* step; const float* g;
+  long long goff, n;
+  int gbase, pad_;
+} SaAdamRec;
+int sa_adam_record_bytes(void);
+int sa_adam_step(const SaAdamRec* table, int ntensors, const int* map, int nblocks, const SaFlats* bases,
+                 const float* lr_dev, double lr, double beta1, double beta2, double eps, void* stream);
 #define SA_BIAS_MAX 8
 typedef struct SaBiasDesc {
   const float* part; double* rows; float* db;

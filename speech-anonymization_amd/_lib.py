@@ -88,6 +88,14 @@ class SaFlats(C.Structure):
 
 
 
+class SaAdamRec(C.Structure):
+    _fields_ = [("p", vp), ("m", vp), ("v", vp), ("step", vp), ("g", vp),
+                ("goff", C.c_longlong), ("n", C.c_longlong), ("gbase", C.c_int), ("pad_", C.c_int)]
+
+
+ADAM_CHUNK = 1024
+
+
 class SaWredDesc(C.Structure):
     _fields_ = [("slabs", vp), ("dst", vp)] + [(k, C.c_int) for k in ("nslab", "ntaps", "cin", "cout", "sk", "sn", "st",
                                                                       "accumulate", "vec", "pad_")]
@@ -112,6 +120,7 @@ SYMBOLS = [
     "sa_comm_unique_id", "sa_comm_init", "sa_comm_world", "sa_comm_allreduce", "sa_comm_allreduce_inline", "sa_comm_join", "sa_comm_ncalls",
     "sa_comm_destroy", "sa_head_fwd", "sa_head_bwd", "sa_head_bwd_wide", "sa_head_max_rows",
     "sa_add_layernorm_fwd", "sa_layernorm_bwd", "sa_reflect_pad_fwd", "sa_reflect_pad_bwd", "sa_ln_leaky_fwd", "sa_ln_leaky_bwd", "sa_bias_multi", "sa_asr_block0_fwd", "sa_asr_block0_bwd", "sa_wgrad_reduce_multi", "sa_clip_grads",
+    "sa_adam_record_bytes", "sa_adam_step",
     "sa_xv_tdnn_fwd_train", "sa_xv_tdnn_ntiles", "sa_xv_colsums", "sa_xv_tdnn_wgrad", "sa_xv_wgrad_reduce",
     "sa_xv_tdnn_dgrad", "sa_xv_pool_affine", "sa_xv_pool_affine_bwd",
     "sa_fc_tiles", "sa_fc_groups", "sa_fc_nparam", "sa_fc_nhead", "sa_fc_max_rows", "sa_fc_enc_fwd", "sa_fc_bn_fin",
@@ -158,6 +167,9 @@ def load():
             if _lib.sa_abi_sizeof(i) != C.sizeof(rec):
                 raise SaHipError(f"{rec.__name__}: binding has {C.sizeof(rec)} bytes, {LIB_PATH} "
                                  f"{_lib.sa_abi_sizeof(i)} -- rebuild the library (stale build?)")
+        if _lib.sa_adam_record_bytes() != C.sizeof(SaAdamRec):
+            raise SaHipError(f"SaAdamRec: binding has {C.sizeof(SaAdamRec)} bytes, {LIB_PATH} "
+                             f"{_lib.sa_adam_record_bytes()} -- rebuild the library (stale build?)")
     return _lib
 
 

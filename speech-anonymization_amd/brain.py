@@ -138,6 +138,11 @@ class Brain:
         # backward started from the model outputs instead of through a graph of 0-dim tensors (same bits;
         # SexAnonymizationTraining._native_tail says when)
         self.step_tail = bool(run_opts.get("step_tail", os.environ.get("SA_STEP_TAIL", "1") == "1"))
+        # native_adam (default on; SA_NATIVE_ADAM=0): the arithmetic of a plain fused Adam's step() in one launch
+        # (ops.adam_step: torch's fused update, same bits).  torch keeps the optimizer -- param_groups, state,
+        # state_dict, Noam's lr -- and its own step() runs whatever the launch does not cover: the first step of a
+        # process (no state yet), weight decay / amsgrad / a grad scaler, non-fp32 tensors (optimizer_step)
+        self.native_adam = bool(run_opts.get("native_adam", os.environ.get("SA_NATIVE_ADAM", "1") == "1"))
         self.distributed_launch = bool(run_opts.get("distributed_launch", sdist.is_distributed()))
         self.modules = torch.nn.ModuleDict(modules or {})
         # dp_batch_sizes (default "equal"): how the data-parallel ranks' batches relate.  The data
@@ -200,6 +205,15 @@ class Brain:
                 except (TypeError, RuntimeError):
                     self.hip_graph = False
             self.optimizer = self.opt_class(params)
+
+    def optimizer_step(self):
+        """optimizer.step(); with native_adam, as one launch on the optimizer's own tensors where that covers it"""
+        if self.native_adam and self.device.type == "cuda":
+            from . import ops
+            model = self.modules["ConvAE"] if "ConvAE" in self.modules else None
+            if ops.adam_step(self.optimizer, getattr(model, "_last_flats", None)):
+                return
+        self.optimizer.step()
 
     def check_gradients(self, loss):
         """speechbrain semantics: count non-finite losses (raise after `nonfinite_patience`),
@@ -297,7 +311,7 @@ class Brain:
         loss = self.compute_objectives(outputs, batch, Stage.TRAIN)
         loss.backward()
         if self.check_gradients(loss):
-            self.optimizer.step()
+            self.optimizer_step()
         self.optimizer.zero_grad()
         return loss.detach()
 
@@ -610,7 +624,7 @@ class SexAnonymizationTraining(Brain):
                 # SpecAugment of the input: three more launches in the captured step
                 self.__dict__.get("_specaug") is not None,
                 # step_tail: whether the captured step ends in the one-launch loss tail
-                self._native_tail())
+                self._native_tail(), self.native_adam)
 
     def _step_core(self, batch):
         predictions = self.compute_forward(batch, Stage.TRAIN)
@@ -619,7 +633,7 @@ class SexAnonymizationTraining(Brain):
         if getattr(self.hparams, "epoch_parity_schedule", False):
             self._zero_grads_of_frozen()
         self.check_gradients(loss)
-        self.optimizer.step()
+        self.optimizer_step()
         return loss.detach()
 
     def _fit_batch_graph(self, batch):
@@ -657,10 +671,22 @@ class SexAnonymizationTraining(Brain):
                 ent["specaug"] = self._specaug_shapes[tuple(wavs.shape)]
                 aug.draw(*ent["specaug"], device=self.device)
                 self._specaug_drawn = True
+            # torch no longer collects garbage before a capture (torch.cuda.graph.__enter__: in 2.10 only with
+            # torch.compiler.config.force_cudagraph_gc).  A dead reference cycle that holds GPU objects -- an
+            # earlier Brain with its graphs, their pools, pinned buffers and events -- must be destroyed before
+            # the capture, not by a collection that happens to run inside it: their destructors call the
+            # runtime, which a capture in global mode answers with an error that aborts the process.  So:
+            # collect now, and no automatic collection until the capture has ended
+            import gc
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
             try:
                 with torch.cuda.graph(g):
                     ent["loss"] = self._step_core(ent["batch"])
             finally:
+                if gc_was_on:
+                    gc.enable()
                 self._specaug_drawn = False
             ent["graph"] = g
             # the capture itself does not execute the step: replay it for this batch below
@@ -709,7 +735,7 @@ class SexAnonymizationTraining(Brain):
             if getattr(self.hparams, "epoch_parity_schedule", False):
                 self._zero_grads_of_frozen()
             self.check_gradients(loss)          # return value ignored, like the reference (:249-251)
-            self.optimizer.step()
+            self.optimizer_step()
             self.optimizer.zero_grad()
             self.hparams.noam_annealing(self.optimizer)
         return loss.detach()

@@ -878,6 +878,133 @@ def clip_flats(flats, max_norm, eps=1e-6):
     return total
 
 
+# ---- the arithmetic of torch.optim.Adam(fused=True).step() in one launch (csrc/sa_optim.hip) ----
+def _adam_plain(opt):
+    """the configuration half of adam_step's conditions: torch.optim.Adam itself, fused, nothing but the plain
+    update (no weight decay, amsgrad, maximize, grad scaler, step hooks), scalar betas, lr a host number or the
+    capturable optimizer's float32 device scalar"""
+    from torch.optim import optimizer as _o
+    if type(opt) is not torch.optim.Adam:
+        return False
+    if getattr(opt, "grad_scale", None) is not None or getattr(opt, "found_inf", None) is not None:
+        return False
+    if (opt._optimizer_step_pre_hooks or opt._optimizer_step_post_hooks or _o._global_optimizer_pre_hooks
+            or _o._global_optimizer_post_hooks):
+        return False
+    for g in opt.param_groups:
+        if (not g.get("fused") or g["weight_decay"] != 0 or g["amsgrad"] or g["maximize"] or g.get("differentiable")
+                or g.get("decoupled_weight_decay")):
+            return False
+        if any(torch.is_tensor(b) for b in g["betas"]) or torch.is_tensor(g["eps"]):
+            return False
+        lr = g["lr"]
+        if torch.is_tensor(lr) and not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1):
+            return False
+    return True
+
+
+def _adam_group(opt, group, spans):
+    """(key, steps, device) of one param group, or None when a tensor is outside what the kernel covers: every
+    parameter with a gradient has state (torch creates it in its first step), everything fp32, contiguous, on one
+    GPU.  key: per tensor (param, exp_avg, exp_avg_sq, step pointers, numel, bucket index, element offset in the
+    bucket | -1, gradient pointer) -- equal keys mean the cached device table still describes the group"""
+    st, key, steps, dev = opt.state, [], [], None
+    f32 = torch.float32
+    for p in group["params"]:
+        g = p.grad
+        if g is None:
+            continue
+        s = st.get(p)
+        if not s:
+            return None
+        step, m, v = s["step"], s["exp_avg"], s["exp_avg_sq"]
+        n = p.numel()
+        if dev is None:
+            dev = p.device
+            if dev.type != "cuda":
+                return None
+        for t in (p, g, m, v):
+            if (t.dtype is not f32 or t.device != dev or t.layout is not torch.strided or t.numel() != n
+                    or not t.is_contiguous()):
+                return None
+        if step.dtype is not f32 or step.device != dev or step.numel() != 1 or n == 0:
+            return None
+        a = g.data_ptr()
+        rec = (p.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(), n, -1, a)
+        for i, (lo, hi) in enumerate(spans):
+            if lo <= a and a + 4 * n <= hi:
+                rec = rec[:5] + (i, (a - lo) // 4)
+                break
+        key.append(rec)
+        steps.append(step)
+    return tuple(key), steps, dev
+
+
+def _adam_table(key, dev):
+    """device table (SaAdamRec per tensor) and block -> (tensor, chunk) map of one param group"""
+    arr = (L.SaAdamRec * len(key))()
+    blocks = []
+    for t, (r, (p, m, v, step, n, gbase, goff)) in enumerate(zip(arr, key)):
+        r.p, r.m, r.v, r.step, r.n, r.gbase = p, m, v, step, n, gbase
+        r.g, r.goff = (goff, 0) if gbase < 0 else (None, goff)
+        blocks.extend((t, c) for c in range(-(-n // L.ADAM_CHUNK)))
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    bmap = torch.tensor(blocks, dtype=torch.int32).to(dev)
+    return table, bmap, len(key), len(blocks)
+
+
+def adam_step(opt, flats=None):
+    """optimizer.step() of a plain torch.optim.Adam(fused=True) with its arithmetic in one launch per param group
+    (sa_adam_step: torch 2.10's fused fp32 update, same bits); torch keeps owning param_groups, state and lr, and
+    advances the step counters (_foreach_add_) as its own step() does.  Returns False, having done nothing, for
+    every case the kernel does not cover -- the caller then runs opt.step().
+
+    flats: flat gradient buckets (a model's _last_flats).  A gradient that is a view of one is recorded as
+    (bucket, offset), so buckets that every backward allocates anew change a launch argument and the cached table
+    stays.  A table that has to be rebuilt while a hipGraph is being captured is a case for torch's step()."""
+    if not _adam_plain(opt):
+        return False
+    flats = list(flats or ())[:L.FLATS_MAX]
+    spans = [(f.data_ptr(), f.data_ptr() + 4 * f.numel()) for f in flats]
+    cache = opt.__dict__.setdefault("_sa_adam_tables", {})
+    # a captured launch reads its table on every replay: those tables stay alive (and findable) for the optimizer's
+    # lifetime, whatever later steps put into the one-entry cache
+    captured = opt.__dict__.setdefault("_sa_adam_captured", [])
+    capturing = torch.cuda.is_current_stream_capturing()
+    plans = []
+    for gi, group in enumerate(opt.param_groups):
+        plan = _adam_group(opt, group, spans)
+        if plan is None:
+            return False
+        key, steps, dev = plan
+        if not key:
+            continue
+        ent = cache.get(gi)
+        if ent is None or ent[0] != key:
+            ent = next((e for e in captured if e[0] == key), None)
+            if ent is None:
+                if capturing:
+                    return False
+                ent = (key,) + _adam_table(key, dev)
+            cache[gi] = ent
+        plans.append((group, steps, ent))
+    if capturing:
+        captured.extend(ent for _, _, ent in plans if not any(ent is e for e in captured))
+    bases = L.SaFlats()
+    bases.n = len(flats)
+    for d, (lo, hi) in zip(bases.f, spans):
+        d.p, d.n = lo, (hi - lo) // 4
+    lib = L.load()
+    for group, steps, (_, table, bmap, nt, nblocks) in plans:
+        torch._foreach_add_(steps, 1)
+        lr = group["lr"]
+        lr_dev, lr_host = (_f(lr), 0.0) if torch.is_tensor(lr) else (None, float(lr))
+        b1, b2 = group["betas"]
+        L.check(lib.sa_adam_step(_f(table), nt, _f(bmap), nblocks, C.byref(bases), lr_dev, C.c_double(lr_host),
+                                 C.c_double(b1), C.c_double(b2), C.c_double(group["eps"]), L.stream()), "sa_adam_step")
+    return True
+
+
 # ---- waveform augmentation (csrc/sa_augment.hip; augment.py) ----
 def _aug_in(t, what, dtype=torch.float32, shape=None, family="augmentation"):
     if not torch.is_tensor(t) or not t.is_cuda:
