@@ -6,6 +6,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
         --recon_ckpt DIR --out_dir OUT [--csv FILE | --synthetic N] [--passthrough true] [--n_iter 32] [--seed S]
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
         [--psola true] [--formant_norm true [--formant_target F1,F2,F3]] [--formant_norm_ratio X]
+        [--resynth true [--resynth_pitch_hz X] [--aspiration A]]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
         [--report_formants true]
 
@@ -46,6 +47,16 @@ the pitch path that keeps the envelope, and PSOLA then runs on the normalised wa
 ``"formant_norm": true`` and per utterance ``q``, ``gain``, ``formant_frames_in`` (0 when the utterance had fewer than
 8 scored frames and was left as it is), ``f1_in_hz``, ``f2_in_hz``, ``f3_in_hz`` (the input's median formants, null
 when not scored), ``silent_frames``, ``fallback_frames`` and ``peak``.
+
+``--resynth true [--resynth_pitch_hz X] [--aspiration A] [--f0_method M] [--seed S]`` runs no model and reads no
+checkpoint either: OUT receives the source-filter resynthesis of every waveform (speech_anonymization_amd.sourcefilter;
+DESIGN section 27) -- each frame keeps its order-20 LPC envelope and its energy, its residual is discarded, and the
+filter is driven by pulses at the F0 track where the frame is voiced and by noise elsewhere.  Without
+``--resynth_pitch_hz`` every utterance keeps its own pitch; with it the pulses are laid down so that the mean voiced F0
+becomes X, in the same pass.  ``--aspiration A`` in [0, 1] (default 0.3, a convention) is the noise under a voiced
+frame's pulses; ``--seed`` seeds the noise.  It takes no other mode's flag.  Its JSON line carries ``"resynth": true``
+and per utterance ``pulses``, ``ratio``, ``gain``, ``silent_frames``, ``fallback_frames``, ``unexcited_frames`` and
+``peak``.
 
 ``--phase vocoder`` (with --pitch_norm true and/or --formant_ratio X) carries the input's own phases through the
 stretch instead of reconstructing them with Griffin-Lim (speech_anonymization_amd.ops.pv_synth):
@@ -115,7 +126,8 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import data, features, formantnorm, gender, mcadams, pitchnorm, reports, vocoder
+from speech_anonymization_amd import (data, features, formantnorm, gender, mcadams, pitchnorm, reports, sourcefilter,
+                                      vocoder)
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -222,6 +234,23 @@ def _formant_norm(settings, device, bs, seed):
     return step, head, dict(shown, **tail)
 
 
+def _resynth(settings, device, bs, seed):
+    """--resynth true: every utterance's LPC envelope under a pulse/noise excitation, written; no model"""
+    opts = dict(sourcefilter.check_resynth_options(settings), seed=seed)
+    sf = sourcefilter.SourceFilter(**opts)
+
+    def step(ids, wavs, lens):
+        out = sf(wavs, lens)
+        _, rho_q, pulses, gain, counts = sf.last
+        ratio = (rho_q[:, 0].double() / float(1 << 16)).cpu().tolist()
+        pulses, gain, counts = (v.cpu().tolist() for v in (pulses, gain, counts))
+        return out, _counts(lens, out.shape[1]), [
+            {"pulses": pulses[i], "ratio": ratio[i], "gain": gain[i], "silent_frames": counts[i][1],
+             "fallback_frames": counts[i][2], "unexcited_frames": counts[i][3]} for i in range(len(ids))], None
+
+    return step, {"resynth": True}, {k: v for k, v in opts.items() if k != "f0_method"}
+
+
 def _model(settings, device, bs, seed):
     """an anonymiser's reconstruction (or with --passthrough true the original features) inverted by Griffin-Lim"""
     mt, passthrough = settings["model_type"], bool(settings.get("passthrough"))
@@ -263,7 +292,7 @@ def _model(settings, device, bs, seed):
                   "n_iter": gl.n_iter, "seed": seed}, {}
 
 
-MODES = {"formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
+MODES = {"resynth": _resynth, "formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
          "model": _model}
 
 

@@ -985,6 +985,76 @@ int sa_formant_centre(const float* freq, const int* status, const float* f0, con
                       float t2, float t3, float q_min, float q_max, int min_frames, float* med, float* q, int* count,
                       void* stream);
 
+/* ---- LPC source-filter resynthesis (sa_srcfilt.hip; sourcefilter.py, ops.srcfilt_pulses, ops.srcfilt_excite,
+ * ops.srcfilt_synth, ops.srcfilt): the classic LPC vocoder.  Every frame keeps its all-pole envelope
+ * and its energy; its residual is discarded and the filter is driven by a synthetic excitation, pulses at the F0 track
+ * where the frame is voiced and noise elsewhere.  The pulses are laid down at the period asked for, so the same pass
+ * sets the pitch.  No STFT, no phase, no pitch marks, no iteration, no root finder, no copy to the host.  Every decision
+ * of the first two entry points is made on integers, or on fp64 formed from the fp32 inputs; only the filtered output
+ * rounds.  Sample rate 16000; W = 320, H = 160, P = 20 and the periodic sqrt-Hann window w are sa_mcadams's.
+ *   Per row b: n_valid int32, clamped to [0, N]; a sample outside [0, n_valid_b) reads as 0 and is written as 0.
+ *   f0 [T] fp32 in Hz from either tracker, T = N / 160 + 1 or T = ceil(N / 160) + 1 (what sa_psola_marks accepts),
+ *   nothing else.  frame(n) = min((n + 80) / 160, T - 1).  Frame t is voiced when f0[t] > 0 and f0[t] < +inf: a NaN,
+ *   a negative value and an infinity are unvoiced.  Positions are int64 in units of 2^-16 samples.
+ *   sa_srcfilt_pulses: f0 [B][T] fp32; rho_q [B][T] int32, the pitch ratio per frame in units of 2^-16, or NULL;
+ *   n_valid [B] int32 -> pos_q [B][Kcap] int64, period_q [B][Kcap] int32, count [B] int32, Kcap = N / 40 + 2.
+ *     rho = clamp(rho_q[t], 2^15, 2^17), 2^16 when rho_q is NULL.
+ *     P_q[t] = (int)clamp(rint(16000 2^32 / ((double)f0[t] (double)rho)), 40 2^16, 266 2^16): the denominator is exact
+ *       in fp64 (24 by 18 bits), the quotient is rounded once, rint rounds half to even, and the clamp is applied in
+ *       fp64 before the conversion.  A ratio above 1 raises the pitch, so rho divides the period.
+ *     The walk starts at s = 0 and runs while floor(s / 2^16) < n_valid_b, with t = frame(floor(s / 2^16)):
+ *       voiced: emit (pos_q, period_q) = (s, P_q[t]), then s += P_q[t];
+ *       unvoiced and t = T - 1: stop;   unvoiced otherwise: s = (160 t + 80) 2^16, the first sample of frame t + 1.
+ *     Pulses are 40 samples or more apart and a row has at most N / 40 + 1 of them.  Every step moves s forward, so
+ *     the walk ends; the kernel also stops after Kcap + T steps.  Entries past a row's count mean nothing.
+ *   sa_srcfilt_excite: f0, the table of sa_srcfilt_pulses, seed [B] int32, n_valid [B], aspiration -> exc [B][N] fp32.
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16, in uint32.
+ *     k_b = mix((uint32)seed_b);  h = mix((uint32)n ^ k_b);  u_n = ((int)(h >> 8) - 2^23) 2^-23: exact in fp32, in
+ *     [-1, 1).  For n < n_valid_b, every fp32 operation rounded on its own and none contracted:
+ *       e = c u_n, c = aspiration when frame(n) is voiced and 1 otherwise;
+ *       the pulse k with floor(s_k / 2^16) = n adds A_k (1 - phi_k);
+ *       the pulse k with floor(s_k / 2^16) + 1 = n and phi_k > 0 adds A_k phi_k;
+ *       phi_k = (s_k mod 2^16) 2^-16;  A_k = fp32(sqrt((double)P_k 2^-16)), which gives the pulse train unit mean power.
+ *     exc[n] = e, and 0 for n >= n_valid_b.  A sample receives at most one pulse term (the spacing is 40 or more), so
+ *     there is no order to fix.  Uniform noise has power 1 / 3: a voiced frame's noise lies at aspiration^2 / 3 of the
+ *     pulses' power.  period_q is clamped to [40 2^16, 266 2^16] and count to [0, Kcap] where they are read; pos_q is
+ *     only compared.  (Left open by the feature's statement and settled here: the entry point takes f0 and T, since
+ *     the noise level of a sample depends on its frame's voicing; the last pulse's second term falls away when its
+ *     sample is n_valid_b.)
+ *   sa_srcfilt_synth: wav [B][N] fp32 (the envelope and the level), exc [B][N] fp32, n_valid [B] -> out [B][N] fp32,
+ *   out != wav, out != exc.  sa_mcadams's framing: T' = (N + 159) / 160 + 1 frames, frame t over
+ *   [160 t - 160, 160 t + 160).  Per frame, in fp64, f = w x and ex = w e:
+ *     (a) r_k = sum_j f[j] f[j + k], k = 0..20;  r_0 < 1e-10: silent (status 1), rec = f;
+ *     (b) r_0 *= 1 + 1e-9;  a[0..20] by Levinson-Durbin with the final prediction error E = r_0 prod (1 - k_i^2), formed
+ *         step by step;  some |k_i| >= 1 or an error <= 0: fallback (status 2), rec = f;
+ *     (c) Ee = sum_j ex[j]^2;  Ee < 1e-20: no excitation (status 3), rec = 0;  otherwise g = sqrt(E / Ee);
+ *     (d) rec = IIR(1 / a)(g ex) from zero history: rec[j] = g ex[j] - sum_{k=1..20} a[k] rec[j - k];
+ *     (e) the frame stored is fp32(rec w).
+ *   y[n] = F_t0[n - 160 t0 + 160] + F_{t0 + 1}[n - 160 t0], t0 = n / 160 (fp32);  out[n] = fp32(g_b y[n]) for
+ *   n < n_valid_b and 0 from there on;  level != 0: g_b = sqrt(sum x^2 / sum y^2) over n < n_valid_b (fp64, a fixed
+ *   order; 1 when either sum is 0), else 1.  No setting is an identity, so no row is ever copied.
+ *   ws: the caller's, sa_srcfilt_workspace_bytes(B, N) = 4 B T' 320 + 8 (2 B ceil(N / C) + B) bytes (sa_mcadams's
+ *     layout), 8-byte aligned, C = sa_srcfilt_dim(4); its contents mean nothing between calls.  status: NULL, or int32
+ *     [B][T'].  gain: NULL, or fp32 [B].
+ *   One wave per row (pulses), one workgroup per 256 samples (excite), one wave per frame (synth); no atomics, every
+ *   sum in a fixed order, a row's result does not depend on its neighbours: the same bits on every run and in every
+ *   batch.
+ *   sa_srcfilt_dim(which): 0 W 320, 1 H 160, 2 P 20, 3 threads per frame, 4 samples per block of the level sums, 5 and
+ *     6 the period bounds 40 and 266, 7 the divisor 40 of Kcap, 8 samples per workgroup of sa_srcfilt_excite, 9 pulses
+ *     staged per workgroup there; else -EINVAL.
+ *   sa_srcfilt_workspace_bytes(B, N): the size above, or -EINVAL for a B or N the kernels refuse.
+ *   -EINVAL, before any launch: a NULL required pointer (rho_q, status and gain may be NULL), B < 1 or > 65535,
+ *     N < 1 or > 2^24, a T that is neither of the two above (pulses, excite), an aspiration outside [0, 1] (a NaN
+ *     too). */
+int sa_srcfilt_dim(int which);
+long long sa_srcfilt_workspace_bytes(int B, int N);
+int sa_srcfilt_pulses(const float* f0, const int* rho_q, const int* n_valid, int B, int N, int T, long long* pos_q,
+                      int* period_q, int* count, void* stream);
+int sa_srcfilt_excite(const float* f0, const long long* pos_q, const int* period_q, const int* count, const int* seed,
+                      const int* n_valid, int B, int N, int T, float aspiration, float* exc, void* stream);
+int sa_srcfilt_synth(const float* wav, const float* exc, const int* n_valid, int B, int N, int level, float* out,
+                     void* ws, int* status, float* gain, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

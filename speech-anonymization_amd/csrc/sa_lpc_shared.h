@@ -1,7 +1,7 @@
 // The LPC steps of the frame kernels, templated on the order P: the Levinson-Durbin recursion and the Aberth-Ehrlich
 // root finder, as sa_mcadams.hip (P = 20) and sa_formants.hip (P = 18) each spell them out (DESIGN sections 17, 25).
-// Included by sa_formant_norm.hip only: the two older files keep their own copies, so that their objects stay what
-// they were.  One wave of 64 lanes; every lane holds the same r and a.
+// Included by sa_formant_norm.hip and sa_srcfilt.hip: the two older files keep their own copies, so that their objects
+// stay what they were.  One wave of 64 lanes; every lane holds the same r and a.
 #pragma once
 #include "sa_common.h"
 
@@ -35,6 +35,37 @@ __device__ static __forceinline__ void sa_lpc_levinson(const double (&r)[P + 1],
     err *= 1.0 - k * k;
     bad = bad || !(err > 0.0);
   }
+  if (bad) st = 2;
+}
+
+// The same recursion, word for word, which also hands out the final prediction error (err = r_0 prod (1 - k_i^2), formed
+// step by step as above): sa_srcfilt.hip scales its excitation to it.  A second text and not a parameter of the first,
+// so that sa_formant_norm.hip's object stays what it was.
+template <int P>
+__device__ static __forceinline__ void sa_lpc_levinson_err(const double (&r)[P + 1], double (&a)[P + 1], int& st,
+                                                           double& err_out) {
+  double err = r[0];
+  bool bad = false;
+  a[0] = 1.0;
+#pragma unroll
+  for (int i = 1; i <= P; ++i) a[i] = 0.0;
+#pragma unroll
+  for (int m = 1; m <= P; ++m) {
+    double acc = r[m];
+#pragma unroll
+    for (int i = 1; i < m; ++i) acc = fma(a[i], r[m - i], acc);
+    const double k = -acc / err;
+    bad = bad || !(fabs(k) < 1.0);
+    double prev[P + 1];
+#pragma unroll
+    for (int i = 1; i < m; ++i) prev[i] = a[i];
+#pragma unroll
+    for (int i = 1; i < m; ++i) a[i] = fma(k, prev[m - i], prev[i]);
+    a[m] = k;
+    err *= 1.0 - k * k;
+    bad = bad || !(err > 0.0);
+  }
+  err_out = err;
   if (bad) st = 2;
 }
 

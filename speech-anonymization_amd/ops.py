@@ -1894,3 +1894,120 @@ def formant_centre(freq, status, f0, frames, target_hz, q_min=0.8, q_max=1.2, mi
                                        C.c_float(t3), C.c_float(float(q_min)), C.c_float(float(q_max)), min_frames,
                                        _f(med), _f(q), _f(count), L.stream()), "sa_formant_centre")
     return med, q, count
+
+
+# ---- LPC source-filter resynthesis (csrc/sa_srcfilt.hip; sourcefilter.py) ----
+SRCFILT_MAX_N = 1 << 24
+SRCFILT_KDIV = 40                          # sa_srcfilt_dim(7): Kcap = N // 40 + 2
+SRCFILT_RHO_ONE = 1 << 16
+
+_sf_in = functools.partial(_aug_in, family="source-filter")
+
+
+def _sf_dims(who, B, N, T=None):
+    if B > GL_MAX_B or not 1 <= N <= SRCFILT_MAX_N:
+        raise L.SaHipError(f"{who}: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N in 1..{SRCFILT_MAX_N}")
+    if T is not None and T not in (N // YIN_HOP + 1, -(-N // YIN_HOP) + 1):
+        raise L.SaHipError(f"{who}: f0 has {T} frames; N // 160 + 1 = {N // YIN_HOP + 1} of the waveform (or "
+                           f"{-(-N // YIN_HOP) + 1} of the padded one) expected")
+
+
+def _sf_track(who, f0, rho_q, n_valid, N):
+    if _sf_in(f0, "f0").dim() != 2 or f0.numel() == 0:
+        raise L.SaHipError(f"f0: expected [B, T] with B, T >= 1, got {tuple(f0.shape)}")
+    B, T = f0.shape
+    N = int(N)
+    _sf_dims(who, B, N, T)
+    if rho_q is not None:
+        _sf_in(rho_q, "rho_q", torch.int32, (B, T))
+    _sf_in(n_valid, "n_valid", torch.int32, (B,))
+    return B, N, T
+
+
+def _sf_aspiration(who, aspiration):
+    if isinstance(aspiration, bool) or not 0.0 <= float(aspiration) <= 1.0:
+        raise L.SaHipError(f"{who}: aspiration {aspiration} in 0..1 expected (the noise under the pulses of a voiced "
+                           "frame, relative to the noise of an unvoiced one)")
+    return float(aspiration)
+
+
+def srcfilt_workspace(B, N, device):
+    """the workspace sa_srcfilt_synth takes (sa_srcfilt_workspace_bytes: sa_mcadams's layout), as one 8-byte-aligned
+    buffer"""
+    nbytes = L.load().sa_srcfilt_workspace_bytes(int(B), int(N))
+    if nbytes < 0:
+        raise L.SaHipError(f"srcfilt_workspace: [B, N] = [{B}, {N}] refused")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def srcfilt_pulses(f0, rho_q, n_valid, *, N):
+    """f0 fp32 [B, T] in Hz (voiced where 0 < f0 < inf), rho_q int32 [B, T] (the pitch ratio per frame in units of
+    2^-16, clamped to [2^15, 2^17]) or None (1 throughout), n_valid int32 [B], N (by keyword: the samples per row) ->
+    (pos_q int64 [B, N // 40 + 2] in units of 2^-16 samples, period_q int32 of that shape, count int32 [B]): a pulse
+    every 16000 / (f0 rho) samples through the voiced frames; entries from count on mean nothing
+    (sa_srcfilt_pulses)"""
+    B, N, T = _sf_track("srcfilt_pulses", f0, rho_q, n_valid, N)
+    K = N // SRCFILT_KDIV + 2
+    pos_q = torch.empty(B, K, dtype=torch.int64, device=f0.device)
+    period_q = torch.empty(B, K, dtype=torch.int32, device=f0.device)
+    count = torch.empty(B, dtype=torch.int32, device=f0.device)
+    L.check(L.load().sa_srcfilt_pulses(_f(f0), _f(rho_q), _f(n_valid), B, N, T, _f(pos_q), _f(period_q), _f(count),
+                                       L.stream()), "sa_srcfilt_pulses")
+    return pos_q, period_q, count
+
+
+def srcfilt_excite(f0, pos_q, period_q, count, seed, n_valid, aspiration=0.3, *, N):
+    """f0 fp32 [B, T], the table of srcfilt_pulses, seed int32 [B], n_valid int32 [B] -> exc fp32 [B, N]: uniform noise
+    in [-1, 1) hashed from (seed_b, n), scaled by ``aspiration`` where the frame is voiced, plus the linearly
+    interpolated pulses of amplitude sqrt(period); zero from n_valid on (sa_srcfilt_excite)"""
+    B, N, T = _sf_track("srcfilt_excite", f0, None, n_valid, N)
+    K = N // SRCFILT_KDIV + 2
+    _sf_in(pos_q, "pos_q", torch.int64, (B, K))
+    _sf_in(period_q, "period_q", torch.int32, (B, K))
+    _sf_in(count, "count", torch.int32, (B,))
+    _sf_in(seed, "seed", torch.int32, (B,))
+    aspiration = _sf_aspiration("srcfilt_excite", aspiration)
+    exc = torch.empty(B, N, dtype=torch.float32, device=f0.device)
+    L.check(L.load().sa_srcfilt_excite(_f(f0), _f(pos_q), _f(period_q), _f(count), _f(seed), _f(n_valid), B, N, T,
+                                       C.c_float(aspiration), _f(exc), L.stream()), "sa_srcfilt_excite")
+    return exc
+
+
+def srcfilt_synth(wav, exc, n_valid, level=True, return_status=False):
+    """wav fp32 [B, N] at 16 kHz, exc fp32 [B, N], n_valid int32 [B] -> (out fp32 [B, N], gain fp32 [B]): every frame
+    of sa_mcadams's framing is its own order-20 all-pole filter driven by the windowed excitation, scaled so that the
+    frame keeps its prediction-error energy; ``level``: the RMS over the samples below n_valid_b brought back to the
+    input's (sa_srcfilt_synth).  return_status: also int32 [B, T'], 0 a frame that was resynthesised, 1 a silent one,
+    2 one kept as it was (the fit failed), 3 one without excitation (written as zeros)."""
+    if _sf_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    _sf_dims("srcfilt_synth", B, N)
+    _sf_in(exc, "exc", shape=(B, N))
+    _sf_in(n_valid, "n_valid", torch.int32, (B,))
+    out = torch.empty_like(wav)
+    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
+    status = torch.empty(B, mcadams_frames(N), dtype=torch.int32, device=wav.device) if return_status else None
+    ws = srcfilt_workspace(B, N, wav.device)
+    L.check(L.load().sa_srcfilt_synth(_f(wav), _f(exc), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws),
+                                      _f(status), _f(gain), L.stream()), "sa_srcfilt_synth")
+    return (out, gain, status) if return_status else (out, gain)
+
+
+def srcfilt(wav, f0, rho_q, seed, n_valid, aspiration=0.3, level=True, return_status=False):
+    """wav fp32 [B, N], f0 fp32 [B, T], rho_q int32 [B, T] or None, seed int32 [B], n_valid int32 [B] -> (out fp32
+    [B, N], gain fp32 [B], count int32 [B][, status int32 [B, T']]): the waveform's LPC envelope and level under a
+    pulse/noise excitation at rho_q / 2^16 times its own pitch -- pulses, excitation and synthesis in a row, and
+    nothing copied to the host"""
+    if _sf_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    if _sf_in(f0, "f0").dim() != 2 or f0.shape[0] != B:
+        raise L.SaHipError(f"f0: expected [{B}, T], got {tuple(f0.shape)}")
+    _sf_track("srcfilt", f0, rho_q, n_valid, N)
+    _sf_in(seed, "seed", torch.int32, (B,))
+    _sf_aspiration("srcfilt", aspiration)
+    pos_q, period_q, count = srcfilt_pulses(f0, rho_q, n_valid, N=N)
+    exc = srcfilt_excite(f0, pos_q, period_q, count, seed, n_valid, aspiration, N=N)
+    res = srcfilt_synth(wav, exc, n_valid, level, return_status)
+    return (res[0], res[1], count) + tuple(res[2:])

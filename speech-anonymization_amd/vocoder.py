@@ -193,7 +193,10 @@ RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
 
 def anonymize_mode(settings):
     """what anonymize.py runs: formant_norm (--formant_norm true or --formant_norm_ratio X), mcadams,
-    pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough or model"""
+    pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough or model; before all of them resynth
+    (--resynth true)"""
+    if settings.get("resynth"):
+        return "resynth"
     if settings.get("formant_norm") or settings.get("formant_norm_ratio") is not None:
         return "formant_norm"
     if any(settings.get(k) is not None for k in ("mcadams", "mcadams_min", "mcadams_max")):
@@ -208,7 +211,7 @@ def anonymize_mode(settings):
 def check_anonymize_options(settings, run_opts, environ=None):
     """what anonymize.py refuses before anything touches a GPU, one line each"""
     import os
-    from . import formantnorm, mcadams, pitchnorm           # (all import this module)
+    from . import formantnorm, mcadams, pitchnorm, sourcefilter             # (all import this module)
     environ = os.environ if environ is None else environ
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
@@ -226,6 +229,31 @@ def check_anonymize_options(settings, run_opts, environ=None):
             if given[flag]:
                 raise SystemExit(text.format(flag))
 
+    if mode == "resynth":                                   # (no model, no checkpoint, no STFT)
+        sourcefilter.check_resynth_options(settings)
+        given["--formant_norm"] = settings.get("formant_norm") or settings.get("formant_norm_ratio") is not None
+        exclude("--resynth true and {} exclude each other: the source-filter resynthesis runs no model and no other "
+                "transform; it keeps every frame's LPC envelope and replaces its excitation", "--formant_norm",
+                "--mcadams", "--recon_ckpt", "--passthrough true", "--formant_ratio", "--preserve_formants true")
+        if settings.get("pitch_norm"):
+            raise SystemExit("--resynth true and --pitch_norm true exclude each other: the pulses are laid down at the "
+                             "period asked for, so --resynth_pitch_hz X moves the pitch in the same pass")
+        if settings.get("pitch_target_hz") is not None:
+            raise SystemExit("--resynth true takes no --pitch_target_hz: its target is --resynth_pitch_hz X, and "
+                             "without one every utterance keeps its own pitch")
+        if phase:
+            raise SystemExit("--resynth true and --phase exclude each other: there is no STFT whose phases could be "
+                             "chosen")
+        for key in ("psola", "contour_scale", "contour_smooth", "lifter") + formantnorm.FLAGS[1:]:
+            if settings.get(key) is not None:
+                raise SystemExit(f"--resynth true takes no --{key}: that option steers another path, and the "
+                                 "resynthesis has no grains, no contour, no cepstral envelope and no formant target")
+    else:
+        if settings.get("resynth") is not None and not isinstance(settings.get("resynth"), bool):
+            raise SystemExit(f"--resynth {settings.get('resynth')}: true or false")
+        for key in sourcefilter.FLAGS[1:]:
+            if settings.get(key) is not None:
+                raise SystemExit(f"--{key} goes with --resynth true: nothing else synthesises an excitation")
     if mode == "formant_norm":                              # (no model, no checkpoint, no STFT)
         formantnorm.check_formant_norm_options(settings)
         exclude("--formant_norm and {} exclude each other: the formant normalisation runs no model and no envelope "
@@ -258,7 +286,8 @@ def check_anonymize_options(settings, run_opts, environ=None):
     if pitchnorm.check_psola_option(settings).get("psola") and not pitch:                  # 
         raise SystemExit("--psola true goes with --pitch_norm true: it is the pitch normalisation done in the time "
                          "domain, grains between pitch marks laid down again at the new spacing")
-    if pitchnorm.check_f0_option(settings) and not pitch and mode != "formant_norm" and not settings.get("report_f0") \
+    if pitchnorm.check_f0_option(settings) and not pitch and mode not in ("formant_norm", "resynth") and \
+            not settings.get("report_f0") \
             and settings.get("report_prosody") is not True and settings.get("report_formants") is not True:
         raise SystemExit("--f0_method goes with --pitch_norm true or --report_f0 true: nothing else tracks F0")  # (21)
     if mode in ("passthrough", "model") and settings.get("model_type") not in ANON_MODEL_TYPES:

@@ -20,6 +20,8 @@ moved, all three together (formant_shift) and one by one (f1_shift, f2_shift, f3
   formant_norm, formant_norm_psola
                           formant normalisation to (550, 1650, 2750) Hz (--formant_norm true), alone
                           and with --pitch_norm true --psola true behind it: both cues at their targets
+  resynth, resynth_170    LPC source-filter resynthesis (--resynth true): every frame's envelope under
+                          a pulse/noise excitation, at the utterance's own pitch and with --resynth_pitch_hz 170
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech; the formant columns in
@@ -47,7 +49,9 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("pitch_norm_psola", ["--pitch_norm", "true", "--psola", "true"]),
          ("pitch_norm_psola_contour", ["--pitch_norm", "true", "--psola", "true", "--contour_scale", "1"]),
          ("formant_norm", ["--formant_norm", "true"]),
-         ("formant_norm_psola", ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"]))
+         ("formant_norm_psola", ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"]),
+         ("resynth", ["--resynth", "true"]),
+         ("resynth_170", ["--resynth", "true", "--resynth_pitch_hz", "170"]))
 
 
 def _mean(vals):
