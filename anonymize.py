@@ -7,6 +7,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
         [--phase griffin_lim|vocoder] [--contour_scale G [--contour_smooth S]] [--f0_method yin|viterbi]
         [--psola true] [--formant_norm true [--formant_target F1,F2,F3]] [--formant_norm_ratio X]
         [--resynth true [--resynth_pitch_hz X] [--aspiration A]]
+        [--modspec_cutoff_hz X [--modspec_depth D]]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
         [--report_formants true]
 
@@ -57,6 +58,15 @@ becomes X, in the same pass.  ``--aspiration A`` in [0, 1] (default 0.3, a conve
 frame's pulses; ``--seed`` seeds the noise.  It takes no other mode's flag.  Its JSON line carries ``"resynth": true``
 and per utterance ``pulses``, ``ratio``, ``gain``, ``silent_frames``, ``fallback_frames``, ``unexcited_frames`` and
 ``peak``.
+
+``--modspec_cutoff_hz X [--modspec_depth D]`` runs no model and reads no checkpoint either: OUT receives every
+waveform with its modulation spectrum smoothed (speech_anonymization_amd.modspec) -- the log
+magnitude of every STFT bin is low-pass filtered along time at X Hz (3.2 to 50 of the 100 Hz frame rate; a Hann-windowed
+sinc of ceil(200 / X) taps a side), the input's phases are kept and the result is inverted once: no Griffin-Lim, no
+tracker, no random numbers.  ``--modspec_depth D`` in [0, 1] (default 1) applies that share of the smoothing; without
+the cutoff it is refused.  It takes no other mode's flag.  Its JSON line carries ``"modspec": true``, ``cutoff_hz``,
+``depth``, ``taps`` (the taps a side), ``"n_iter": null`` and per utterance ``frames`` (the STFT frames that were
+filtered) and ``peak``.  A cutoff of 10 Hz is a convention, not validated on speech.
 
 ``--phase vocoder`` (with --pitch_norm true and/or --formant_ratio X) carries the input's own phases through the
 stretch instead of reconstructing them with Griffin-Lim (speech_anonymization_amd.ops.pv_synth):
@@ -126,8 +136,8 @@ import sys
 import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import (data, features, formantnorm, gender, mcadams, pitchnorm, reports, sourcefilter,
-                                      vocoder)
+from speech_anonymization_amd import (data, features, formantnorm, gender, mcadams, modspec, pitchnorm, reports,
+                                      sourcefilter, vocoder)
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -251,6 +261,20 @@ def _resynth(settings, device, bs, seed):
     return step, {"resynth": True}, {k: v for k, v in opts.items() if k != "f0_method"}
 
 
+def _modspec(settings, device, bs, seed):
+    """--modspec_cutoff_hz X: every utterance's log |STFT| low-pass filtered along time, inverted once, written; no
+    model"""
+    opts = modspec.check_modspec_options(settings)
+    ms = modspec.ModulationSmoother(**opts)
+
+    def step(ids, wavs, lens):
+        out = ms(wavs, lens)
+        frames = ms.last[1].cpu().tolist()
+        return out, _counts(lens, out.shape[1]), [{"frames": frames[i]} for i in range(len(ids))], None
+
+    return step, {"modspec": True, "cutoff_hz": ms.cutoff_hz, "depth": ms.depth, "taps": ms.J, "n_iter": None}, {}
+
+
 def _model(settings, device, bs, seed):
     """an anonymiser's reconstruction (or with --passthrough true the original features) inverted by Griffin-Lim"""
     mt, passthrough = settings["model_type"], bool(settings.get("passthrough"))
@@ -292,7 +316,7 @@ def _model(settings, device, bs, seed):
                   "n_iter": gl.n_iter, "seed": seed}, {}
 
 
-MODES = {"resynth": _resynth, "formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
+MODES = {"modspec": _modspec, "resynth": _resynth, "formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
          "model": _model}
 
 

@@ -1055,6 +1055,48 @@ int sa_srcfilt_excite(const float* f0, const long long* pos_q, const int* period
 int sa_srcfilt_synth(const float* wav, const float* exc, const int* n_valid, int B, int N, int level, float* out,
                      void* ws, int* status, float* gain, void* stream);
 
+/* ---- modulation-spectrum smoothing (sa_modspec.hip; modspec.py, ops.modspec_smooth): every STFT
+ * bin's log-magnitude trajectory is low-pass filtered along time by a symmetric FIR, the input's phases are kept, and
+ * the caller inverts once.  The only transform here that acts between frames.  n_fft 400, hop 160, 201 bins, 100
+ * frames a second.
+ *   R, C: [B][T][201] complex64 (interleaved re, im fp32), C != R.
+ *   taps: device fp64 [J + 1], the half h[0..J] of a symmetric FIR along time, used as given (ops.modspec_taps
+ *     normalises it to h0 + 2 sum h_j = 1).
+ *   depth: [B] fp32, read on the device; a value outside [0, 1] is taken as the nearer bound and a NaN as 0.
+ *   frames: [B] int32, clamped to [0, T]: T_b, the frames of row b that count.
+ *   peak: [B] fp64, receives peak_b (0 for a row with T_b = 0).
+ *   Lout: NULL, or fp64 [B][T][201], receives L + g (tests); 0 for t >= T_b.
+ *   Per row b, in fp64 formed from the fp32 values:
+ *     m[t][k] = sqrt(re^2 + im^2): the products are exact, the sum and the root are rounded once each;
+ *     peak_b = max over t < T_b and all k of m (a maximum is exact in any order);
+ *     fl_b = max(floor_rel peak_b, 1e-10);   L[t][k] = ln(max(m, fl_b));
+ *     for t < T_b:  s = h0 L[t] + sum_{j = 1..J} h_j (L[c(t - j)] + L[c(t + j)]), j ascending, c(i) = clamp(i, 0,
+ *       T_b - 1) (edge replication, as sa_pitch_contour does); each pair is added first, and its product with h_j is
+ *       fused into the running sum (one rounding per j after the pair's);
+ *     g = clamp(d_b (s - L[t]), +-max_gain_ln);
+ *     C[t][k] = (fp32(re e^g), fp32(im e^g)), each rounded once from the fp64 product.
+ *   The phase is kept by construction: no atan2, no division; R = 0 gives C = 0.
+ *   Copied bit for bit from R: the frames t >= T_b of every row, and every frame of a row with d_b = 0 (after the
+ *   clamp) or T_b = 0.  J = 0 with h0 = 1 gives C = R by arithmetic (g = 0).
+ *   R is taken as finite; what a non-finite value spoils is unspecified.  No address depends on data.
+ *   Two launches: the row peak as per-workgroup partial maxima of re^2 + im^2 into ws (the root is monotonic, so the
+ *   root of the largest sum is the largest root), reduced by every workgroup of the second launch that reads them;
+ *   then the smoothing pass, one workgroup per (sa_modspec_dim(4) frames) x (sa_modspec_dim(5) bins) tile, which
+ *   stages fp64 L of the tile and J frames either side in LDS.  No atomics, every sum in a fixed order, no workgroup
+ *   waits on another, a row's result does not depend on its neighbours: the same bits on every run and in every batch.
+ *   ws: the caller's, sa_modspec_workspace_bytes(B, T) = 8 B min(ceil(T / 64), 256) bytes, 8-byte aligned; its
+ *     contents mean nothing between calls.
+ *   sa_modspec_dim(which): 0 n_fft 400, 1 hop 160, 2 bins 201, 3 the largest J 64, 4 frames per workgroup 128,
+ *     5 bins per workgroup 16, 6 consecutive frames per thread 8, 7 the most partial maxima per row 256, 8 the fewest
+ *     frames per partial maximum 64; else -EINVAL.
+ *   sa_modspec_workspace_bytes(B, T): the size above, or -EINVAL for a B or T the kernels refuse.
+ *   -EINVAL, before any launch: a NULL pointer (Lout may be NULL), C == R, B < 1 or > 65535, T < 1 or > 2^23, J outside
+ *     0..64, floor_rel outside (0, 1) (a NaN too), max_gain_ln <= 0 (a NaN too). */
+long long sa_modspec_workspace_bytes(int B, int T);
+int sa_modspec_dim(int which);
+int sa_modspec_smooth(const void* R, const double* taps, int J, const float* depth, const int* frames, int B, int T,
+                      float floor_rel, float max_gain_ln, void* C, double* peak, double* Lout, void* ws, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -6,6 +6,7 @@ current torch stream.  Activations are channels-last [B, L, C] (see include/sa_h
 import collections
 import ctypes as C
 import functools
+import math
 import sys
 
 import torch
@@ -2011,3 +2012,75 @@ def srcfilt(wav, f0, rho_q, seed, n_valid, aspiration=0.3, level=True, return_st
     exc = srcfilt_excite(f0, pos_q, period_q, count, seed, n_valid, aspiration, N=N)
     res = srcfilt_synth(wav, exc, n_valid, level, return_status)
     return (res[0], res[1], count) + tuple(res[2:])
+
+
+# ---- modulation-spectrum smoothing (csrc/sa_modspec.hip; modspec.py) ----
+MODSPEC_JMAX = 64                          # sa_modspec_dim(3)
+MODSPEC_FRAME_RATE = 100.0                 # 16000 / 160 frames a second
+MODSPEC_CUTOFF_LOW, MODSPEC_CUTOFF_HIGH = 3.2, 50.0      # J = ceil(200 / cutoff) stays under 64; 50 Hz is Nyquist
+
+_ms_in = functools.partial(_aug_in, family="modulation-spectrum")
+_modspec_taps = {}
+
+
+def _modspec_half(cutoff_hz):
+    """h[0..J] of modspec_taps as Python floats: a Hann-windowed sinc, the sine taken of the argument's distance to
+    the nearest whole number so that a whole argument gives an exact zero (at 50 Hz the taps are the identity)"""
+    J = math.ceil(200.0 / cutoff_hz)
+    h = []
+    for j in range(J + 1):
+        x = 2.0 * cutoff_hz * j / MODSPEC_FRAME_RATE
+        n = round(x)
+        sinc = 1.0 if x == 0.0 else (-1.0 if n % 2 else 1.0) * math.sin(math.pi * (x - n)) / (math.pi * x)
+        h.append(sinc * (0.5 + 0.5 * math.cos(math.pi * j / (J + 1))))
+    total = h[0] + 2.0 * math.fsum(h[1:])
+    return [v / total for v in h], J
+
+
+def modspec_taps(cutoff_hz, device):
+    """(taps fp64 [J + 1] on ``device``, J): the half h[0..J] of the symmetric low-pass along time at ``cutoff_hz`` of
+    the 100 Hz frame rate, J = ceil(200 / cutoff_hz), h_j ~ sinc(2 cutoff j / 100) (0.5 + 0.5 cos(pi j / (J + 1))),
+    normalised to h0 + 2 sum h_j = 1; built in fp64 on the host once per (cutoff, device)"""
+    if isinstance(cutoff_hz, bool) or not MODSPEC_CUTOFF_LOW <= float(cutoff_hz) <= MODSPEC_CUTOFF_HIGH:
+        raise L.SaHipError(f"modspec_taps: cutoff_hz {cutoff_hz} in {MODSPEC_CUTOFF_LOW:g}..{MODSPEC_CUTOFF_HIGH:g} "
+                           "expected (the filter has at most 64 taps a side, and 50 Hz is the frame rate's Nyquist)")
+    key = (float(cutoff_hz), torch.device(device))
+    t = _modspec_taps.get(key)
+    if t is None:
+        h, _ = _modspec_half(key[0])
+        t = _modspec_taps[key] = torch.tensor(h, dtype=torch.float64).to(key[1])
+    return t, t.numel() - 1
+
+
+def modspec_workspace(B, T, device):
+    """the workspace sa_modspec_smooth takes (sa_modspec_workspace_bytes: the partial maxima of every row), as one
+    8-byte-aligned buffer"""
+    nbytes = L.load().sa_modspec_workspace_bytes(int(B), int(T))
+    if nbytes < 0:
+        raise L.SaHipError(f"modspec_workspace: [B, T] = [{B}, {T}] refused")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def modspec_smooth(R, taps, depth, frames, floor_rel=1e-4, max_gain_db=40.0, return_log=False):
+    """R complex64 [B, T, 201], taps fp64 [J + 1] (the half of a symmetric FIR along time, J up to 64), depth fp32 [B]
+    (taken into [0, 1], a NaN as 0), frames int32 [B] (clamped to [0, T]) -> (C complex64 [B, T, 201], peak fp64 [B]):
+    C = R exp(g), g = clamp(depth (smoothed L - L), +-max_gain_db ln 10 / 20), L = ln max(|R|, floor_rel peak, 1e-10)
+    with edge replication inside the row's frames; frames past them, and rows of depth 0, are R's bits
+    (sa_modspec_smooth).  return_log: also L + g fp64 [B, T, 201], zero past the row's frames (tests)."""
+    B, T = _gl_spec(R, "R", torch.complex64, _ms_in, 1)
+    if _ms_in(taps, "taps", torch.float64).dim() != 1 or not 1 <= taps.numel() <= MODSPEC_JMAX + 1:
+        raise L.SaHipError(f"taps: expected [J + 1] with J in 0..{MODSPEC_JMAX}, got {tuple(taps.shape)}")
+    _ms_in(depth, "depth", shape=(B,))
+    _ms_in(frames, "frames", torch.int32, (B,))
+    if not 0.0 < float(floor_rel) < 1.0:
+        raise L.SaHipError(f"modspec_smooth: floor_rel = {floor_rel} in (0, 1) expected")
+    if not float(max_gain_db) > 0.0:
+        raise L.SaHipError(f"modspec_smooth: max_gain_db = {max_gain_db} > 0 expected")
+    out = torch.empty_like(R)
+    peak = torch.empty(B, dtype=torch.float64, device=R.device)
+    Lout = torch.empty(B, T, 201, dtype=torch.float64, device=R.device) if return_log else None
+    ws = modspec_workspace(B, T, R.device)
+    L.check(L.load().sa_modspec_smooth(_f(R), _f(taps), taps.numel() - 1, _f(depth), _f(frames), B, T,
+                                       C.c_float(float(floor_rel)), C.c_float(float(max_gain_db) * LN10_OVER_20),
+                                       _f(out), _f(peak), _f(Lout), _f(ws), L.stream()), "sa_modspec_smooth")
+    return (out, peak, Lout) if return_log else (out, peak)

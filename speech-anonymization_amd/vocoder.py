@@ -194,7 +194,9 @@ RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
 def anonymize_mode(settings):
     """what anonymize.py runs: formant_norm (--formant_norm true or --formant_norm_ratio X), mcadams,
     pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough or model; before all of them resynth
-    (--resynth true)"""
+    (--resynth true), and before that modspec (--modspec_cutoff_hz X)"""
+    if settings.get("modspec_cutoff_hz") is not None:
+        return "modspec"
     if settings.get("resynth"):
         return "resynth"
     if settings.get("formant_norm") or settings.get("formant_norm_ratio") is not None:
@@ -211,7 +213,7 @@ def anonymize_mode(settings):
 def check_anonymize_options(settings, run_opts, environ=None):
     """what anonymize.py refuses before anything touches a GPU, one line each"""
     import os
-    from . import formantnorm, mcadams, pitchnorm, sourcefilter             # (all import this module)
+    from . import formantnorm, mcadams, modspec, pitchnorm, sourcefilter    # (all import this module)
     environ = os.environ if environ is None else environ
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
@@ -229,6 +231,19 @@ def check_anonymize_options(settings, run_opts, environ=None):
             if given[flag]:
                 raise SystemExit(text.format(flag))
 
+    if mode == "modspec":                                   # (no model, no checkpoint, one ISTFT)
+        modspec.check_modspec_options(settings)
+        for key in sourcefilter.FLAGS + formantnorm.FLAGS + (
+                "mcadams", "mcadams_min", "mcadams_max", "pitch_norm", "pitch_target_hz", "formant_ratio",
+                "preserve_formants", "phase", "psola", "contour_scale", "contour_smooth", "lifter", "recon_ckpt",
+                "passthrough"):
+            if settings.get(key) is not None:
+                raise SystemExit(f"--modspec_cutoff_hz takes no --{key}: the modulation smoothing runs no model and no "
+                                 "other transform; it filters every STFT bin's log magnitude along time, keeps the "
+                                 "input's phases and inverts once")
+    elif settings.get("modspec_depth") is not None:
+        raise SystemExit("--modspec_depth goes with --modspec_cutoff_hz X: the depth is the share of that smoothing "
+                         "that is applied")
     if mode == "resynth":                                   # (no model, no checkpoint, no STFT)
         sourcefilter.check_resynth_options(settings)
         given["--formant_norm"] = settings.get("formant_norm") or settings.get("formant_norm_ratio") is not None

@@ -5,16 +5,18 @@
 
 Every output tensor (the waveforms and ``last``) of PitchNormalizer over phase x formants x f0_method x contour, of
 FormantShifter in both phases, of McAdams with a fixed coefficient and with a range, of FormantNormalizer to its
-default target and with a fixed ratio and of SourceFilter at the utterance's own pitch and to 170 Hz, each on
+default target and with a fixed ratio, of SourceFilter at the utterance's own pitch and to 170 Hz and of
+ModulationSmoother at 10 Hz and at 5 Hz with depth 0.5, each on
 data.synthetic_gender_dataset(6, 3) and on one batch of width 16037 (no multiple of the hop) with lens (1.0, 0.73,
-0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of ten anonymize.py modes,
+0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of twelve anonymize.py modes,
 each with --report_f0 and --report_stoi (``anonymize/<mode>``) and with all four reports (``anonymize_reports/<mode>``).
 Prints one JSON object with one digest per transform and input (over the digests of its tensors, batch by batch) and
 one per mode (over its JSON line and its WAV files by name); ``--each`` prints every item's own digest instead, to find
 what differs.  profiles/anon_reports_digest.json is its output before the formant normalisation's groups
 (FormantNormalizer/*, */formant_norm*), which every later output has to contain unchanged, and
 profiles/anon_formant_norm_digest.json its output with them, the 76 groups before the source-filter resynthesis's
-(SourceFilter/*, */resynth*), and profiles/anon_resynth_digest.json its output with those;
+(SourceFilter/*, */resynth*), profiles/anon_resynth_digest.json its output with those, the 84 groups before the
+modulation smoothing's (ModulationSmoother/*, */modspec*), and profiles/anon_modspec_digest.json its output with those;
 profiles/anon_refactor_digest.json the 62 groups it had before the second family."""
 import contextlib
 import hashlib
@@ -31,7 +33,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import speech_anonymization_amd as pkg  # noqa: E402,F401  (registers the package name)
-from speech_anonymization_amd import data, formantnorm, mcadams, pitchnorm, sourcefilter  # noqa: E402
+from speech_anonymization_amd import data, formantnorm, mcadams, modspec, pitchnorm, sourcefilter  # noqa: E402
 
 MODES = {"passthrough": ["--passthrough", "true"],
          "pitch_norm": ["--pitch_norm", "true"],
@@ -43,7 +45,9 @@ MODES = {"passthrough": ["--passthrough", "true"],
          "formant_norm": ["--formant_norm", "true"],
          "formant_norm_psola": ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"],
          "resynth": ["--resynth", "true"],
-         "resynth_170": ["--resynth", "true", "--resynth_pitch_hz", "170"]}
+         "resynth_170": ["--resynth", "true", "--resynth_pitch_hz", "170"],
+         "modspec": ["--modspec_cutoff_hz", "10"],
+         "modspec_5_half": ["--modspec_cutoff_hz", "5", "--modspec_depth", "0.5"]}
 COMMON = ["--synthetic", "3", "--batch_size", "3", "--n_iter", "2", "--report_f0", "true", "--report_stoi", "true"]
 # family -> what its runs add to COMMON: the modes as they always ran, and with all four reports on
 FAMILIES = {"anonymize": [],
@@ -84,6 +88,8 @@ def transforms():
     out["FormantNormalizer/ratio_0.9"] = lambda: formantnorm.FormantNormalizer(ratio=0.9)
     out["SourceFilter/own_pitch"] = lambda: sourcefilter.SourceFilter()
     out["SourceFilter/target_170"] = lambda: sourcefilter.SourceFilter(170.0)
+    out["ModulationSmoother/cutoff_10"] = lambda: modspec.ModulationSmoother()
+    out["ModulationSmoother/cutoff_5_depth_0.5"] = lambda: modspec.ModulationSmoother(5.0, 0.5)
     return out
 
 

@@ -22,6 +22,8 @@ moved, all three together (formant_shift) and one by one (f1_shift, f2_shift, f3
                           and with --pitch_norm true --psola true behind it: both cues at their targets
   resynth, resynth_170    LPC source-filter resynthesis (--resynth true): every frame's envelope under
                           a pulse/noise excitation, at the utterance's own pitch and with --resynth_pitch_hz 170
+  modspec_10              modulation-spectrum smoothing (--modspec_cutoff_hz 10): every STFT bin's log
+                          magnitude low-pass filtered along time at 10 Hz, the input's phases kept
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech; the formant columns in
@@ -51,7 +53,8 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("formant_norm", ["--formant_norm", "true"]),
          ("formant_norm_psola", ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"]),
          ("resynth", ["--resynth", "true"]),
-         ("resynth_170", ["--resynth", "true", "--resynth_pitch_hz", "170"]))
+         ("resynth_170", ["--resynth", "true", "--resynth_pitch_hz", "170"]),
+         ("modspec_10", ["--modspec_cutoff_hz", "10"]))
 
 
 def _mean(vals):
