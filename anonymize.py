@@ -8,6 +8,7 @@ are inverted to a waveform by Griffin-Lim (speech_anonymization_amd.vocoder; DES
         [--psola true] [--formant_norm true [--formant_target F1,F2,F3]] [--formant_norm_ratio X]
         [--resynth true [--resynth_pitch_hz X] [--aspiration A]]
         [--modspec_cutoff_hz X [--modspec_depth D]]
+        [--tempo X | --tempo_min LO --tempo_max HI]
         [--report_prosody true [--prosody_max_lag K]] [--report_mcd true [--mcd_band R] [--mcd_order K]]
         [--report_formants true]
 
@@ -67,6 +68,16 @@ tracker, no random numbers.  ``--modspec_depth D`` in [0, 1] (default 1) applies
 the cutoff it is refused.  It takes no other mode's flag.  Its JSON line carries ``"modspec": true``, ``cutoff_hz``,
 ``depth``, ``taps`` (the taps a side), ``"n_iter": null`` and per utterance ``frames`` (the STFT frames that were
 filtered) and ``peak``.  A cutoff of 10 Hz is a convention, not validated on speech.
+
+``--tempo X`` (or ``--tempo_min LO --tempo_max HI``: one tempo per utterance, drawn from [LO, HI] by a host generator
+seeded with ``--seed``) runs no model and reads no checkpoint either: OUT receives every waveform played at X times its
+speed, 0.5 to 2 (speech_anonymization_amd.timescale) -- WSOLA: 20 ms windows copied at a 10 ms hop,
+each cut within +-10 ms of its nominal place where it continues the previous one best.  Pitch and envelope stay, the
+duration becomes n / X; no STFT, no phase, no iteration, no random number in the transform.  It takes no other mode's
+flag, and none of --report_stoi, --report_prosody, --report_mcd and --report_formants, which compare input and output
+frame against frame; ``--report_f0 true`` measures over the samples written.  Its JSON line carries ``"tempo": true``,
+``"n_iter": null`` and per utterance ``tempo``, ``samples_in``, ``frames`` (the windows), ``jumps`` (the windows that
+do not continue their predecessor) and ``peak``.
 
 ``--phase vocoder`` (with --pitch_norm true and/or --formant_ratio X) carries the input's own phases through the
 stretch instead of reconstructing them with Griffin-Lim (speech_anonymization_amd.ops.pv_synth):
@@ -137,7 +148,7 @@ import torch
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
 from speech_anonymization_amd import (data, features, formantnorm, gender, mcadams, modspec, pitchnorm, reports,
-                                      sourcefilter, vocoder)
+                                      sourcefilter, timescale, vocoder)
 from speech_anonymization_amd.yaml_loader import load_plain, parse_arguments
 
 
@@ -275,6 +286,25 @@ def _modspec(settings, device, bs, seed):
     return step, {"modspec": True, "cutoff_hz": ms.cutoff_hz, "depth": ms.depth, "taps": ms.J, "n_iter": None}, {}
 
 
+def _tempo(settings, device, bs, seed):
+    """--tempo X / --tempo_min LO --tempo_max HI: every utterance played at another speed (WSOLA) and written; no
+    model.  The step's fifth value: the relative lengths of what it wrote, which the reports measure over."""
+    opts = timescale.check_tempo_options(settings)
+    if "tempo_range" in opts:
+        opts["seed"] = seed
+    ts = timescale.TimeScaler(**opts)
+
+    def step(ids, wavs, lens):
+        out, lens_out = ts(wavs, lens)
+        tq, n_out, count, jumps = (v.cpu().tolist() for v in ts.last)
+        n_in = _counts(lens, wavs.shape[1])
+        return out, n_out, [{"tempo": tq[i] / 65536.0, "samples_in": n_in[i], "frames": count[i], "jumps": jumps[i]}
+                            for i in range(len(ids))], None, lens_out.cpu()
+
+    return step, {"tempo": True, "n_iter": None}, \
+        ({"tempo_range": list(opts["tempo_range"]), "seed": seed} if "tempo_range" in opts else {})
+
+
 def _model(settings, device, bs, seed):
     """an anonymiser's reconstruction (or with --passthrough true the original features) inverted by Griffin-Lim"""
     mt, passthrough = settings["model_type"], bool(settings.get("passthrough"))
@@ -316,7 +346,7 @@ def _model(settings, device, bs, seed):
                   "n_iter": gl.n_iter, "seed": seed}, {}
 
 
-MODES = {"modspec": _modspec, "resynth": _resynth, "formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
+MODES = {"tempo": _tempo, "modspec": _modspec, "resynth": _resynth, "formant_norm": _formant_norm, "mcadams": _mcadams, "pitch_norm": _pitch_norm, "formant_shift": _formant_shift, "passthrough": _model,
          "model": _model}
 
 
@@ -330,16 +360,17 @@ def main(argv):
     torch.cuda.set_device(device)
     os.makedirs(settings["out_dir"], exist_ok=True)
     # step(ids, wavs on the device, lens) -> (the waveforms to write, on the device; the samples of each row; the
-    # mode's own keys per utterance; the spectral convergence per row or None); head and tail: the mode's keys of the
-    # final object before and after "utterances"
+    # mode's own keys per utterance; the spectral convergence per row or None; from a mode that changes the duration
+    # also the relative lengths of what it wrote); head and tail: the mode's keys of the final object before and after
+    # "utterances"
     step, head, tail = MODES[vocoder.anonymize_mode(settings)](settings, device, bs, seed)
     f0m = pitchnorm.check_f0_option(settings)
     utts, active = [], reports.active(settings)
     for ids, batch in _batches(settings, bs, seed):
         wavs, lens = batch.sig
         wavs = wavs.to(device).contiguous()
-        out, counts, extra, sc = step(ids, wavs, lens)
-        scored = reports.Batch(wavs, lens, out, counts)
+        out, counts, extra, sc, *own = step(ids, wavs, lens)
+        scored = reports.Batch(wavs, own[0] if own else lens, out, counts)
         for report in active:
             report.score(ids, scored)
         out = out.cpu()

@@ -1097,6 +1097,60 @@ int sa_modspec_dim(int which);
 int sa_modspec_smooth(const void* R, const double* taps, int J, const float* depth, const int* frames, int B, int T,
                       float floor_rel, float max_gain_ln, void* C, double* peak, double* Lout, void* ws, void* stream);
 
+/* ---- WSOLA time-scale modification (sa_wsola.hip; ops.wsola_quant, ops.wsola_search, ops.wsola_ola, ops.wsola;
+ * timescale.py): windows of W = 320 samples of the input are copied to the output at a hop of
+ * H = 160, and each window's position is chosen within D = 160 samples of where the tempo says it should be, so that it
+ * continues the previous one.  The samples are moved, not altered: pitch and envelope stay, the duration changes, and
+ * there is no STFT, no phase, no iteration and no random number.  Every decision is made on integers; the overlap-add
+ * is two fp32 products and one fp32 sum.  tests/wsola_ref.py restates all of it and agrees with the kernels exactly.
+ *   Per row b:  wav [N] fp32;  n_valid int32, clamped to [0, N];  tempo_q int32 in units of 2^-16, clamped to
+ *   [2^15, 2^17] where it is read; above 2^16 is faster, a shorter output.
+ *   1. Length.  n_out = min(Nout, (n_valid 2^16 + tempo_q / 2) / tempo_q) in int64 (/ truncates), 0 when n_valid = 0;
+ *     K = (n_out - 1) / H + 1, 0 when n_out = 0.  sa_wsola_out_len(n, tempo_q) is the same figure before the cap.
+ *   2. Search signal.  s = the largest finite |wav[n]|, n < n_valid.  q[n] = rint((double)wav[n] 16383 / (double)s) as
+ *     int16: the product is exact, the division rounds once, ties go to even.  q[n] = 0 where the sample is not
+ *     finite, where s = 0, and for n >= n_valid; a q read outside [0, n_valid) is 0.
+ *   3. Positions.  p_0 = 0.  For k = 1 .. K - 1, with int64 products: a = (k H tempo_q + 2^15) >> 16 and
+ *     t = p_{k-1} + H.  The candidates c are the integers of [lo, hi], lo = max(a - D, 0), hi = min(a + D,
+ *     max(n_valid - 1, 0)); when hi < lo the one candidate is hi.  cost(c) = sum_{n < W} |q[t + n] - q[c + n]|, an
+ *     integer below 2^24 and so exact in any order.  p_k is the candidate of least cost; ties go to the smallest
+ *     |c - a|, then to the smaller c.  A silent or constant stretch therefore follows a; at tempo_q = 2^16 the cost at
+ *     c = t = a is 0 and p_k = k H.
+ *   4. Overlap-add.  For m < n_out, k = m / H, r = m - k H;  X(i) = wav[i] for 0 <= i < n_valid and 0 elsewhere;
+ *     hann[j] = 0.5 - 0.5 cos(2 pi j / W), j < W, formed in fp64 by the caller and rounded once (a table of W floats:
+ *     a device cosine may round differently).  out[m] = X(p_k + r), the sample's own bits, when k = 0 or
+ *     p_k = p_{k-1} + H (both windows hold the same sample there: contiguous stretches and the whole of tempo 1 are
+ *     copies).  Otherwise out[m] = fl(fl(hann[r] X(p_k + r)) + fl(hann[r + H] X(p_{k-1} + H + r))) in fp32, each
+ *     operation rounded on its own, no fused multiply-add; a sum that is a NaN is written as 0x7fc00000 (which NaN
+ *     an invalid operation gives is not the same on every machine).  out[m] = 0 for n_out <= m < Nout.
+ *   Outputs: out [B][Nout] fp32;  pos [B][Kcap] int32, Kcap = (Nout - 1) / H + 1, entries from count on mean nothing;
+ *   count [B] = K;  n_out [B].
+ *   sa_wsola_quant: two launches, the partial maxima of every 4096 samples and then q, int16 [B][N] at the start of
+ *     ws; the rest of ws holds the partial maxima.  ws: the caller's, sa_wsola_workspace_bytes(B, N) bytes, 16-byte
+ *     aligned.  sa_wsola_search: one workgroup per row walks step 3 over q staged through LDS sa_wsola_dim(4) samples
+ *     at a time, and writes pos, count and n_out.  sa_wsola_ola: step 4; it forms n_out from n_valid and tempo_q as
+ *     step 1 does, reads count (clamped to [0, Kcap]; a sample of a frame from count on is 0) and pos (clamped to
+ *     [0, N]) -- none of which changes tables sa_wsola_search wrote.  sa_wsola: the three in a row.
+ *   No atomics, fixed orders, a row's result does not depend on its neighbours: the same bits on every run and in
+ *   every batch.
+ *   sa_wsola_dim(which): 0 H = 160, 1 W = 320, 2 D = 160, 3 Q = 16383, 4 the samples per staged chunk of the search,
+ *     5 the samples per workgroup of the overlap-add, 6 the samples per partial maximum; else -EINVAL.
+ *   sa_wsola_out_len(n, tempo_q): step 1's quotient, or -EINVAL for n < 0 or > 2^24.
+ *   sa_wsola_workspace_bytes(B, N): 2 B N rounded up to 16, plus 4 B ceil((N + 3) / 4096) rounded up to 16; -EINVAL
+ *     for a B or N the kernels refuse.
+ *   -EINVAL, before any launch: a NULL pointer, B < 1 or > 65535, N < 1 or > 2^24, Nout < 1 or > 2^25, out
+ *     overlapping wav (sa_wsola_ola, sa_wsola). */
+int sa_wsola_dim(int which);
+int sa_wsola_out_len(int n, int tempo_q);
+long long sa_wsola_workspace_bytes(int B, int N);
+int sa_wsola_quant(const float* wav, const int* n_valid, int B, int N, void* ws, void* stream);
+int sa_wsola_search(const void* ws, const int* tempo_q, const int* n_valid, int B, int N, int Nout, int* pos,
+                    int* count, int* n_out, void* stream);
+int sa_wsola_ola(const float* wav, const int* pos, const int* count, const int* tempo_q, const int* n_valid,
+                 const float* hann, int B, int N, int Nout, float* out, void* stream);
+int sa_wsola(const float* wav, const int* tempo_q, const int* n_valid, const float* hann, int B, int N, int Nout,
+             void* ws, float* out, int* pos, int* count, int* n_out, void* stream);
+
 /* ---- element-wise passes of the frozen recogniser (sa_asr.hip; SURVEY 8f-2, models/SpeechBrain_ASR.py:16-30;
  * bf16 storage, fp32 arithmetic; the GEMMs around them are library calls).
  *   sa_add_layernorm_fwd: s = bf16(x + r) (r may be NULL), y = LayerNorm_d(s) * gamma + beta over rows of d

@@ -143,6 +143,7 @@ SYMBOLS = [
     "sa_pole_warp_dim", "sa_pole_warp", "sa_formant_centre",
     "sa_srcfilt_dim", "sa_srcfilt_pulses", "sa_srcfilt_excite", "sa_srcfilt_synth",
     "sa_modspec_dim", "sa_modspec_smooth",
+    "sa_wsola_dim", "sa_wsola_out_len", "sa_wsola_quant", "sa_wsola_search", "sa_wsola_ola", "sa_wsola",
 ]
 
 _lib = None
@@ -163,10 +164,11 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         for s in SYMBOLS:
             getattr(_lib, s).restype = C.c_int
-        _lib.sa_pv_workspace_bytes.restype = C.c_longlong     # (the four entry points that do not return an int)
+        _lib.sa_pv_workspace_bytes.restype = C.c_longlong     # (the five entry points that do not return an int)
         _lib.sa_psola_workspace_bytes.restype = C.c_longlong
         _lib.sa_srcfilt_workspace_bytes.restype = C.c_longlong
         _lib.sa_modspec_workspace_bytes.restype = C.c_longlong
+        _lib.sa_wsola_workspace_bytes.restype = C.c_longlong
         for i, rec in enumerate((SaConvArgs, SaWgradArgs, SaEwArgs, SaPackDesc, SaTaps, SaBiasMulti, SaWredMulti, SaFlats)):
             if _lib.sa_abi_sizeof(i) != C.sizeof(rec):
                 raise SaHipError(f"{rec.__name__}: binding has {C.sizeof(rec)} bytes, {LIB_PATH} "

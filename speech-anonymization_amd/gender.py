@@ -391,3 +391,20 @@ class GenderFormantNormBrain(GenderBrain):
         if pn is not None:
             wavs = pn(wavs, lens)
         return super().prepare_features(wavs, lens, stage)
+
+
+class GenderTempoBrain(GenderBrain):
+    """gender_classifier_train_tempo.py: ``hparams.time_scaler`` (timescale.TimeScaler) plays every
+    waveform at another tempo at every stage, train, valid and test alike, before augmentation and features.  The
+    batch's width and its relative lengths change, so the scaler's own lengths go on to the normaliser and the
+    pooling.  It is given the loader's CPU lengths: the output's width is then known without a device read."""
+
+    def compute_forward(self, batch, stage):
+        host_lens = batch.sig[1]
+        batch = batch.to(self.device)
+        wavs, lens = self.hparams.time_scaler(batch.sig[0], host_lens)
+        self._host_lens = None                               # (the lengths changed: the augmentation reads the device's)
+        feats = self.prepare_features(wavs, lens, stage)
+        if self.__dict__.get("_aug"):
+            lens = self._aug[0]
+        return xvector.train_log_probs(self.modules.embedding_model, self.modules.classifier, feats, lens)

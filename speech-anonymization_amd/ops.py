@@ -2084,3 +2084,139 @@ def modspec_smooth(R, taps, depth, frames, floor_rel=1e-4, max_gain_db=40.0, ret
                                        C.c_float(float(floor_rel)), C.c_float(float(max_gain_db) * LN10_OVER_20),
                                        _f(out), _f(peak), _f(Lout), _f(ws), L.stream()), "sa_modspec_smooth")
     return (out, peak, Lout) if return_log else (out, peak)
+
+
+# ---- WSOLA time-scale modification (csrc/sa_wsola.hip; timescale.py) ----
+WSOLA_H, WSOLA_W, WSOLA_D, WSOLA_Q = 160, 320, 160, 16383          # sa_wsola_dim(0..3)
+WSOLA_MAX_N, WSOLA_MAX_NOUT = 1 << 24, 1 << 25
+WSOLA_ONE = 1 << 16                        # tempo_q of tempo 1; the kernels take 2^15..2^17
+WSOLA_QTILE = 4096                         # sa_wsola_dim(6): the samples per partial maximum
+
+_wso_in = functools.partial(_aug_in, family="WSOLA")
+_wsola_windows = {}
+
+
+def _wso_dims(who, B, N, Nout=None):
+    if not 1 <= B <= GL_MAX_B or not 1 <= N <= WSOLA_MAX_N:
+        raise L.SaHipError(f"{who}: [B, N] = [{B}, {N}] -- B in 1..{GL_MAX_B} (a grid extent), N in 1..{WSOLA_MAX_N}")
+    if Nout is not None and not 1 <= Nout <= WSOLA_MAX_NOUT:
+        raise L.SaHipError(f"{who}: Nout = {Nout} in 1..{WSOLA_MAX_NOUT} expected")
+
+
+def _wso_wav(who, wav, n_valid):
+    if _wso_in(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    _wso_in(n_valid, "n_valid", torch.int32, (B,))
+    _wso_dims(who, B, N)
+    return B, N
+
+
+def wsola_out_len(n, tempo_q):
+    """the samples a row of ``n`` valid ones has at ``tempo_q`` (units of 2^-16, read as 2^15..2^17): host integers,
+    (n 2^16 + tempo_q / 2) / tempo_q, what sa_wsola_out_len returns -- the host sizes the output with it"""
+    n, tq = int(n), min(max(int(tempo_q), WSOLA_ONE // 2), 2 * WSOLA_ONE)
+    if not 0 <= n <= WSOLA_MAX_N:
+        raise L.SaHipError(f"wsola_out_len: n = {n} in 0..{WSOLA_MAX_N} expected")
+    return ((n << 16) + tq // 2) // tq if n else 0
+
+
+def wsola_workspace_bytes(B, N):
+    """sa_wsola_workspace_bytes as host integers: q, then the partial maxima, each rounded up to 16 bytes"""
+    B, N = int(B), int(N)
+    return ((2 * B * N + 15) & ~15) + ((4 * B * ((N + 3 + WSOLA_QTILE - 1) // WSOLA_QTILE) + 15) & ~15)
+
+
+def wsola_workspace(B, N, device):
+    """the workspace the WSOLA kernels share (sa_wsola_workspace_bytes), int16: q [B][N] at its start"""
+    _wso_dims("wsola_workspace", int(B), int(N))
+    return torch.empty(wsola_workspace_bytes(B, N) // 2, dtype=torch.int16, device=device)
+
+
+def wsola_window(device):
+    """hann fp32 [320] on ``device``: 0.5 - 0.5 cos(2 pi j / 320), formed in fp64 on the host and rounded once; built
+    once per device"""
+    key = torch.device(device)
+    t = _wsola_windows.get(key)
+    if t is None:
+        h = [0.5 - 0.5 * math.cos(2.0 * math.pi * j / WSOLA_W) for j in range(WSOLA_W)]
+        t = _wsola_windows[key] = torch.tensor(h, dtype=torch.float64).to(torch.float32).to(key)
+    return t
+
+
+def _wso_ws(ws, B, N):
+    _wso_in(ws, "ws", torch.int16)
+    if ws.dim() != 1 or ws.numel() * 2 < wsola_workspace_bytes(B, N) or ws.data_ptr() % 16:
+        raise L.SaHipError(f"ws: expected wsola_workspace({B}, {N}), int16 [{wsola_workspace_bytes(B, N) // 2}], "
+                           f"16-byte aligned; got {tuple(ws.shape)}")
+    return ws
+
+
+def wsola_quant(wav, n_valid, ws=None):
+    """wav fp32 [B, N], n_valid int32 [B] -> q int16 [B, N], a view of the workspace's start: the search signal,
+    rint(wav 16383 / peak) with the row's largest finite |wav| below n_valid as the peak, 0 where the sample is not
+    finite or does not count (sa_wsola_quant).  ``ws``: a wsola_workspace to write into."""
+    B, N = _wso_wav("wsola_quant", wav, n_valid)
+    ws = wsola_workspace(B, N, wav.device) if ws is None else _wso_ws(ws, B, N)
+    L.check(L.load().sa_wsola_quant(_f(wav), _f(n_valid), B, N, _f(ws), L.stream()), "sa_wsola_quant")
+    return ws[:B * N].view(B, N)
+
+
+def _wso_tempo(tempo_q, B):
+    return _wso_in(tempo_q, "tempo_q", torch.int32, (B,))
+
+
+def wsola_search(q, tempo_q, n_valid, Nout):
+    """wsola_quant's q int16 [B, N], tempo_q int32 [B] (units of 2^-16, read as 2^15..2^17), n_valid int32 [B], Nout
+    -> (pos int32 [B, (Nout - 1) // 160 + 1], count int32 [B], n_out int32 [B]): where every window of the output is
+    cut from the input, how many there are and how many samples they give; entries of pos from count on mean nothing
+    (sa_wsola_search)"""
+    if _wso_in(q, "q", torch.int16).dim() != 2 or q.numel() == 0:
+        raise L.SaHipError(f"q: expected [B, N] with B, N >= 1, got {tuple(q.shape)}")
+    B, N = q.shape
+    Nout = int(Nout)
+    _wso_dims("wsola_search", B, N, Nout)
+    if q.data_ptr() % 16:
+        raise L.SaHipError("q: expected 16-byte aligned rows' start (wsola_quant's)")
+    _wso_tempo(tempo_q, B)
+    _wso_in(n_valid, "n_valid", torch.int32, (B,))
+    pos = torch.empty(B, (Nout - 1) // WSOLA_H + 1, dtype=torch.int32, device=q.device)
+    count, n_out = (torch.empty(B, dtype=torch.int32, device=q.device) for _ in range(2))
+    L.check(L.load().sa_wsola_search(_f(q), _f(tempo_q), _f(n_valid), B, N, Nout, _f(pos), _f(count), _f(n_out),
+                                     L.stream()), "sa_wsola_search")
+    return pos, count, n_out
+
+
+def wsola_ola(wav, pos, count, tempo_q, n_valid, Nout):
+    """the overlap-add of wsola_search's windows: wav fp32 [B, N], pos, count, tempo_q, n_valid, Nout -> out fp32
+    [B, Nout], zero from the row's n_out on; a stretch whose windows are contiguous in the input is a copy
+    (sa_wsola_ola)"""
+    B, N = _wso_wav("wsola_ola", wav, n_valid)
+    Nout = int(Nout)
+    _wso_dims("wsola_ola", B, N, Nout)
+    _wso_in(pos, "pos", torch.int32, (B, (Nout - 1) // WSOLA_H + 1))
+    _wso_in(count, "count", torch.int32, (B,))
+    _wso_tempo(tempo_q, B)
+    out = torch.empty(B, Nout, dtype=torch.float32, device=wav.device)
+    L.check(L.load().sa_wsola_ola(_f(wav), _f(pos), _f(count), _f(tempo_q), _f(n_valid), _f(wsola_window(wav.device)),
+                                  B, N, Nout, _f(out), L.stream()), "sa_wsola_ola")
+    return out
+
+
+def wsola(wav, tempo_q, n_valid, Nout, return_pos=False):
+    """wav fp32 [B, N], tempo_q int32 [B], n_valid int32 [B], Nout -> (out fp32 [B, Nout], n_out int32 [B]): every row
+    played at tempo_q / 2^16 of its speed, pitch and envelope kept, n_out = min(Nout, wsola_out_len(n_valid,
+    tempo_q)) samples and zeros after them -- quantisation, search and overlap-add in one library call (sa_wsola),
+    nothing copied to the host.  return_pos: also (pos, count)."""
+    B, N = _wso_wav("wsola", wav, n_valid)
+    Nout = int(Nout)
+    _wso_dims("wsola", B, N, Nout)
+    _wso_tempo(tempo_q, B)
+    dev = wav.device
+    ws = wsola_workspace(B, N, dev)
+    out = torch.empty(B, Nout, dtype=torch.float32, device=dev)
+    pos = torch.empty(B, (Nout - 1) // WSOLA_H + 1, dtype=torch.int32, device=dev)
+    count, n_out = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    L.check(L.load().sa_wsola(_f(wav), _f(tempo_q), _f(n_valid), _f(wsola_window(dev)), B, N, Nout, _f(ws), _f(out),
+                              _f(pos), _f(count), _f(n_out), L.stream()), "sa_wsola")
+    return (out, n_out, pos, count) if return_pos else (out, n_out)

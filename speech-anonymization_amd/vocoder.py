@@ -191,10 +191,18 @@ RESYNTH_MODES = {"pitch_norm": ("--pitch_norm true", "pitch-normalised"),
                  "formant_shift": ("--formant_ratio", "formant-shifted")}
 
 
+TEMPO_FLAGS = ("tempo", "tempo_min", "tempo_max")
+# what the time-scale mode refuses: the reports that compare input and output frame against frame
+TEMPO_REPORTS = ("report_stoi", "report_prosody", "report_mcd", "report_formants")
+
+
 def anonymize_mode(settings):
     """what anonymize.py runs: formant_norm (--formant_norm true or --formant_norm_ratio X), mcadams,
     pitch_norm, formant_shift (--formant_ratio without --pitch_norm), passthrough or model; before all of them resynth
-    (--resynth true), and before that modspec (--modspec_cutoff_hz X)"""
+    (--resynth true), before that modspec (--modspec_cutoff_hz X), and before
+    that tempo (--tempo X or --tempo_min LO --tempo_max HI)"""
+    if any(settings.get(k) is not None for k in TEMPO_FLAGS):
+        return "tempo"
     if settings.get("modspec_cutoff_hz") is not None:
         return "modspec"
     if settings.get("resynth"):
@@ -213,7 +221,7 @@ def anonymize_mode(settings):
 def check_anonymize_options(settings, run_opts, environ=None):
     """what anonymize.py refuses before anything touches a GPU, one line each"""
     import os
-    from . import formantnorm, mcadams, modspec, pitchnorm, sourcefilter    # (all import this module)
+    from . import formantnorm, mcadams, modspec, pitchnorm, sourcefilter, timescale    # (all import this module)
     environ = os.environ if environ is None else environ
     formant = pitchnorm.check_formant_options(settings)
     phase = pitchnorm.check_phase_option(settings)
@@ -231,6 +239,19 @@ def check_anonymize_options(settings, run_opts, environ=None):
             if given[flag]:
                 raise SystemExit(text.format(flag))
 
+    if mode == "tempo":                                     # (no model, no checkpoint, no STFT)
+        timescale.check_tempo_options(settings)
+        for key in ("modspec_cutoff_hz", "modspec_depth") + sourcefilter.FLAGS + formantnorm.FLAGS + (
+                "mcadams", "mcadams_min", "mcadams_max", "pitch_norm", "pitch_target_hz", "formant_ratio",
+                "preserve_formants", "phase", "psola", "contour_scale", "contour_smooth", "lifter", "recon_ckpt",
+                "passthrough"):
+            if settings.get(key) is not None:
+                raise SystemExit(f"--tempo takes no --{key}: the time-scale modification runs no model and no other "
+                                 "transform; it copies windows of the waveform to a new time axis")
+        for key in TEMPO_REPORTS:
+            if settings.get(key):
+                raise SystemExit(f"--tempo takes no --{key} true: that report compares input and output frame against "
+                                 "frame, and a changed tempo leaves no such alignment")
     if mode == "modspec":                                   # (no model, no checkpoint, one ISTFT)
         modspec.check_modspec_options(settings)
         for key in sourcefilter.FLAGS + formantnorm.FLAGS + (

@@ -5,18 +5,22 @@
 
 Every output tensor (the waveforms and ``last``) of PitchNormalizer over phase x formants x f0_method x contour, of
 FormantShifter in both phases, of McAdams with a fixed coefficient and with a range, of FormantNormalizer to its
-default target and with a fixed ratio, of SourceFilter at the utterance's own pitch and to 170 Hz and of
-ModulationSmoother at 10 Hz and at 5 Hz with depth 0.5, each on
+default target and with a fixed ratio, of SourceFilter at the utterance's own pitch and to 170 Hz, of
+ModulationSmoother at 10 Hz and at 5 Hz with depth 0.5 and of TimeScaler at tempo 0.8 and with a range (its second
+output, the relative lengths, as ``lens_out``), each on
 data.synthetic_gender_dataset(6, 3) and on one batch of width 16037 (no multiple of the hop) with lens (1.0, 0.73,
 0.5); and every WAV file and the final JSON line (its out_dir replaced by the mode's name) of twelve anonymize.py modes,
-each with --report_f0 and --report_stoi (``anonymize/<mode>``) and with all four reports (``anonymize_reports/<mode>``).
+each with --report_f0 and --report_stoi (``anonymize/<mode>``) and with all four reports (``anonymize_reports/<mode>``),
+and of the two tempo modes with --report_f0 alone (``anonymize/tempo*``: they refuse the reports that need an alignment).
 Prints one JSON object with one digest per transform and input (over the digests of its tensors, batch by batch) and
 one per mode (over its JSON line and its WAV files by name); ``--each`` prints every item's own digest instead, to find
 what differs.  profiles/anon_reports_digest.json is its output before the formant normalisation's groups
 (FormantNormalizer/*, */formant_norm*), which every later output has to contain unchanged, and
 profiles/anon_formant_norm_digest.json its output with them, the 76 groups before the source-filter resynthesis's
 (SourceFilter/*, */resynth*), profiles/anon_resynth_digest.json its output with those, the 84 groups before the
-modulation smoothing's (ModulationSmoother/*, */modspec*), and profiles/anon_modspec_digest.json its output with those;
+modulation smoothing's (ModulationSmoother/*, */modspec*), profiles/anon_modspec_digest.json its output with those, the
+92 groups before the time-scale modification's (TimeScaler/*, anonymize/tempo*), and profiles/anon_tempo_digest.json its
+output with those;
 profiles/anon_refactor_digest.json the 62 groups it had before the second family."""
 import contextlib
 import hashlib
@@ -33,7 +37,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import speech_anonymization_amd as pkg  # noqa: E402,F401  (registers the package name)
-from speech_anonymization_amd import data, formantnorm, mcadams, modspec, pitchnorm, sourcefilter  # noqa: E402
+from speech_anonymization_amd import (data, formantnorm, mcadams, modspec, pitchnorm, sourcefilter,  # noqa: E402
+                                      timescale)
 
 MODES = {"passthrough": ["--passthrough", "true"],
          "pitch_norm": ["--pitch_norm", "true"],
@@ -48,6 +53,9 @@ MODES = {"passthrough": ["--passthrough", "true"],
          "resynth_170": ["--resynth", "true", "--resynth_pitch_hz", "170"],
          "modspec": ["--modspec_cutoff_hz", "10"],
          "modspec_5_half": ["--modspec_cutoff_hz", "5", "--modspec_depth", "0.5"]}
+# the modes that change the duration: --report_f0 alone, and in the first family only
+TEMPO_MODES = {"tempo_0.8": ["--tempo", "0.8"], "tempo_range": ["--tempo_min", "0.8", "--tempo_max", "1.25"]}
+TEMPO_COMMON = ["--synthetic", "3", "--batch_size", "3", "--report_f0", "true"]
 COMMON = ["--synthetic", "3", "--batch_size", "3", "--n_iter", "2", "--report_f0", "true", "--report_stoi", "true"]
 # family -> what its runs add to COMMON: the modes as they always ran, and with all four reports on
 FAMILIES = {"anonymize": [],
@@ -90,6 +98,8 @@ def transforms():
     out["SourceFilter/target_170"] = lambda: sourcefilter.SourceFilter(170.0)
     out["ModulationSmoother/cutoff_10"] = lambda: modspec.ModulationSmoother()
     out["ModulationSmoother/cutoff_5_depth_0.5"] = lambda: modspec.ModulationSmoother(5.0, 0.5)
+    out["TimeScaler/tempo_0.8"] = lambda: timescale.TimeScaler(0.8)
+    out["TimeScaler/range_0.8_1.25"] = lambda: timescale.TimeScaler(tempo_range=(0.8, 1.25))
     return out
 
 
@@ -97,12 +107,15 @@ def anonymize_modes(device, res):
     spec = importlib.util.spec_from_file_location("anonymize", os.path.join(ROOT, "anonymize.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    for (family, more), (name, argv) in itertools.product(FAMILIES.items(), MODES.items()):
+    runs = [(family, name, COMMON + more + argv)
+            for (family, more), (name, argv) in itertools.product(FAMILIES.items(), MODES.items())]
+    runs += [("anonymize", name, TEMPO_COMMON + argv) for name, argv in TEMPO_MODES.items()]
+    for family, name, argv in runs:
         with tempfile.TemporaryDirectory() as out:
             text = io.StringIO()
             with contextlib.redirect_stdout(text):
                 mod.main([os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", device, "--out_dir",
-                          out] + COMMON + more + argv)
+                          out] + argv)
             line = json.loads(text.getvalue().strip().splitlines()[-1])
             line["out_dir"] = name
             res[f"{family}/{name}/json"] = hashlib.sha256(json.dumps(line).encode()).hexdigest()
@@ -119,6 +132,9 @@ def main(argv):
         tr = make()
         for k, (wavs, lens) in enumerate(batches):
             out = tr(wavs.to(device).contiguous(), lens)
+            if isinstance(out, tuple):                       # (a transform that changes the duration: its lengths too)
+                out, lens_out = out
+                res[f"{tn}/{name}/{k}/lens_out"] = sha(lens_out)
             res[f"{tn}/{name}/{k}/out"] = sha(out)
             for j, t in enumerate(getattr(tr, "last", None) or ()):
                 res[f"{tn}/{name}/{k}/last{j}"] = sha(t)

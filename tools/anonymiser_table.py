@@ -24,6 +24,9 @@ moved, all three together (formant_shift) and one by one (f1_shift, f2_shift, f3
                           a pulse/noise excitation, at the utterance's own pitch and with --resynth_pitch_hz 170
   modspec_10              modulation-spectrum smoothing (--modspec_cutoff_hz 10): every STFT bin's log
                           magnitude low-pass filtered along time at 10 Hz, the input's phases kept
+  tempo_0.8, tempo_1.25   WSOLA time-scale modification (--tempo X): the F0 columns only -- the mode
+                          refuses the reports that compare input and output frame against frame, and their columns
+                          are null
 
 The synthetic utterances are steady harmonic series in white noise: the table shows that the scorer and the modes
 run end to end and how they rank on that material.  It says nothing about real speech; the formant columns in
@@ -54,7 +57,10 @@ MODES = (("passthrough", ["--passthrough", "true"]),
          ("formant_norm_psola", ["--formant_norm", "true", "--pitch_norm", "true", "--psola", "true"]),
          ("resynth", ["--resynth", "true"]),
          ("resynth_170", ["--resynth", "true", "--resynth_pitch_hz", "170"]),
-         ("modspec_10", ["--modspec_cutoff_hz", "10"]))
+         ("modspec_10", ["--modspec_cutoff_hz", "10"]),
+         ("tempo_0.8", ["--tempo", "0.8"]),
+         ("tempo_1.25", ["--tempo", "1.25"]))
+ALIGNED = ["--report_stoi", "true", "--report_mcd", "true", "--report_formants", "true"]   # what a tempo row leaves out
 
 
 def _mean(vals):
@@ -76,21 +82,22 @@ def main():
             r = subprocess.run([sys.executable, os.path.join(ROOT, "anonymize.py"),
                                 os.path.join(ROOT, "speechbrain_configs", "convae.yaml"), "--device", a.device,
                                 "--synthetic", str(a.synthetic), "--batch_size", str(a.batch_size), "--out_dir",
-                                os.path.join(tmp, name), "--report_stoi", "true", "--report_f0", "true",
-                                "--report_mcd", "true", "--report_formants", "true"] + flags,
+                                os.path.join(tmp, name), "--report_f0", "true"] +
+                               ([] if name.startswith("tempo_") else ALIGNED) + flags,
                                cwd=ROOT, capture_output=True, text=True, timeout=a.timeout)
             if r.returncode != 0:
                 raise SystemExit(f"{name}: anonymize.py ended with {r.returncode}\n{r.stdout[-1000:]}{r.stderr[-2000:]}")
             res = json.loads(r.stdout.strip().splitlines()[-1])
             utts = res["utterances"]
-            table[name] = {"stoi": res["stoi_mean"], "estoi": res["estoi_mean"],
-                           "scored": sum(1 for u in utts if u["stoi_segments"] > 0), "utterances": len(utts),
+            table[name] = {"stoi": res.get("stoi_mean"), "estoi": res.get("estoi_mean"),
+                           "scored": sum(1 for u in utts if u.get("stoi_segments", 0) > 0), "utterances": len(utts),
                            "f0_mean_hz": _mean([u["f0_mean_hz"] for u in utts if u["voiced_share"] > 0]),
                            "voiced_share": _mean([u["voiced_share"] for u in utts]),
-                           "mcd": res["mcd_mean"], "mcd_sync": res["mcd_sync_mean"], "mcd_scored": res["mcd_scored"],
-                           "formant_shift": res["formant_shift_mean"], "f1_shift": res["f1_shift_mean"],
-                           "f2_shift": res["f2_shift_mean"], "f3_shift": res["f3_shift_mean"],
-                           "formants_scored": res["formants_scored"]}
+                           "mcd": res.get("mcd_mean"), "mcd_sync": res.get("mcd_sync_mean"),
+                           "mcd_scored": res.get("mcd_scored"),
+                           "formant_shift": res.get("formant_shift_mean"), "f1_shift": res.get("f1_shift_mean"),
+                           "f2_shift": res.get("f2_shift_mean"), "f3_shift": res.get("f3_shift_mean"),
+                           "formants_scored": res.get("formants_scored")}
     line = json.dumps({"synthetic": a.synthetic, "modes": table})
     print(line)
     if a.out:
