@@ -9,25 +9,19 @@
 //   fewer than three kept: short (status 3); otherwise F1..F3 and their bandwidths are the three of lowest f
 // sa_formant_compare: over the frames scored and voiced in both signals, the lower medians of the degraded track and
 // of the per-frame ratios, and the geometric mean of the three ratios; the medians by a bitwise radix select.
-// The LPC and Aberth steps are a second copy of sa_mcadams.hip's at order 18 (that file is left as it is, so that
-// its objects and every digest of the anonymisers stay what they were).
+// The fit and the root finder are sa_lpc_shared.h's at order 18, the select's helpers too.
 // No atomics, every sum in a fixed order: the same bits on every run.
-#include "sa_common.h"
-#include <errno.h>
+#include "sa_lpc_shared.h"
 
 #define FT_W 400
 #define FT_H 160
 #define FT_P 18
 #define FT_NF 3
 #define FT_THREADS 64
-#define FT_ITERS 64
 #define FT_PART 147                      // samples per part of a lag sum: 147 mod 32 = 19 (the LDS banks, below)
 #define FT_MAX_B 65535                   // grid.y
 #define FT_MAX_N (1 << 24)
 #define FT_MAX_T 104858                  // the frames of 2^24 samples
-#define FT_SILENCE 1e-10
-#define FT_TOL2 1e-28                    // (1e-14)^2
-#define FT_REAL 1e-6
 #define FT_FMIN 90.0
 #define FT_FMAX 5500.0
 #define FT_BMAX 700.0
@@ -44,7 +38,7 @@ extern "C" int sa_formant_dim(int which) {
     case 2: return FT_P;
     case 3: return FT_NF;
     case 4: return FT_THREADS;
-    case 5: return FT_ITERS;
+    case 5: return SA_LPC_ITERS;
     case 6: return FT_MAX_T;
     case 7: return FC_THREADS;
     default: return -EINVAL;
@@ -90,46 +84,9 @@ __global__ __launch_bounds__(FT_THREADS) void sa_formant_tracks_kernel(const flo
   if (lane < FT_P) fs[FT_W + lane] = 0.0;
   __syncthreads();
 
-  // (b)
-  {
-    const int k = lane % (FT_P + 1), p = min(lane / (FT_P + 1), 2), j0 = FT_PART * p, j1 = min(FT_W, j0 + FT_PART);
-    double acc = 0.0;
-    for (int j = j0; j < j1; ++j) acc = fma(fs[j], fs[j + k], acc);
-    part[lane] = lane < 3 * (FT_P + 1) ? acc : 0.0;
-  }
-  __syncthreads();
-  double r[FT_P + 1];
-#pragma unroll
-  for (int k = 0; k <= FT_P; ++k) r[k] = (part[k] + part[FT_P + 1 + k]) + part[2 * (FT_P + 1) + k];
-
-  int st = r[0] < FT_SILENCE ? 1 : 0;
-  double a[FT_P + 1];
-  if (st == 0) {                                            // (uniform: every lane holds the same r)
-    // (c)
-    r[0] *= 1.0 + 1e-9;
-    double err = r[0];
-    bool bad = false;
-    a[0] = 1.0;
-#pragma unroll
-    for (int i = 1; i <= FT_P; ++i) a[i] = 0.0;
-#pragma unroll
-    for (int m = 1; m <= FT_P; ++m) {
-      double acc = r[m];
-#pragma unroll
-      for (int i = 1; i < m; ++i) acc = fma(a[i], r[m - i], acc);
-      const double k = -acc / err;
-      bad = bad || !(fabs(k) < 1.0);
-      double prev[FT_P + 1];
-#pragma unroll
-      for (int i = 1; i < m; ++i) prev[i] = a[i];
-#pragma unroll
-      for (int i = 1; i < m; ++i) a[i] = fma(k, prev[m - i], prev[i]);
-      a[m] = k;
-      err *= 1.0 - k * k;
-      bad = bad || !(err > 0.0);
-    }
-    if (bad) st = 2;
-  }
+  // (b), (c)
+  double a[FT_P + 1], unused;
+  int st = sa_lpc_fit<FT_P, FT_W, FT_PART, 0>(fs, part, lane, a, unused);
 
   double fz = 0.0, bz = 0.0;
   bool kept = false;
@@ -137,37 +94,7 @@ __global__ __launch_bounds__(FT_THREADS) void sa_formant_tracks_kernel(const flo
     // (d)
     const bool mine = lane < FT_P;
     double zr, zi;
-    {
-      double s, c;
-      sincospi(((double)lane + 0.25) * (2.0 / FT_P), &s, &c);
-      zr = mine ? 0.9 * c : 2.0 + (double)lane;             // the idle lanes sit far away, apart from each other
-      zi = mine ? 0.9 * s : 0.0;
-    }
-    bool conv = false;
-    for (int it = 0; it < FT_ITERS && !conv; ++it) {
-      double pr = 1.0, pi = 0.0, dr = 0.0, di = 0.0;
-#pragma unroll
-      for (int k = 1; k <= FT_P; ++k) {
-        const double tr = fma(dr, zr, fma(-di, zi, pr)), ti = fma(dr, zi, fma(di, zr, pi));
-        dr = tr, di = ti;
-        const double ur = fma(pr, zr, fma(-pi, zi, a[k])), ui = fma(pr, zi, pi * zr);
-        pr = ur, pi = ui;
-      }
-      const double dm = 1.0 / fma(dr, dr, di * di);
-      const double qr = fma(pr, dr, pi * di) * dm, qi = fma(pi, dr, -pr * di) * dm;      // p / p'
-      double sr = 0.0, si = 0.0;
-#pragma unroll
-      for (int k = 0; k < FT_P; ++k) {
-        const double er = zr - __shfl(zr, k, 64), ei = zi - __shfl(zi, k, 64);
-        const double m = 1.0 / fma(er, er, ei * ei);
-        if (k != lane) sr = fma(er, m, sr), si = fma(-ei, m, si);
-      }
-      const double gr = 1.0 - fma(qr, sr, -qi * si), gi = -fma(qr, si, qi * sr);          // 1 - (p / p') sum
-      const double gm = 1.0 / fma(gr, gr, gi * gi);
-      const double cr = fma(qr, gr, qi * gi) * gm, ci = fma(qi, gr, -qr * gi) * gm;
-      zr -= cr, zi -= ci;
-      conv = !__any(mine && !(fma(cr, cr, ci * ci) < FT_TOL2));
-    }
+    const bool conv = sa_lpc_aberth<FT_P>(a, lane, zr, zi);
     if (!conv) st = 2;
 
     if (st == 0) {
@@ -175,7 +102,7 @@ __global__ __launch_bounds__(FT_THREADS) void sa_formant_tracks_kernel(const flo
       const double mod = sqrt(fma(zr, zr, zi * zi));
       fz = atan2(zi, zr) * FT_HZ_PER_RAD;
       bz = -log(mod) * FT_BW_PER_NEPER;
-      kept = mine && zi > FT_REAL * mod && fz >= FT_FMIN && fz <= FT_FMAX && bz <= FT_BMAX;
+      kept = mine && zi > SA_LPC_REAL * mod && fz >= FT_FMIN && fz <= FT_FMAX && bz <= FT_BMAX;
       if (__popcll(__ballot(kept)) < FT_NF) st = 3;
     }
   }
@@ -210,41 +137,7 @@ extern "C" int sa_formant_tracks(const float* wav, const int* n_valid, int B, in
 }
 
 // ---- comparison ----------------------------------------------------------------------------------------
-// a key whose unsigned order is the order of the fp32 values (any sign; the tracks' own values are positive)
-__device__ static inline unsigned fc_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ static inline float fc_value(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ static inline int fc_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// The FC_SEL counts of every thread added over the workgroup: the wave by butterfly, the 16 waves in order by every
-// thread from LDS.  buf alternates between calls, so that one barrier per call is enough: a thread writes a buffer
-// again only after the barrier of the call in between, which every thread reaches after its reads of that buffer.
-__device__ static inline void fc_block_sum(int (&c)[FC_SEL], int (*cnt)[FC_WAVES][FC_SEL], int buf) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < FC_SEL; ++s) {
-    const int v = fc_wave_sum_i(c[s]);
-    if (lane == 0) cnt[buf][wv][s] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < FC_SEL; ++s) {
-    int v = 0;
-#pragma unroll
-    for (int w = 0; w < FC_WAVES; ++w) v += cnt[buf][w][s];
-    c[s] = v;
-  }
-}
-
+// (the key, its inverse and the workgroup count of the select: sa_lpc_shared.h)
 // grid B, one workgroup of 16 waves per row; thread i takes the frames i, i + 1024, ...  A first pass counts the frames
 // that count; then 32 passes, one per bit of the key from the top, settle that bit of all six medians at once: the
 // frames whose key agrees with the bits settled so far and has a 0 at this one are counted, and the rank sought lies
@@ -268,7 +161,7 @@ __global__ __launch_bounds__(FC_THREADS) void sa_formant_compare_kernel(
   for (int s = 0; s < FC_SEL; ++s) c[s] = 0;
   for (int t = tid; t < F; t += FC_THREADS)
     c[0] += sr[t] == 0 && sd[t] == 0 && pr[t] > 0.0f && pd[t] > 0.0f;
-  fc_block_sum(c, cnt, 0);
+  sa_sel_block_sum(c, cnt, 0);
   const int n = c[0];
   const bool scored = n >= min_common;                      // (uniform)
 
@@ -287,12 +180,12 @@ __global__ __launch_bounds__(FC_THREADS) void sa_formant_compare_kernel(
           for (int k = 0; k < FT_NF; ++k) {
             const float d = Fd[(size_t)t * FT_NF + k], g = Fr[(size_t)t * FT_NF + k];
             const float q = (float)((double)d / (double)g);
-            c[k] += (fc_key(d) & mask) == prefix[k];
-            c[FT_NF + k] += (fc_key(q) & mask) == prefix[FT_NF + k];
+            c[k] += (sa_sel_key(d) & mask) == prefix[k];
+            c[FT_NF + k] += (sa_sel_key(q) & mask) == prefix[FT_NF + k];
           }
         }
       }
-      fc_block_sum(c, cnt, bit & 1);                        // (31 -> 1 after the count's 0, then alternating)
+      sa_sel_block_sum(c, cnt, bit & 1);                        // (31 -> 1 after the count's 0, then alternating)
 #pragma unroll
       for (int s = 0; s < FC_SEL; ++s)
         if (want[s] >= c[s]) want[s] -= c[s], prefix[s] |= one;
@@ -303,8 +196,8 @@ __global__ __launch_bounds__(FC_THREADS) void sa_formant_compare_kernel(
   double lg = 0.0;
 #pragma unroll
   for (int k = 0; k < FT_NF; ++k) {
-    m[k] = scored ? fc_value(prefix[k]) : 0.0f;
-    q[k] = scored ? fc_value(prefix[FT_NF + k]) : 0.0f;
+    m[k] = scored ? sa_sel_value(prefix[k]) : 0.0f;
+    q[k] = scored ? sa_sel_value(prefix[FT_NF + k]) : 0.0f;
     lg += log((double)q[k]);
   }
 #pragma unroll

@@ -5,28 +5,19 @@
 // the same pass moves the pitch.
 //   sa_srcfilt_pulses   f0, rho_q -> where every pulse goes (pos_q, int64 in units of 2^-16 samples) and its period
 //   sa_srcfilt_excite   the pulse table -> the excitation: hashed uniform noise plus the linearly interpolated pulses
-//   sa_srcfilt_synth    sa_mcadams's framing, fit, overlap-add and level matching; the frame is the
-//                       all-pole filter 1 / a driven by the windowed excitation, scaled to the frame's prediction error
+//   sa_srcfilt_synth    the framing, fit, overlap-add and level matching of sa_lpc_shared.h (section 17); the frame is
+//                       the all-pole filter 1 / a driven by the windowed excitation, scaled to its prediction error
 // Every decision of the first two is made on integers, or on fp64 formed from the fp32 inputs; the excitation's fp32
 // operations are rounded one by one.  Only the filtered output has a rounding bar.  No root finder, no FIR.
 // Plain HIP C++, no atomics, fixed summation orders: the same bits on every run, and a row alone gives the bits it
 // gives inside a batch.
-#include "sa_common.h"
 #include "sa_lpc_shared.h"
-#include <errno.h>
 #include <limits.h>
 #include <math.h>
 
-#define SF_W 320
-#define SF_H 160
-#define SF_P 20
-#define SF_THREADS 64
-#define SF_CHUNK 4096                    // samples per block of the level sums
-#define SF_SUM_THREADS 256
-#define SF_APPLY 1024                    // samples per block of the last pass
-#define SF_MAX_B 65535                   // grid.y
+#define SF_H SA_FR_H
+#define SF_THREADS SA_FR_THREADS
 #define SF_MAX_N (1 << 24)
-#define SF_SILENCE 1e-10
 #define SF_NO_EXC 1e-20
 #define SF_TMIN 40                       // the period's bounds in samples: 400 Hz ..
 #define SF_TMAX 266                      // .. 60 Hz
@@ -39,11 +30,11 @@
 
 extern "C" int sa_srcfilt_dim(int which) {
   switch (which) {
-    case 0: return SF_W;
+    case 0: return SA_FR_W;
     case 1: return SF_H;
-    case 2: return SF_P;
+    case 2: return SA_FR_P;
     case 3: return SF_THREADS;
-    case 4: return SF_CHUNK;
+    case 4: return SA_FR_CHUNK;
     case 5: return SF_TMIN;
     case 6: return SF_TMAX;
     case 7: return SF_KDIV;
@@ -53,13 +44,12 @@ extern "C" int sa_srcfilt_dim(int which) {
   }
 }
 
-static inline bool sf_dims_ok(int B, int N) { return B >= 1 && B <= SF_MAX_B && N >= 1 && N <= SF_MAX_N; }
+static inline bool sf_dims_ok(int B, int N) { return B >= 1 && B <= SA_FR_MAX_B && N >= 1 && N <= SF_MAX_N; }
 static inline bool sf_frames_ok(int N, int T) { return T == N / SF_H + 1 || T == (N + SF_H - 1) / SF_H + 1; }
-static inline int sf_synth_frames(int N) { return (N + SF_H - 1) / SF_H + 1; }
 
 extern "C" long long sa_srcfilt_workspace_bytes(int B, int N) {
   if (!sf_dims_ok(B, N)) return -EINVAL;
-  return 4LL * B * sf_synth_frames(N) * SF_W + 8LL * (2LL * B * sa_div_up(N, SF_CHUNK) + B);
+  return 4LL * B * sa_fr_frames(N) * SA_FR_W + 8LL * (2LL * B * sa_div_up(N, SA_FR_CHUNK) + B);
 }
 
 __device__ static inline int sf_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -221,65 +211,28 @@ extern "C" int sa_srcfilt_excite(const float* f0, const long long* pos_q, const 
 }
 
 // ---- synthesis ---------------------------------------------------------------------------------------
-__device__ static inline double sf_window(int j) { return sqrt(0.5 - 0.5 * cospi((double)j * (1.0 / 160.0))); }
-
-// grid (T, B), one wave; the structure of sa_pole_warp_frame_kernel without its roots and its FIR.  LDS: the windowed
-// frame with 20 zeros on either side (the lag sums' far end reads zeros instead of branching), the windowed
-// excitation, the output.
+// grid (T, B), one wave; sa_fr_roots_kernel's framing, fit, recursion and store (sa_lpc_shared.h) without its roots
+// and its FIR.  LDS: the windowed frame with 20 zeros on either side (the lag sums' far end reads zeros instead of
+// branching), the windowed excitation, the output.
 //   (a) lane j mod 64 windows five samples of the frame and of the excitation
 //   (b) lane (k, part) sums lag k over a third of the frame; the three parts are added in order: sa_mcadams's sums
 //   (c) every lane runs the Levinson recursion on the same values, unrolled in registers
 //   (d) Ee: five squares per lane in order, the wave by butterfly
 //   (e) IIR: the 320-step recursion on g ex, the same in every lane, its history a register ring
-__global__ __launch_bounds__(SF_THREADS) void sa_srcfilt_frame_kernel(const float* __restrict__ wav,
-                                                                      const float* __restrict__ exc,
-                                                                      const int* __restrict__ n_valid, int N, int T,
-                                                                      float* __restrict__ ws,
-                                                                      int* __restrict__ status) {
-  __shared__ double fs[SF_P + SF_W + SF_P];
-  __shared__ double es[SF_W];
-  __shared__ double ys[SF_W];
-  __shared__ double part[SF_THREADS];
+__global__ __launch_bounds__(SA_FR_THREADS) void sa_srcfilt_frame_kernel(const float* __restrict__ wav,
+                                                                         const float* __restrict__ exc,
+                                                                         const int* __restrict__ n_valid, int N, int T,
+                                                                         float* __restrict__ ws,
+                                                                         int* __restrict__ status) {
+  __shared__ double fs[SA_FR_P + SA_FR_W + SA_FR_P];
+  __shared__ double es[SA_FR_W];
+  __shared__ double ys[SA_FR_W];
+  __shared__ double part[SA_FR_THREADS];
   const int lane = threadIdx.x, t = blockIdx.x, b = blockIdx.y;
-  const int nv = sf_clamp(n_valid[b], 0, N);
-  float* F = ws + ((size_t)b * T + t) * SF_W;
-
-  // (a)
-  double wv[5], ee = 0.0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const int j = lane + 64 * i, n = SF_H * t - SF_H + j;
-    const bool in = n >= 0 && n < nv;
-    const double x = in ? (double)wav[(size_t)b * N + n] : 0.0;
-    const double e = in ? (double)exc[(size_t)b * N + n] : 0.0;
-    wv[i] = sf_window(j);
-    fs[SF_P + j] = wv[i] * x;
-    const double we = wv[i] * e;
-    es[j] = we;
-    ee = fma(we, we, ee);
-  }
-  if (lane < SF_P) fs[lane] = 0.0, fs[SF_P + SF_W + lane] = 0.0;
-  __syncthreads();
-
-  // (b)
-  {
-    const int k = lane % (SF_P + 1), p = min(lane / (SF_P + 1), 2), j0 = 107 * p, j1 = min(SF_W, j0 + 107);
-    double acc = 0.0;
-    for (int j = j0; j < j1; ++j) acc = fma(fs[SF_P + j], fs[SF_P + j + k], acc);
-    part[lane] = lane < 3 * (SF_P + 1) ? acc : 0.0;
-  }
-  __syncthreads();
-  double r[SF_P + 1];
-#pragma unroll
-  for (int k = 0; k <= SF_P; ++k) r[k] = (part[k] + part[SF_P + 1 + k]) + part[2 * (SF_P + 1) + k];
-
-  int st = r[0] < SF_SILENCE ? 1 : 0;
-  double a[SF_P + 1], err = 0.0;
-  if (st == 0) {                                            // (uniform: every lane holds the same r)
-    // (c)
-    r[0] *= 1.0 + 1e-9;
-    sa_lpc_levinson_err<SF_P>(r, a, st, err);
-  }
+  double wv[5], a[SA_FR_P + 1], ee = 0.0, err = 0.0;
+  // (a), (b), (c)
+  sa_fr_load<true>(wav, exc, b, t, N, sa_fr_valid(n_valid, b, N), lane, fs, es, wv, ee);
+  int st = sa_lpc_fit<SA_FR_P, SA_FR_W, SA_FR_PART, SA_FR_P>(fs, part, lane, a, err);
   // (d)
   ee = sa_wave_sum_d(ee);
   if (st == 0 && ee < SF_NO_EXC) st = 3;
@@ -287,115 +240,21 @@ __global__ __launch_bounds__(SF_THREADS) void sa_srcfilt_frame_kernel(const floa
   if (st == 0) {
     // (e)
     const double g = sqrt(err / ee);
-    double h[SF_P];
-#pragma unroll
-    for (int k = 0; k < SF_P; ++k) h[k] = 0.0;
-    for (int jb = 0; jb < SF_W; jb += SF_P) {
-#pragma unroll
-      for (int u = 0; u < SF_P; ++u) {                      // h[(j - k) mod 20] is sample j - k
-        double s = g * es[jb + u];
-#pragma unroll
-        for (int k = 1; k <= SF_P; ++k) s = fma(-a[k], h[(u - k + SF_P) % SF_P], s);
-        h[u] = s;
-        ys[jb + u] = s;
-      }
-    }
+    sa_fr_allpole(a, [&](int j) { return g * es[j]; }, ys);
   }
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const int j = lane + 64 * i;
-    const double rec = st == 0 ? ys[j] : (st == 3 ? 0.0 : fs[SF_P + j]);
-    F[j] = (float)(rec * wv[i]);
-  }
+  sa_fr_store(ws + ((size_t)b * T + t) * SA_FR_W, lane, st, ys, fs, wv);
   if (status && lane == 0) status[(size_t)b * T + t] = st;
 }
 
-__device__ static inline float sf_y(const float* __restrict__ Fr, int n) {
-  const int t0 = n / SF_H, o = n - SF_H * t0;
-  return Fr[(size_t)t0 * SF_W + o + SF_H] + Fr[(size_t)(t0 + 1) * SF_W + o];
-}
-
-// grid (blocks of 4096 samples, B): sums[b][blk] = (sum x^2, sum y^2) over the block's samples below n_valid, each
-// thread its 16 samples in order, the wave by butterfly, the four waves in order (sa_mcadams's pass)
-__global__ __launch_bounds__(SF_SUM_THREADS) void sa_srcfilt_sums_kernel(const float* __restrict__ wav,
-                                                                         const int* __restrict__ n_valid, int N, int T,
-                                                                         const float* __restrict__ ws,
-                                                                         double* __restrict__ sums) {
-  __shared__ double sh[2 * (SF_SUM_THREADS / 64)];
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const int nv = sf_clamp(n_valid[b], 0, N);
-  const float* Fr = ws + (size_t)b * T * SF_W;
-  double sx = 0.0, sy = 0.0;
-  for (int i = 0; i < SF_CHUNK / SF_SUM_THREADS; ++i) {
-    const int n = blockIdx.x * SF_CHUNK + i * SF_SUM_THREADS + tid;
-    if (n < nv) {
-      const double x = (double)wav[(size_t)b * N + n], y = (double)sf_y(Fr, n);
-      sx = fma(x, x, sx), sy = fma(y, y, sy);
-    }
-  }
-  sx = sa_wave_sum_d(sx), sy = sa_wave_sum_d(sy);
-  if ((tid & 63) == 0) sh[2 * (tid >> 6)] = sx, sh[2 * (tid >> 6) + 1] = sy;
-  __syncthreads();
-  if (tid == 0) {
-    double* o = sums + 2 * ((size_t)b * gridDim.x + blockIdx.x);
-    o[0] = ((sh[0] + sh[2]) + sh[4]) + sh[6];
-    o[1] = ((sh[1] + sh[3]) + sh[5]) + sh[7];
-  }
-}
-
-// grid B, one wave: lane l adds the blocks l, l + 64, ... in order, the wave by butterfly;
-// g = sqrt(sum x^2 / sum y^2), 1 when either is 0 or when level is off
-__global__ __launch_bounds__(64) void sa_srcfilt_gain_kernel(const double* __restrict__ sums, int nblk, int level,
-                                                             double* __restrict__ g, float* __restrict__ gain) {
-  const int lane = threadIdx.x, b = blockIdx.x;
-  double v = 1.0;
-  if (level) {
-    double sx = 0.0, sy = 0.0;
-    for (int i = lane; i < nblk; i += 64) {
-      sx += sums[2 * ((size_t)b * nblk + i)];
-      sy += sums[2 * ((size_t)b * nblk + i) + 1];
-    }
-    sx = sa_wave_sum_d(sx), sy = sa_wave_sum_d(sy);
-    if (sx > 0.0 && sy > 0.0) v = sqrt(sx / sy);
-  }
-  if (lane == 0) {
-    g[b] = v;
-    if (gain) gain[b] = (float)v;
-  }
-}
-
-// grid (blocks of 1024 samples, B): out = fp32(g y) below n_valid, 0 from there on
-__global__ __launch_bounds__(256) void sa_srcfilt_apply_kernel(const int* __restrict__ n_valid, int N, int T,
-                                                               const float* __restrict__ ws,
-                                                               const double* __restrict__ g,
-                                                               float* __restrict__ out) {
-  const int b = blockIdx.y;
-  const int nv = sf_clamp(n_valid[b], 0, N);
-  const float* Fr = ws + (size_t)b * T * SF_W;
-  const double gb = g[b];
-#pragma unroll
-  for (int i = 0; i < SF_APPLY / 256; ++i) {
-    const int n = blockIdx.x * SF_APPLY + i * 256 + threadIdx.x;
-    if (n < N) out[(size_t)b * N + n] = n < nv ? (float)(gb * (double)sf_y(Fr, n)) : 0.0f;
-  }
-}
+struct SaNoCopy {                                           // every row is synthesised: no parameter is read
+  static constexpr bool COPIES = false;
+};
 
 extern "C" int sa_srcfilt_synth(const float* wav, const float* exc, const int* n_valid, int B, int N, int level,
                                 float* out, void* ws, int* status, float* gain, void* stream) {
   if (!wav || !exc || !n_valid || !out || !ws || !sf_dims_ok(B, N)) return -EINVAL;
-  const int T = sf_synth_frames(N);
-  const int nblk = sa_div_up(N, SF_CHUNK);
-  float* F = (float*)ws;
-  double* sums = (double*)(F + (size_t)B * T * SF_W);       // 1280 bytes per frame: 8-byte aligned
-  double* g = sums + 2 * (size_t)B * nblk;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sa_srcfilt_frame_kernel, dim3(T, B), dim3(SF_THREADS), 0, s, wav, exc, n_valid, N, T, F, status);
-  if (level)
-    hipLaunchKernelGGL(sa_srcfilt_sums_kernel, dim3(nblk, B), dim3(SF_SUM_THREADS), 0, s, wav, n_valid, N, T,
-                       (const float*)F, sums);
-  hipLaunchKernelGGL(sa_srcfilt_gain_kernel, dim3(B), dim3(64), 0, s, (const double*)sums, nblk, level, g, gain);
-  hipLaunchKernelGGL(sa_srcfilt_apply_kernel, dim3(sa_div_up(N, SF_APPLY), B), dim3(256), 0, s, n_valid, N, T,
-                     (const float*)F, (const double*)g, out);
-  return -(int)hipGetLastError();
+  hipLaunchKernelGGL(sa_srcfilt_frame_kernel, dim3(sa_fr_frames(N), B), dim3(SA_FR_THREADS), 0, (hipStream_t)stream,
+                     wav, exc, n_valid, N, sa_fr_frames(N), (float*)ws, status);
+  return sa_fr_level<SaNoCopy>(wav, nullptr, n_valid, B, N, level, out, ws, gain, (hipStream_t)stream);
 }

@@ -1422,26 +1422,37 @@ def mcadams_workspace(B, N, device):
     return torch.empty(words, dtype=torch.float64, device=device)
 
 
+def _fr_bounds(B, N):
+    if B > GL_MAX_B or N > PN_MAX_N or mcadams_frames(N) > GL_MAX_T:
+        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
+
+
+def _fr_call(entry, wav, other, n_valid, level, return_status, *, check, bounds, workspace, what, per_sample=False):
+    """what mcadams, pole_warp and srcfilt_synth share: the [B, N] check of wav (``check``: the family's _aug_in),
+    ``bounds(B, N)``, the second input ``other`` (named ``what``; [B, N] when per_sample, [B] otherwise) and n_valid,
+    the outputs, the workspace and the call of ``entry``"""
+    if check(wav, "wav").dim() != 2 or wav.numel() == 0:
+        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
+    B, N = wav.shape
+    bounds(B, N)
+    check(other, what, shape=(B, N) if per_sample else (B,))
+    check(n_valid, "n_valid", torch.int32, (B,))
+    out = torch.empty_like(wav)
+    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
+    status = torch.empty(B, mcadams_frames(N), dtype=torch.int32, device=wav.device) if return_status else None
+    ws = workspace(B, N, wav.device)
+    L.check(getattr(L.load(), entry)(_f(wav), _f(other), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws),
+                                     _f(status), _f(gain), L.stream()), entry)
+    return (out, gain, status) if return_status else (out, gain)
+
+
 def mcadams(wav, alpha, n_valid, level=True, return_status=False):
     """wav fp32 [B, N], alpha fp32 [B], n_valid int32 [B] -> (out fp32 [B, N], gain fp32 [B]): every frame's LPC poles
     moved from angle phi to phi^alpha_b and the frame re-synthesised from its own residual; ``level``: the RMS over
     the samples below n_valid_b brought back to the input's (sa_mcadams).  return_status: also int32 [B, T], 0 a frame
     that was transformed, 1 a silent one, 2 one kept as it was (tests, reports)."""
-    if _mc_in(wav, "wav").dim() != 2 or wav.numel() == 0:
-        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
-    B, N = wav.shape
-    T = mcadams_frames(N)
-    if B > GL_MAX_B or N > PN_MAX_N or T > GL_MAX_T:
-        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
-    _mc_in(alpha, "alpha", shape=(B,))
-    _mc_in(n_valid, "n_valid", torch.int32, (B,))
-    out = torch.empty_like(wav)
-    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
-    status = torch.empty(B, T, dtype=torch.int32, device=wav.device) if return_status else None
-    ws = mcadams_workspace(B, N, wav.device)
-    L.check(L.load().sa_mcadams(_f(wav), _f(alpha), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws), _f(status),
-                                _f(gain), L.stream()), "sa_mcadams")
-    return (out, gain, status) if return_status else (out, gain)
+    return _fr_call("sa_mcadams", wav, alpha, n_valid, level, return_status, check=_mc_in, bounds=_fr_bounds,
+                    workspace=mcadams_workspace, what="alpha")
 
 
 # ---- STOI / ESTOI intelligibility scoring (csrc/sa_stoi.hip) ----
@@ -1843,21 +1854,8 @@ def pole_warp(wav, q, n_valid, level=True, return_status=False):
     (0, pi) maps onto itself) and the frame re-synthesised from its own residual, in sa_mcadams's framing; ``level``:
     the RMS over the samples below n_valid_b brought back to the input's (sa_pole_warp).  return_status: also int32
     [B, T], 0 a frame that was transformed, 1 a silent one, 2 one kept as it was."""
-    if _fn_in(wav, "wav").dim() != 2 or wav.numel() == 0:
-        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
-    B, N = wav.shape
-    T = mcadams_frames(N)
-    if B > GL_MAX_B or N > PN_MAX_N or T > GL_MAX_T:
-        raise L.SaHipError(f"wav: [B, N] = [{B}, {N}] -- B up to {GL_MAX_B} (a grid extent), N up to {PN_MAX_N}")
-    _fn_in(q, "q", shape=(B,))
-    _fn_in(n_valid, "n_valid", torch.int32, (B,))
-    out = torch.empty_like(wav)
-    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
-    status = torch.empty(B, T, dtype=torch.int32, device=wav.device) if return_status else None
-    ws = pole_warp_workspace(B, N, wav.device)
-    L.check(L.load().sa_pole_warp(_f(wav), _f(q), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws), _f(status),
-                                  _f(gain), L.stream()), "sa_pole_warp")
-    return (out, gain, status) if return_status else (out, gain)
+    return _fr_call("sa_pole_warp", wav, q, n_valid, level, return_status, check=_fn_in, bounds=_fr_bounds,
+                    workspace=pole_warp_workspace, what="q")
 
 
 def formant_centre(freq, status, f0, frames, target_hz, q_min=0.8, q_max=1.2, min_frames=8):
@@ -1980,19 +1978,9 @@ def srcfilt_synth(wav, exc, n_valid, level=True, return_status=False):
     frame keeps its prediction-error energy; ``level``: the RMS over the samples below n_valid_b brought back to the
     input's (sa_srcfilt_synth).  return_status: also int32 [B, T'], 0 a frame that was resynthesised, 1 a silent one,
     2 one kept as it was (the fit failed), 3 one without excitation (written as zeros)."""
-    if _sf_in(wav, "wav").dim() != 2 or wav.numel() == 0:
-        raise L.SaHipError(f"wav: expected [B, N] with B, N >= 1, got {tuple(wav.shape)}")
-    B, N = wav.shape
-    _sf_dims("srcfilt_synth", B, N)
-    _sf_in(exc, "exc", shape=(B, N))
-    _sf_in(n_valid, "n_valid", torch.int32, (B,))
-    out = torch.empty_like(wav)
-    gain = torch.empty(B, dtype=torch.float32, device=wav.device)
-    status = torch.empty(B, mcadams_frames(N), dtype=torch.int32, device=wav.device) if return_status else None
-    ws = srcfilt_workspace(B, N, wav.device)
-    L.check(L.load().sa_srcfilt_synth(_f(wav), _f(exc), _f(n_valid), B, N, int(bool(level)), _f(out), _f(ws),
-                                      _f(status), _f(gain), L.stream()), "sa_srcfilt_synth")
-    return (out, gain, status) if return_status else (out, gain)
+    return _fr_call("sa_srcfilt_synth", wav, exc, n_valid, level, return_status, check=_sf_in,
+                    bounds=functools.partial(_sf_dims, "srcfilt_synth"), workspace=srcfilt_workspace, what="exc",
+                    per_sample=True)
 
 
 def srcfilt(wav, f0, rho_q, seed, n_valid, aspiration=0.3, level=True, return_status=False):

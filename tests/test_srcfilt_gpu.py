@@ -284,6 +284,28 @@ def test_the_three_in_a_row_equal_the_steps_and_rows_do_not_depend_on_the_batch(
 
 
 @gpu
+def test_the_three_frame_kernels_agree_on_which_frames_are_silent_or_kept():
+    """sa_mcadams, sa_pole_warp and sa_srcfilt_synth frame, sum and fit through one text (csrc/sa_lpc_shared.h): on the
+    width-16037 batch (no multiple of the hop; rows cut at 1.0, 0.73 and 0.5 of it, so there are voiced frames and
+    frames past n_valid), with no alpha or q equal to 1, they mark the same frames silent, a frame whose fit fails in
+    one fails in all, and the two that go on to the roots agree throughout."""
+    from speech_anonymization_amd import data, ops
+    wav = next(iter(data.synthetic_gender_dataset(3, 3, n_samples=16037, seed=7))).sig[0].to(DEV).contiguous()
+    B, N = wav.shape
+    nv = torch.round(torch.tensor([1.0, 0.73, 0.5], dtype=torch.float64) * N).to(torch.int32).to(DEV)
+    f0 = ops.yin_f0(wav)
+    pos_q, period_q, count = ops.srcfilt_pulses(f0, None, nv, N=N)
+    exc = ops.srcfilt_excite(f0, pos_q, period_q, count, _dev([11, 12, 13], torch.int32), nv, N=N)
+    mc = ops.mcadams(wav, _dev([0.8, 0.9, 1.1], torch.float32), nv, return_status=True)[2]
+    pw = ops.pole_warp(wav, _dev([0.9, 1.1, 1.2], torch.float32), nv, return_status=True)[2]
+    sf = ops.srcfilt_synth(wav, exc, nv, return_status=True)[2]
+    assert bool((sf == R.SILENT).any()) and bool((sf == 0).any()) and bool((f0 > 0).any())
+    assert torch.equal(mc == R.SILENT, sf == R.SILENT) and torch.equal(pw == R.SILENT, sf == R.SILENT)
+    assert bool((mc[sf == 2] == 2).all()) and bool((pw[sf == 2] == 2).all())
+    assert torch.equal(mc, pw)
+
+
+@gpu
 def test_entry_points_and_bindings_refuse():
     """only arguments the library rejects before launching: -EINVAL, and the poisoned outputs untouched"""
     from speech_anonymization_amd import _lib, ops
