@@ -13,44 +13,14 @@ cues end at their targets.
 
 One GPU, no --hip_graph.  Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the
 checkpoint layout, the JSON summary as the last line (with the normaliser's settings added)."""
-import json
-import os
 import sys
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import formantnorm, gender, pitchnorm
-from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
+from speech_anonymization_amd import gender
 
 
 def main(argv):
-    hparams_file, run_opts, overrides = parse_arguments(argv)
-    synthetic = overrides.pop("synthetic", None)
-    flags = {k: overrides.pop(k) for k in ("formant_norm",) if k in overrides}      # (the key is the file's block)
-    with open(hparams_file) as fin:
-        settings = load_hyperpyyaml(fin, overrides)
-    if flags.get("formant_norm") is not True and flags:
-        raise SystemExit(f"--formant_norm {flags['formant_norm']}: this recipe normalises the formants; leave the flag "
-                         "out")
-    opts, pitch = formantnorm.check_recipe_options(settings, run_opts)
-    os.makedirs(settings["output_folder"], exist_ok=True)
-    print(gender.augment_notice("gender_classifier_train_formant_norm", settings))
-    hparams = dict(settings, **gender.build(settings))
-    hparams["formant_normalizer"] = formantnorm.FormantNormalizer(**opts)
-    hparams["pitch_normalizer"] = None if pitch is None else pitchnorm.PitchNormalizer(**pitch)
-    run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
-    brain = gender.GenderFormantNormBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,
-                                          run_opts=run_opts, checkpointer=hparams["checkpointer"])
-    counter = hparams["epoch_counter"]
-    train, valid, test = gender.loaders(hparams, synthetic, counter)
-    brain.fit(counter, train, valid)
-    brain.evaluate(test, min_key="error")
-    summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
-               "best_checkpoint": getattr(brain, "best_checkpoint", None), "formant_norm": True}
-    summary.update({k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()})
-    summary["pitch_norm"] = pitch is not None
-    if pitch is not None:
-        summary.update(pitch_target_hz=pitch["target_hz"], psola=True)
-    print(json.dumps(summary))
+    gender.run_recipe("gender_classifier_train_formant_norm", argv)
 
 
 if __name__ == "__main__":

@@ -25,37 +25,14 @@ envelope and the duration and needs no phase; it takes ``--contour_scale`` witho
 
 Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
 summary as the last line (with pitch_target_hz added, and the envelope settings that were given)."""
-import json
-import os
 import sys
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import gender, pitchnorm
-from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
+from speech_anonymization_amd import gender
 
 
 def main(argv):
-    hparams_file, run_opts, overrides = parse_arguments(argv)
-    synthetic = overrides.pop("synthetic", None)
-    with open(hparams_file) as fin:
-        settings = load_hyperpyyaml(fin, overrides)
-    pn = pitchnorm.check_pitch_options(settings, run_opts)
-    os.makedirs(settings["output_folder"], exist_ok=True)
-    print(gender.augment_notice("gender_classifier_train_pitch_norm", settings))
-    hparams = dict(settings, **gender.build(settings))
-    hparams["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pn)
-    run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
-    brain = gender.GenderPitchNormBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,
-                                        run_opts=run_opts, checkpointer=hparams["checkpointer"])
-    counter = hparams["epoch_counter"]
-    train, valid, test = gender.loaders(hparams, synthetic, counter)
-    brain.fit(counter, train, valid)
-    brain.evaluate(test, min_key="error")
-    summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
-               "best_checkpoint": getattr(brain, "best_checkpoint", None), "pitch_target_hz": pn["target_hz"]}
-    summary.update({k: pn[k] for k in ("preserve_formants", "formant_ratio", "lifter", "phase", "contour_scale",
-                                        "contour_smooth", "f0_method", "psola") if k in pn})
-    print(json.dumps(summary))
+    gender.run_recipe("gender_classifier_train_pitch_norm", argv)
 
 
 if __name__ == "__main__":

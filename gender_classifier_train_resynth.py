@@ -16,36 +16,14 @@ are deterministic in the block's seed and the batch count.  One GPU, no --hip_gr
 
 Everything else is gender_classifier_train.py: manifests or ``--synthetic N``, the checkpoint layout, the JSON
 summary as the last line (with the resynthesis settings added)."""
-import json
-import os
 import sys
 
 import speech_anonymization_amd as pkg  # noqa: F401  (registers the package name)
-from speech_anonymization_amd import gender, sourcefilter
-from speech_anonymization_amd.yaml_loader import load_hyperpyyaml, parse_arguments
+from speech_anonymization_amd import gender
 
 
 def main(argv):
-    hparams_file, run_opts, overrides = parse_arguments(argv)
-    synthetic = overrides.pop("synthetic", None)
-    with open(hparams_file) as fin:
-        settings = load_hyperpyyaml(fin, overrides)
-    opts = sourcefilter.check_recipe_options(settings, run_opts)
-    os.makedirs(settings["output_folder"], exist_ok=True)
-    print(gender.augment_notice("gender_classifier_train_resynth", settings))
-    hparams = dict(settings, **gender.build(settings))
-    hparams["pitch_normalizer"] = sourcefilter.SourceFilter(**opts)   # (the brain's hook for a waveform transform)
-    run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
-    brain = gender.GenderPitchNormBrain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams,
-                                        run_opts=run_opts, checkpointer=hparams["checkpointer"])
-    counter = hparams["epoch_counter"]
-    train, valid, test = gender.loaders(hparams, synthetic, counter)
-    brain.fit(counter, train, valid)
-    brain.evaluate(test, min_key="error")
-    summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
-               "best_checkpoint": getattr(brain, "best_checkpoint", None), "resynth": True}
-    summary.update(opts)
-    print(json.dumps(summary))
+    gender.run_recipe("gender_classifier_train_resynth", argv)
 
 
 if __name__ == "__main__":

@@ -147,9 +147,7 @@ def check_formant_norm_options(settings, block=None):
 def check_recipe_options(settings, run_opts, environ=None):
     """what gender_classifier_train_formant_norm.py refuses before anything touches a GPU, one line each -> (the
     keyword arguments of ``FormantNormalizer``, those of the PSOLA ``PitchNormalizer`` behind it or None)"""
-    import os
     from . import pitchnorm
-    environ = os.environ if environ is None else environ
     block = settings.get("formant_norm") if isinstance(settings.get("formant_norm"), dict) else {}
     opts = check_formant_norm_options(settings, block)
     pitch = None
@@ -159,9 +157,5 @@ def check_recipe_options(settings, run_opts, environ=None):
     if flag:
         target = settings.get("pitch_target_hz", block.get("pitch_target_hz", 170.0))
         pitch = {"target_hz": pitchnorm.check_pitch_target(target), "psola": True, "f0_method": opts["f0_method"]}
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_formant_norm runs on one GPU: data parallelism is not implemented "
-                         "for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_formant_norm does not support --hip_graph")
+    pitchnorm.refuse_run_modes("gender_classifier_train_formant_norm", settings, run_opts, environ)
     return opts, pitch

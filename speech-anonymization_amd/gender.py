@@ -18,17 +18,22 @@ noise rows in place of EnvCorrupt's OpenRIR noise, and TimeDomainSpecAugment, at
 default -- the recipe trains without it.
 
 The second half of the module is the same recipe on RECONSTRUCTED features (the reference's
-gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser), and at its end the
-recipe on PITCH-NORMALISED waveforms (gender_classifier_train_pitch_norm.py; GenderPitchNormBrain)."""
+gender_classifier_train_recon.py; GenderReconBrain and the loading of the frozen anonymiser).  At its end stand
+RECIPES, one row per gender_classifier_train*.py script, and run_recipe, the ``main`` of all of them: the recipes
+on TRANSFORMED waveforms (pitch_norm, mcadams, formant_norm, resynth, modspec, tempo) are GenderBrain with their
+transform in ``hparams.waveform_transforms``."""
+import collections
 import functools
+import json
 import os
 
 import torch
 
-from . import data, features, losses, xvector
+from . import data, features, formantnorm, losses, mcadams, modspec, pitchnorm, sourcefilter, timescale, xvector
 from .brain import Brain, EpochCounter, FileTrainLogger, Stage
 from .checkpoint import Checkpointer
 from .data import SEX
+from .yaml_loader import load_hyperpyyaml, parse_arguments
 
 
 class ReduceLROnPlateau:
@@ -134,7 +139,9 @@ def build(hp):
 
 class GenderBrain(Brain):
     """gender_classifier_train.py:58-216 on the Brain base (fused Adam, clipping at max_grad_norm,
-    the lazy finite check, checkpoint resume)."""
+    the lazy finite check, checkpoint resume).  ``hparams.waveform_transforms`` (absent: none) run on every batch at
+    every stage, train, valid and test alike, before augmentation and features: what the reference's pitch-norm
+    ``audio_pipeline`` does to every waveform it loads, and the hook of every waveform recipe in RECIPES."""
 
     def augment(self, wavs, lens, stage):
         """modules.augmentation (reference :79-86) at Stage.TRAIN: -> the augmented waveforms and their lengths.
@@ -151,11 +158,26 @@ class GenderBrain(Brain):
         # no epoch is passed (reference :104): the global statistics follow every training batch
         return self.modules.mean_var_norm(feats, lens)
 
+    def transform_waveforms(self, wavs, lens, loader_lens):
+        """``hparams.waveform_transforms`` in order, each called as t(wavs, lens) -> wavs (width and lengths kept) or
+        (wavs, lens).  A transform marked ``host_lengths`` is given ``loader_lens``, the lengths as the loader made
+        them, so that it knows its output's width without a device read; once a transform has returned lengths of
+        its own, those are what every later step sees and ``_host_lens`` is None."""
+        for t in getattr(self.hparams, "waveform_transforms", None) or ():
+            out = t(wavs, loader_lens if loader_lens is not None and getattr(t, "host_lengths", False) else lens)
+            if isinstance(out, tuple):
+                wavs, lens = out
+                loader_lens = self._host_lens = None
+            else:
+                wavs = out
+        return wavs, lens
+
     def compute_forward(self, batch, stage):
         # the loader's CPU lengths: the augmentation draws its chunk positions from them without a device read
-        self._host_lens = None if batch.sig[1].is_cuda else batch.sig[1]
+        loader_lens = batch.sig[1]
+        self._host_lens = None if loader_lens.is_cuda else loader_lens
         batch = batch.to(self.device)
-        wavs, lens = batch.sig
+        wavs, lens = self.transform_waveforms(*batch.sig, loader_lens)
         feats = self.prepare_features(wavs, lens, stage)
         if self.__dict__.get("_aug"):
             lens = self._aug[0]
@@ -266,7 +288,6 @@ RECON_NORMALIZERS = ("own", "checkpoint")
 
 def check_recon_options(settings, run_opts, environ=None):
     """what gender_classifier_train_recon.py refuses before anything touches a GPU, one line each"""
-    environ = os.environ if environ is None else environ
     mt = settings.get("model_type")
     if mt not in RECON_MODEL_TYPES:
         raise SystemExit(f"unknown model_type {mt!r}: the anonymiser is one of convae, fcae and endtoend")
@@ -275,10 +296,7 @@ def check_recon_options(settings, run_opts, environ=None):
                          "(model.ckpt, normalizer.ckpt)")
     if settings.get("recon_normalizer", "own") not in RECON_NORMALIZERS:
         raise SystemExit(f"unknown recon_normalizer {settings.get('recon_normalizer')!r}: own or checkpoint")
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_recon runs on one GPU: data parallelism is not implemented for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_recon does not support --hip_graph")
+    pitchnorm.refuse_run_modes("gender_classifier_train_recon", settings, run_opts, environ)
 
 
 def build_anonymiser(model_type, precision="bf16x3", external_classifier=None, batch_size=None):
@@ -367,44 +385,109 @@ class GenderReconBrain(GenderBrain):
 
 
 # ---------------------------------------------------------------------------------------------------
-# the same recipe on pitch-normalised waveforms (the reference's gender_classifier_train_pitch_norm.py)
+# the eight recipes: one row each, one driver
 # ---------------------------------------------------------------------------------------------------
-class GenderPitchNormBrain(GenderBrain):
-    """gender_classifier_train_pitch_norm.py: the reference's ``audio_pipeline`` pitch-normalises every waveform
-    it loads, for train, valid and test alike, so ``hparams.pitch_normalizer`` (pitchnorm.PitchNormalizer; DESIGN
-    section 15) runs at every stage, before augmentation and features.  Shapes and lengths are kept, so the rest
-    of the recipe is GenderBrain's."""
-
-    def prepare_features(self, wavs, lens, stage):
-        return super().prepare_features(self.hparams.pitch_normalizer(wavs, lens), lens, stage)
+def formant_transforms(checked):
+    opts, pitch = checked
+    return [formantnorm.FormantNormalizer(**opts)] + ([] if pitch is None else [pitchnorm.PitchNormalizer(**pitch)])
 
 
-class GenderFormantNormBrain(GenderBrain):
-    """gender_classifier_train_formant_norm.py: ``hparams.formant_normalizer`` (formantnorm.FormantNormalizer; DESIGN
-    section 26) brings every waveform's formants to the target at every stage, train, valid and test alike, before
-    augmentation and features; with ``hparams.pitch_normalizer`` (a PitchNormalizer with psola=True, or None) the
-    pitch of the result is normalised too.  Shapes and lengths are kept, so the rest of the recipe is GenderBrain's."""
-
-    def prepare_features(self, wavs, lens, stage):
-        wavs = self.hparams.formant_normalizer(wavs, lens)
-        pn = getattr(self.hparams, "pitch_normalizer", None)
-        if pn is not None:
-            wavs = pn(wavs, lens)
-        return super().prepare_features(wavs, lens, stage)
+def formant_summary(settings, checked):
+    opts, pitch = checked
+    extra = dict({"formant_norm": True}, **_listed(opts), pitch_norm=pitch is not None)
+    if pitch is not None:
+        extra.update(pitch_target_hz=pitch["target_hz"], psola=True)
+    return extra
 
 
-class GenderTempoBrain(GenderBrain):
-    """gender_classifier_train_tempo.py: ``hparams.time_scaler`` (timescale.TimeScaler) plays every
-    waveform at another tempo at every stage, train, valid and test alike, before augmentation and features.  The
-    batch's width and its relative lengths change, so the scaler's own lengths go on to the normaliser and the
-    pooling.  It is given the loader's CPU lengths: the output's width is then known without a device read."""
+def recon_setup(settings):
+    """loads the frozen anonymiser before build() seeds and makes the classifier, as the script always has -> what
+    puts it, and the checkpoint's normaliser where that is asked for, into the built hparams"""
+    ext = None
+    if settings["model_type"] == "endtoend" and settings.get("external_classifier_ckpt"):
+        ext = load_external_classifier(settings["external_classifier_ckpt"])
+    model = load_anonymiser(build_anonymiser(settings["model_type"], settings.get("precision", "bf16x3"), ext,
+                                             int(settings["batch_size"])), settings["recon_ckpt"])
 
-    def compute_forward(self, batch, stage):
-        host_lens = batch.sig[1]
-        batch = batch.to(self.device)
-        wavs, lens = self.hparams.time_scaler(batch.sig[0], host_lens)
-        self._host_lens = None                               # (the lengths changed: the augmentation reads the device's)
-        feats = self.prepare_features(wavs, lens, stage)
-        if self.__dict__.get("_aug"):
-            lens = self._aug[0]
-        return xvector.train_log_probs(self.modules.embedding_model, self.modules.classifier, feats, lens)
+    def finish(hparams):
+        if settings.get("recon_normalizer", "own") == "checkpoint":
+            hparams["recon_norm"] = load_recon_normalizer(settings["recon_ckpt"])
+        hparams["modules"]["model"] = model                # frozen: not a recoverable, not in the optimiser
+    return finish
+
+
+def _listed(opts):
+    return {k: (list(v) if isinstance(v, tuple) else v) for k, v in opts.items()}
+
+
+PITCH_SUMMARY_KEYS = ("preserve_formants", "formant_ratio", "lifter", "phase", "contour_scale", "contour_smooth",
+                      "f0_method", "psola")
+# check(settings, run_opts[, environ]) -> checked: the script's refusals; transforms(checked) -> the list for
+# hparams.waveform_transforms; summary(settings, checked) -> what the script adds to the JSON summary, in order;
+# setup(settings): see recon_setup; own_flag: (key, why) of a flag that names the recipe itself and may only say true
+# -- it is taken off the command line before the file is read, where the key is a block
+Recipe = collections.namedtuple("Recipe", "check transforms summary brain setup own_flag",
+                                defaults=(None, None, lambda settings, checked: {}, GenderBrain, None, None))
+RECIPES = {
+    "gender_classifier_train": Recipe(),
+    "gender_classifier_train_recon": Recipe(
+        check_recon_options, brain=GenderReconBrain, setup=recon_setup,
+        summary=lambda st, _: {"recon_ckpt": st["recon_ckpt"], "model_type": st["model_type"]}),
+    "gender_classifier_train_pitch_norm": Recipe(
+        pitchnorm.check_pitch_options, lambda pn: [pitchnorm.PitchNormalizer(**pn)],
+        lambda st, pn: dict({"pitch_target_hz": pn["target_hz"]}, **{k: pn[k] for k in PITCH_SUMMARY_KEYS if k in pn})),
+    "gender_classifier_train_mcadams": Recipe(
+        mcadams.check_recipe_options, lambda opts: [mcadams.McAdams(**opts)],
+        lambda st, opts: dict({"mcadams": True}, **_listed(opts))),
+    "gender_classifier_train_formant_norm": Recipe(
+        formantnorm.check_recipe_options, formant_transforms, formant_summary,
+        own_flag=("formant_norm", "this recipe normalises the formants; leave the flag out")),
+    "gender_classifier_train_resynth": Recipe(
+        sourcefilter.check_recipe_options, lambda opts: [sourcefilter.SourceFilter(**opts)],
+        lambda st, opts: dict({"resynth": True}, **opts)),
+    "gender_classifier_train_modspec": Recipe(
+        modspec.check_recipe_options, lambda opts: [modspec.ModulationSmoother(**opts)],
+        lambda st, opts: dict({"modspec": True}, **opts)),
+    "gender_classifier_train_tempo": Recipe(
+        timescale.check_recipe_options, lambda opts: [timescale.TimeScaler(**opts)],
+        lambda st, opts: dict({"tempo_mode": True}, **_listed(opts))),
+}
+
+
+def recipe_brain(row, settings, run_opts, checked, checkpointer=True):
+    """the brain of a RECIPES row on loaded ``settings`` and what its checker returned -> (brain, its hparams)"""
+    finish = row.setup(settings) if row.setup else None
+    hparams = dict(settings, **build(settings))
+    if row.transforms:
+        hparams["waveform_transforms"] = row.transforms(checked)
+    if finish:
+        finish(hparams)
+    brain = row.brain(modules=hparams["modules"], opt_class=hparams["opt_class"], hparams=hparams, run_opts=run_opts,
+                      checkpointer=hparams["checkpointer"] if checkpointer else None)
+    return brain, hparams
+
+
+def run_recipe(name, argv):
+    """``main(argv)`` of the script ``name``: parse, load the YAML, refuse, say what the augmentation does, build,
+    train, evaluate the best checkpoint, and print the JSON summary as the last line"""
+    row = RECIPES[name]
+    hparams_file, run_opts, overrides = parse_arguments(argv)
+    synthetic = overrides.pop("synthetic", None)
+    flag = overrides.pop(row.own_flag[0], True) if row.own_flag else True
+    with open(hparams_file) as fin:
+        settings = load_hyperpyyaml(fin, overrides)
+    if flag is not True:
+        raise SystemExit(f"--{row.own_flag[0]} {flag}: {row.own_flag[1]}")
+    checked = row.check(settings, run_opts) if row.check else None
+    os.makedirs(settings["output_folder"], exist_ok=True)
+    print(augment_notice(name, settings))
+    run_opts.setdefault("max_grad_norm", settings.get("max_grad_norm", 5.0))
+    brain, hparams = recipe_brain(row, settings, run_opts, checked)
+    counter = hparams["epoch_counter"]
+    train, valid, test = loaders(hparams, synthetic, counter)
+    brain.fit(counter, train, valid)
+    brain.evaluate(test, min_key="error")
+    summary = {"test_loss": brain.last_stats["loss"], "test_error": brain.last_stats["error"],
+               "best_checkpoint": getattr(brain, "best_checkpoint", None)}
+    summary.update(row.summary(settings, checked))
+    print(json.dumps(summary))

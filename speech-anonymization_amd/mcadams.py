@@ -6,7 +6,7 @@ alpha < 1).  One library call, sa_mcadams, all on the GPU, no phase reconstructi
 import torch
 
 from . import ops
-from .pitchnorm import gpu_only, n_valid
+from .pitchnorm import gpu_only, n_valid, refuse_run_modes
 
 ALPHA_LOW, ALPHA_HIGH = 0.5, 1.2             # what this layer accepts (the kernel itself takes 0.25..2)
 ALPHA_DEFAULT = 0.8
@@ -111,12 +111,6 @@ def check_mcadams_options(settings, block=None):
 
 def check_recipe_options(settings, run_opts, environ=None):
     """what gender_classifier_train_mcadams.py refuses before anything touches a GPU, one line each"""
-    import os
-    environ = os.environ if environ is None else environ
     opts = check_mcadams_options(settings)
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_mcadams runs on one GPU: data parallelism is not implemented "
-                         "for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_mcadams does not support --hip_graph")
+    refuse_run_modes("gender_classifier_train_mcadams", settings, run_opts, environ)
     return opts

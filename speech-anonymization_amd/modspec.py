@@ -15,7 +15,7 @@ The default cutoff of 10 Hz is a convention and has not been validated on speech
 import torch
 
 from . import ops, vocoder
-from .pitchnorm import gpu_only, n_valid, padded_stft
+from .pitchnorm import gpu_only, n_valid, padded_stft, refuse_run_modes
 
 CUTOFF_DEFAULT, DEPTH_DEFAULT = 10.0, 1.0
 CUTOFF_LOW, CUTOFF_HIGH = ops.MODSPEC_CUTOFF_LOW, ops.MODSPEC_CUTOFF_HIGH
@@ -113,12 +113,6 @@ def check_modspec_options(settings, block=None):
 
 def check_recipe_options(settings, run_opts, environ=None):
     """what gender_classifier_train_modspec.py refuses before anything touches a GPU, one line each"""
-    import os
-    environ = os.environ if environ is None else environ
     opts = check_modspec_options(settings)
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_modspec runs on one GPU: data parallelism is not implemented "
-                         "for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_modspec does not support --hip_graph")
+    refuse_run_modes("gender_classifier_train_modspec", settings, run_opts, environ)
     return opts

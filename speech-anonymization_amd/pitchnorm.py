@@ -375,6 +375,16 @@ def check_option(key, value, options=OPTIONS):
     return value if o.kind != "real" else real
 
 
+def refuse_run_modes(script, settings, run_opts, environ=None):
+    """the two run modes no waveform or recon recipe of the gender classifier has, one line each"""
+    import os
+    environ = os.environ if environ is None else environ
+    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"{script} runs on one GPU: data parallelism is not implemented for it")
+    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
+        raise SystemExit(f"{script} does not support --hip_graph")
+
+
 def check_formant_options(settings, block=None):
     """the envelope settings of a recipe's ``pitch_norm:`` block (if any) under the top-level overrides ->
     a dict of the keys that were given (preserve_formants, formant_ratio, lifter), each refused in one line"""
@@ -441,8 +451,6 @@ def check_pitch_target(value):
 
 def check_pitch_options(settings, run_opts, environ=None):
     """what gender_classifier_train_pitch_norm.py refuses before anything touches a GPU, one line each"""
-    import os
-    environ = os.environ if environ is None else environ
     pn = settings.get("pitch_norm") or {}
     target = check_pitch_target(settings.get("pitch_target_hz", pn.get("target_hz", 170.0)))
     r_min, r_max = float(pn.get("r_min", R_LOW)), float(pn.get("r_max", R_HIGH))
@@ -451,11 +459,7 @@ def check_pitch_options(settings, run_opts, environ=None):
                          "ratios the kernels take")
     if r_min > r_max:
         raise SystemExit(f"pitch_norm: r_min {r_min:g} is above r_max {r_max:g}")
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_pitch_norm runs on one GPU: data parallelism is not implemented "
-                         "for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_pitch_norm does not support --hip_graph")
+    refuse_run_modes("gender_classifier_train_pitch_norm", settings, run_opts, environ)
     return dict(pn, target_hz=target, r_min=r_min, r_max=r_max, **check_formant_options(settings, pn),
                 **check_phase_option(settings, pn), **check_contour_options(settings, pn),
                 **check_f0_option(settings, pn), **check_psola_option(settings, pn))

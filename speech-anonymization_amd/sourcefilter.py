@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .pitchnorm import (R_HIGH, R_LOW, TARGET_HIGH, TARGET_LOW, check_f0_option, check_pitch_target, f0_settings,
-                        f0_track, gpu_only, n_valid)
+                        f0_track, gpu_only, n_valid, refuse_run_modes)
 
 ASPIRATION_DEFAULT = 0.3
 SEED_MAX = 2 ** 31 - 1
@@ -168,12 +168,6 @@ def check_resynth_options(settings, block=None):
 
 def check_recipe_options(settings, run_opts, environ=None):
     """what gender_classifier_train_resynth.py refuses before anything touches a GPU, one line each"""
-    import os
-    environ = os.environ if environ is None else environ
     opts = check_resynth_options(settings)
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_resynth runs on one GPU: data parallelism is not implemented "
-                         "for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_resynth does not support --hip_graph")
+    refuse_run_modes("gender_classifier_train_resynth", settings, run_opts, environ)
     return opts

@@ -11,7 +11,7 @@ the device to the host."""
 import torch
 
 from . import ops
-from .pitchnorm import gpu_only, n_valid
+from .pitchnorm import gpu_only, n_valid, refuse_run_modes
 
 TEMPO_LOW, TEMPO_HIGH = 0.5, 2.0
 TEMPO_DEFAULT = 1.0
@@ -40,6 +40,7 @@ class TimeScaler:
     has n_out_b = ops.wsola_out_len(round(lens_b N), tempo_q_b) samples, Nout is the largest of them, samples from
     n_out_b on are zero and lens_out = n_out / Nout.  ``last``: (tempo_q int32 [B], n_out int32 [B], count int32 [B],
     jumps int64 [B]: the windows that do not continue their predecessor) of the last batch, on the device."""
+    host_lengths = True        # GenderBrain's hook hands it the loader's CPU lengths: Nout then needs no device read
 
     def __init__(self, tempo=TEMPO_DEFAULT, tempo_range=None, seed=1):
         if tempo_range is not None:
@@ -125,11 +126,6 @@ def check_tempo_options(settings, block=None):
 
 def check_recipe_options(settings, run_opts, environ=None):
     """what gender_classifier_train_tempo.py refuses before anything touches a GPU, one line each"""
-    import os
-    environ = os.environ if environ is None else environ
     opts = check_tempo_options(settings)
-    if run_opts.get("distributed_launch") or int(environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("gender_classifier_train_tempo runs on one GPU: data parallelism is not implemented for it")
-    if run_opts.get("hip_graph") or settings.get("hip_graph"):   # (from the command line it arrives as a setting)
-        raise SystemExit("gender_classifier_train_tempo does not support --hip_graph")
+    refuse_run_modes("gender_classifier_train_tempo", settings, run_opts, environ)
     return opts

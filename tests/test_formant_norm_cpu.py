@@ -387,7 +387,7 @@ def test_ops_and_class_refuse_cpu_tensors_before_loading_anything(monkeypatch):
 
 # ---- the recipe ---------------------------------------------------------------------------------------------
 def test_recipe_config_loads_and_refuses():
-    from speech_anonymization_amd import formantnorm, gender
+    from speech_anonymization_amd import formantnorm, gender, pitchnorm
     from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
     path = os.path.join(ROOT, "speechbrain_configs", "gender_classifier_formant_norm.yaml")
     with open(path) as fin:
@@ -421,4 +421,46 @@ def test_recipe_config_loads_and_refuses():
     with pytest.raises(SystemExit, match="--pitch_norm 3: true or false"):
         check(dict(settings, pitch_norm=3), {}, {})
     assert os.path.exists(os.path.join(ROOT, "gender_classifier_train_formant_norm.py"))
-    assert issubclass(gender.GenderFormantNormBrain, gender.GenderBrain)
+    # the recipe's row: GenderBrain with the formant normaliser first and, with --pitch_norm true, the PSOLA pitch
+    # normaliser behind it; what the hook does with the list at every stage is tests/test_gender_recipes_cpu.py's
+    row = gender.RECIPES["gender_classifier_train_formant_norm"]
+    assert row.brain is gender.GenderBrain
+    assert [type(t) for t in row.transforms(row.check(settings, {}, {}))] == [formantnorm.FormantNormalizer]
+    both = row.transforms(row.check(dict(settings, pitch_norm=True), {}, {}))
+    assert [type(t) for t in both] == [formantnorm.FormantNormalizer, pitchnorm.PitchNormalizer] and both[1].psola
+
+
+def test_formant_then_pitch_transform_run_at_every_stage_before_the_features(monkeypatch):
+    """the hook on a list of two, as the recipe with --pitch_norm true passes it: the first sees the raw waveform object
+    at TRAIN, VALID and TEST, the second what the first returned, and the front end what the second returned"""
+    import types
+    from speech_anonymization_amd import gender
+    from speech_anonymization_amd.brain import Batch, Stage
+
+    class Modules(dict):
+        __getattr__ = dict.__getitem__
+
+    seen = []
+
+    def stub(name, add):
+        def call(wavs, lens):
+            seen.append((name, wavs))
+            return wavs + add
+        return call
+
+    def fbank(wavs):
+        seen.append(("fbank", wavs))
+        return wavs[:, :, None]
+
+    monkeypatch.setattr(gender.xvector, "train_log_probs", lambda emb, cl, feats, lens: feats)
+    b = object.__new__(gender.GenderBrain)
+    b.device = torch.device("cpu")
+    b.modules = Modules(compute_features=fbank, mean_var_norm=lambda feats, lens: feats, embedding_model=None,
+                        classifier=None)
+    b.hparams = types.SimpleNamespace(waveform_transforms=[stub("formant", 1.0), stub("pitch", 2.0)])
+    wav, lens = torch.zeros(2, 8), torch.ones(2)
+    for stage in (Stage.TRAIN, Stage.VALID, Stage.TEST):
+        del seen[:]
+        out = b.compute_forward(Batch(wav, lens, torch.zeros(2, dtype=torch.long)), stage)
+        assert [k for k, _ in seen] == ["formant", "pitch", "fbank"] and seen[0][1] is wav
+        assert torch.equal(seen[1][1], wav + 1.0) and torch.equal(seen[2][1], wav + 3.0) and out.shape == (2, 8, 1)

@@ -218,11 +218,11 @@ def test_ops_refuse_cpu_tensors_before_loading_anything(monkeypatch):
         pitchnorm.PitchNormalizer().shift(torch.zeros(1, 500), torch.ones(1), torch.ones(1))
 
 
-def test_pitch_norm_brain_normalises_at_every_stage_before_the_features():
-    """GenderPitchNormBrain.prepare_features: the normaliser sees the raw waveforms at TRAIN, VALID and TEST, and
-    the augmentation and the front end see what it returned"""
-    from speech_anonymization_amd import gender
-    from speech_anonymization_amd.brain import Stage
+def test_pitch_norm_brain_normalises_at_every_stage_before_the_features(monkeypatch):
+    """the pitch_norm recipe's brain (GenderBrain with the normaliser as its one waveform transform): the normaliser
+    sees the raw waveforms at TRAIN, VALID and TEST, and the augmentation and the front end see what it returned"""
+    from speech_anonymization_amd import gender, pitchnorm
+    from speech_anonymization_amd.brain import Batch, Stage
 
     class Modules(dict):
         __getattr__ = dict.__getitem__
@@ -237,15 +237,19 @@ def test_pitch_norm_brain_normalises_at_every_stage_before_the_features():
         seen.append(("fbank", wavs))
         return wavs[:, :, None]
 
-    assert issubclass(gender.GenderPitchNormBrain, gender.GenderBrain)
-    assert "prepare_features" not in vars(gender.GenderBrain) or gender.GenderBrain.prepare_features is not \
-        gender.GenderPitchNormBrain.prepare_features
-    b = object.__new__(gender.GenderPitchNormBrain)
-    b.modules = Modules(compute_features=fbank, mean_var_norm=lambda feats, lens: feats)
-    b.hparams = types.SimpleNamespace(pitch_normalizer=normalizer)
+    row = gender.RECIPES["gender_classifier_train_pitch_norm"]
+    assert row.brain is gender.GenderBrain
+    made = row.transforms(row.check({}, {}, {}))
+    assert len(made) == 1 and isinstance(made[0], pitchnorm.PitchNormalizer)
+    monkeypatch.setattr(gender.xvector, "train_log_probs", lambda emb, cl, feats, lens: feats)
+    b = object.__new__(gender.GenderBrain)
+    b.device = torch.device("cpu")
+    b.modules = Modules(compute_features=fbank, mean_var_norm=lambda feats, lens: feats, embedding_model=None,
+                        classifier=None)
+    b.hparams = types.SimpleNamespace(waveform_transforms=[normalizer])
     wav, lens = torch.zeros(2, 8), torch.ones(2)
     for stage in (Stage.TRAIN, Stage.VALID, Stage.TEST):
         del seen[:]
-        out = b.prepare_features(wav, lens, stage)
+        out = b.compute_forward(Batch(wav, lens, torch.zeros(2, dtype=torch.long)), stage)
         assert [k for k, _ in seen] == ["norm", "fbank"] and seen[0][1] is wav
         assert torch.equal(seen[1][1], wav + 1.0) and out.shape == (2, 8, 1)

@@ -23,7 +23,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
-from tools.bench_common import time_calls  # noqa: E402
+from tools.bench_common import bench_brain, time_calls  # noqa: E402
 
 
 def torch_restatement(wav, lens, plan, noise, snr, first, w, h):
@@ -67,9 +67,8 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import augment, gender, ops
+    from speech_anonymization_amd import augment, ops
     from speech_anonymization_amd.brain import Batch
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
     B, L = a.B, a.L
     g = torch.Generator().manual_seed(0)
     host_lens = 0.6 + 0.4 * torch.rand(B, generator=g)
@@ -107,21 +106,12 @@ def main():
 
     if not a.no_step:
         with tempfile.TemporaryDirectory() as tmp:
-            def brain(on, bs):
-                with open(os.path.join(ROOT, "speechbrain_configs", "gender_classifier.yaml")) as f:
-                    st = load_hyperpyyaml(f, {"output_folder": tmp, "augment": on, "batch_size": bs})
-                hp = dict(st, **gender.build(st))
-                b = gender.GenderBrain(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp,
-                                       run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
-                return b
             label = torch.arange(B) % 2
             batch = Batch(wav_cpu, host_lens, label)
             twice = Batch(torch.cat([wav_cpu, wav_cpu]), host_lens.repeat(2), label.repeat(2))
             for name, on, bt in (("step_off_B32_ms", False, batch), ("step_off_B64_ms", False, twice),
                                  ("step_on_B32_ms", True, batch)):
-                b = brain(on, bt.sig[0].shape[0])
+                b = bench_brain("gender_classifier_train", bt.sig[0].shape[0], tmp, {"augment": on})
                 out[name.replace("32", str(B)).replace("64", str(2 * B))] = round(
                     time_calls(lambda: b.fit_batch(bt), a.warmup, a.steps), 4)
                 del b

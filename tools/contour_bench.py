@@ -20,7 +20,7 @@ is that other figure).  Prints one JSON line (and writes it to --out):
   resample_map_ms, torch_resample_map_ms  sa_pitch_resample_map / a [B, N, 66] gather in fp64, in row chunks;
                                         resample_ms: the constant-ratio sibling
   normalizer_vocoder_ms, normalizer_contour_ms, normalizer_contour_formants_ms   the whole call
-  step_vocoder_ms, step_contour_ms      GenderPitchNormBrain.fit_batch on the same batch"""
+  step_vocoder_ms, step_contour_ms      the pitch_norm recipe's fit_batch on the same batch"""
 import argparse
 import math
 import os
@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-from tools.bench_common import write_line  # noqa: E402
+from tools.bench_common import bench_brain, write_line  # noqa: E402
 
 SR, HOP, NBIN = 16000, 160, 201
 SHORT_REPS = 32                           # calls per sample of the entry points that take tens of microseconds
@@ -172,8 +172,7 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, gender, ops, pitchnorm, vocoder
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, ops, pitchnorm, vocoder
     B, N = a.B, int(a.seconds * SR)
     batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
     wav_cpu, lens_cpu = batch.sig
@@ -235,14 +234,7 @@ def main():
     if not a.no_step:
         with tempfile.TemporaryDirectory() as tmp:
             for name, over in (("vocoder", {}), ("contour", {"contour_scale": gamma})):
-                with open(os.path.join(ROOT, "speechbrain_configs", "gender_classifier_pitch_norm.yaml")) as f:
-                    st = load_hyperpyyaml(f, dict({"output_folder": tmp, "batch_size": B, "phase": "vocoder"}, **over))
-                hp = dict(st, **gender.build(st))
-                hp["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pitchnorm.check_pitch_options(st, {}, {}))
-                b = gender.GenderPitchNormBrain(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp,
-                                                run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
+                b = bench_brain("gender_classifier_train_pitch_norm", B, tmp, dict({"phase": "vocoder"}, **over))
                 out[f"step_{name}_ms"] = tm(lambda: b.fit_batch(batch))
                 del b
                 torch.cuda.empty_cache()

@@ -17,7 +17,7 @@ to --out):
                                 FormantNormalizer's stages (pitchnorm.f0_track, ops.formant_tracks,
                                 ops.formant_centre, ops.pole_warp with its status counts) and its whole call
   step_plain_ms, step_formant_norm_ms, step_formant_norm_psola_ms
-                                GenderBrain.fit_batch, and GenderFormantNormBrain.fit_batch without and with the PSOLA
+                                the plain recipe's fit_batch, and the formant_norm recipe's without and with the PSOLA
                                 stage, on the same synthetic batch"""
 import argparse
 import os
@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from tools.bench_common import time_calls, write_line  # noqa: E402
+from tools.bench_common import bench_brain, time_calls, write_line  # noqa: E402
 
 SR = 16000
 
@@ -54,8 +54,7 @@ def main():
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
     import speech_anonymization_amd  # noqa: F401  (registers the package name)
-    from speech_anonymization_amd import data, formantnorm, gender, ops, pitchnorm
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, formantnorm, ops, pitchnorm
     B, N = a.B, int(a.seconds * SR)
     wav, lens = voiced_rows(B, N).to(dev), torch.ones(B, device=dev)
     nv = torch.full((B,), N, dtype=torch.int32, device=dev)
@@ -100,23 +99,11 @@ def main():
     if not a.no_step:
         batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
         with tempfile.TemporaryDirectory() as tmp:
-            def brain(cls, fname, psola=False):
-                with open(os.path.join(ROOT, "speechbrain_configs", fname)) as f:
-                    st_ = load_hyperpyyaml(f, {"output_folder": tmp, "batch_size": B})
-                hp = dict(st_, **gender.build(st_))
-                if cls is gender.GenderFormantNormBrain:
-                    opts, pitch = formantnorm.check_recipe_options(dict(st_, pitch_norm=psola), {}, {})
-                    hp["formant_normalizer"] = formantnorm.FormantNormalizer(**opts)
-                    hp["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pitch) if pitch else None
-                b = cls(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp, run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
-                return b
-            fname = "gender_classifier_formant_norm.yaml"
-            for name, cls, cfg, psola in (("step_plain_ms", gender.GenderBrain, "gender_classifier.yaml", False),
-                                          ("step_formant_norm_ms", gender.GenderFormantNormBrain, fname, False),
-                                          ("step_formant_norm_psola_ms", gender.GenderFormantNormBrain, fname, True)):
-                b = brain(cls, cfg, psola)
+            fname = "gender_classifier_train_formant_norm"
+            for name, cfg, over in (("step_plain_ms", "gender_classifier_train", None),
+                                    ("step_formant_norm_ms", fname, {"pitch_norm": False}),
+                                    ("step_formant_norm_psola_ms", fname, {"pitch_norm": True})):
+                b = bench_brain(cfg, B, tmp, over)
                 res[name] = round(time_calls(lambda: b.fit_batch(batch), a.warmup, a.steps), 4)
                 del b
                 torch.cuda.empty_cache()

@@ -11,8 +11,8 @@ to --out):
                                 anonymize.py's stages in this mode: McAdams.__call__ (the launch and the status
                                 counts), the --report_f0 tracker, the copy of the batch to the host
   step_plain_ms, step_mcadams_ms
-                                GenderBrain.fit_batch, and GenderPitchNormBrain.fit_batch with the transform as its
-                                waveform hook, on the same batch"""
+                                GenderBrain.fit_batch without and with the transform among its waveform_transforms
+                                (the plain and the mcadams recipe), on the same batch"""
 import argparse
 import os
 import sys
@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from tools.bench_common import time_calls, write_line  # noqa: E402
+from tools.bench_common import bench_brain, time_calls, write_line  # noqa: E402
 
 SR = 16000
 
@@ -41,8 +41,7 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, gender, mcadams, ops, pitchnorm
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, mcadams, ops, pitchnorm
     from tests import mcadams_ref as M
     B, N = a.B, int(a.seconds * SR)
     batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
@@ -76,19 +75,9 @@ def main():
 
     if not a.no_step:
         with tempfile.TemporaryDirectory() as tmp:
-            def brain(cls, fn):
-                with open(os.path.join(ROOT, "speechbrain_configs", fn)) as f:
-                    st = load_hyperpyyaml(f, {"output_folder": tmp, "batch_size": B})
-                hp = dict(st, **gender.build(st))
-                if cls is gender.GenderPitchNormBrain:
-                    hp["pitch_normalizer"] = mcadams.McAdams(**mcadams.check_recipe_options(st, {}, {}))
-                b = cls(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp, run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
-                return b
-            for name, cls, fn in (("step_plain_ms", gender.GenderBrain, "gender_classifier.yaml"),
-                                  ("step_mcadams_ms", gender.GenderPitchNormBrain, "gender_classifier_mcadams.yaml")):
-                b = brain(cls, fn)
+            for name, fn in (("step_plain_ms", "gender_classifier_train"),
+                             ("step_mcadams_ms", "gender_classifier_train_mcadams")):
+                b = bench_brain(fn, B, tmp)
                 out[name] = round(time_calls(lambda: b.fit_batch(batch), a.warmup, a.steps), 4)
                 del b
                 torch.cuda.empty_cache()

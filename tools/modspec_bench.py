@@ -14,8 +14,8 @@ to --out):
   stage_stft_ms, stage_smooth_ms, stage_istft_ms, smoother_ms
                                      ModulationSmoother's stages (pitchnorm.padded_stft, ops.modspec_smooth,
                                      ops.gl_istft) and its whole call
-  step_plain_ms, step_modspec_ms     GenderBrain.fit_batch, and GenderPitchNormBrain.fit_batch with the smoother as its
-                                     waveform transform, on the same synthetic batch"""
+  step_plain_ms, step_modspec_ms     GenderBrain.fit_batch without and with the smoother among its
+                                     waveform_transforms (the plain and the modspec recipe), on the same synthetic batch"""
 import argparse
 import os
 import sys
@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from tools.bench_common import time_calls, write_line  # noqa: E402
+from tools.bench_common import bench_brain, time_calls, write_line  # noqa: E402
 
 SR = 16000
 
@@ -65,8 +65,7 @@ def main():
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
     import speech_anonymization_amd  # noqa: F401  (registers the package name)
-    from speech_anonymization_amd import data, gender, modspec, ops, pitchnorm, vocoder
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, modspec, ops, pitchnorm, vocoder
     B, N = a.B, int(a.seconds * SR)
     wav, lens = modulated_rows(B, N).to(dev), torch.ones(B, device=dev)
     _, R = pitchnorm.padded_stft(wav)
@@ -105,20 +104,10 @@ def main():
     if not a.no_step:
         batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
         with tempfile.TemporaryDirectory() as tmp:
-            def brain(cls, fname):
-                with open(os.path.join(ROOT, "speechbrain_configs", fname)) as f:
-                    st_ = load_hyperpyyaml(f, {"output_folder": tmp, "batch_size": B})
-                hp = dict(st_, **gender.build(st_))
-                if cls is gender.GenderPitchNormBrain:
-                    opts = modspec.check_recipe_options(dict(st_, modspec_cutoff_hz=a.cutoff_hz), {}, {})
-                    hp["pitch_normalizer"] = modspec.ModulationSmoother(**opts)
-                b = cls(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp, run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
-                return b
-            for name, cls, cfg in (("step_plain_ms", gender.GenderBrain, "gender_classifier.yaml"),
-                                   ("step_modspec_ms", gender.GenderPitchNormBrain, "gender_classifier_modspec.yaml")):
-                b = brain(cls, cfg)
+            for name, cfg, over in (("step_plain_ms", "gender_classifier_train", None),
+                                    ("step_modspec_ms", "gender_classifier_train_modspec",
+                                     {"modspec_cutoff_hz": a.cutoff_hz})):
+                b = bench_brain(cfg, B, tmp, over)
                 res[name] = round(time_calls(lambda: b.fit_batch(batch), a.warmup, a.steps), 4)
                 del b
                 torch.cuda.empty_cache()

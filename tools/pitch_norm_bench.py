@@ -13,7 +13,7 @@ to --out):
   stage_*_ms             sa_yin_f0, sa_pitch_ratio, vocoder.stft, sa_pitch_stretch_mag, GriffinLim, sa_pitch_resample
                          at the ratios of the batch, and normalizer_ms, the whole call with its one host copy
   step_plain_ms, step_pitch_norm_ms
-                         GenderBrain.fit_batch and GenderPitchNormBrain.fit_batch on the same batch"""
+                         the plain and the pitch_norm recipe's fit_batch on the same batch"""
 import argparse
 import os
 import sys
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-from tools.bench_common import time_calls, write_line  # noqa: E402
+from tools.bench_common import bench_brain, time_calls, write_line  # noqa: E402
 
 SR, HOP, W, TAU_MIN, TAU_MAX = 16000, 160, 400, 40, 266
 
@@ -64,8 +64,7 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, gender, ops, pitchnorm, vocoder
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, ops, pitchnorm, vocoder
     B, N = a.B, int(a.seconds * SR)
     batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
     wav_cpu, lens_cpu = batch.sig
@@ -102,20 +101,9 @@ def main():
 
     if not a.no_step:
         with tempfile.TemporaryDirectory() as tmp:
-            def brain(cls, fn):
-                with open(os.path.join(ROOT, "speechbrain_configs", fn)) as f:
-                    st = load_hyperpyyaml(f, {"output_folder": tmp, "batch_size": B})
-                hp = dict(st, **gender.build(st))
-                if cls is gender.GenderPitchNormBrain:
-                    hp["pitch_normalizer"] = pitchnorm.PitchNormalizer(**pitchnorm.check_pitch_options(st, {}, {}))
-                b = cls(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp, run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
-                return b
-            for name, cls, fn in (("step_plain_ms", gender.GenderBrain, "gender_classifier.yaml"),
-                                  ("step_pitch_norm_ms", gender.GenderPitchNormBrain,
-                                   "gender_classifier_pitch_norm.yaml")):
-                b = brain(cls, fn)
+            for name, fn in (("step_plain_ms", "gender_classifier_train"),
+                             ("step_pitch_norm_ms", "gender_classifier_train_pitch_norm")):
+                b = bench_brain(fn, B, tmp)
                 out[name] = round(time_calls(lambda: b.fit_batch(batch), a.warmup, a.steps), 4)
                 del b
                 torch.cuda.empty_cache()

@@ -12,8 +12,8 @@ writes it to --out); per tempo (``tempo_0.5`` ...):
   jumps                         the windows of the batch that do not continue their predecessor, over all windows
   scaler_ms                     TimeScaler(tempo) with the lengths on the CPU, the whole call
   pv_synth_ms                   ops.pv_synth of the batch's STFT to round((T - 1) / tempo) + 1 frames (no STFT, no ISTFT)
-and once:  psola_ms (ops.psola at ratio 1 with the tracker's f0),  step_ms (GenderTempoBrain.fit_batch at tempo 0.8),
-step_plain_ms (GenderBrain.fit_batch on the same batch)."""
+and once:  psola_ms (ops.psola at ratio 1 with the tracker's f0),  step_ms (the tempo recipe's fit_batch at tempo 0.8),
+step_plain_ms (GenderBrain.fit_batch without the scaler, on the same settings and batch)."""
 import argparse
 import os
 import sys
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-from tools.bench_common import time_calls, write_line  # noqa: E402
+from tools.bench_common import bench_brain, time_calls, write_line  # noqa: E402
 
 SR = 16000
 TEMPOS = (0.5, 0.8, 1.25)
@@ -40,8 +40,7 @@ def main():
     a = ap.parse_args()
     assert a.steps >= 20, "the median of at least 20 calls"
     dev = torch.device("cuda:0")
-    from speech_anonymization_amd import data, gender, ops, pitchnorm, timescale
-    from speech_anonymization_amd.yaml_loader import load_hyperpyyaml
+    from speech_anonymization_amd import data, ops, pitchnorm, timescale
     B, N = a.B, int(a.seconds * SR)
     batch = next(iter(data.synthetic_gender_dataset(B, B, n_samples=N)))
     wav, lens = batch.sig[0].to(dev).contiguous(), batch.sig[1].float()
@@ -76,14 +75,8 @@ def main():
 
     if not a.no_step:
         with tempfile.TemporaryDirectory() as tmp:
-            for name, brain in (("step_ms", gender.GenderTempoBrain), ("step_plain_ms", gender.GenderBrain)):
-                with open(os.path.join(ROOT, "speechbrain_configs", "gender_classifier_tempo.yaml")) as f:
-                    st = load_hyperpyyaml(f, {"output_folder": tmp, "batch_size": B})
-                hp = dict(st, **gender.build(st))
-                hp["time_scaler"] = timescale.TimeScaler(**timescale.check_recipe_options(st, {}, {}))
-                b = brain(modules=hp["modules"], opt_class=hp["opt_class"], hparams=hp, run_opts={"device": "cuda:0"})
-                b.on_fit_start()
-                b.modules.train()
+            for name, plain in (("step_ms", False), ("step_plain_ms", True)):
+                b = bench_brain("gender_classifier_train_tempo", B, tmp, plain=plain)
                 out[name] = tm(lambda: b.fit_batch(batch))
                 del b
                 torch.cuda.empty_cache()
